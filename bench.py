@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the sdrx hot path on MI355X, one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|decim64|chan32|chan128|cfg4|fi64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|decim64|chan32|chan128|cfg4|fi64] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no torchrun around it: bench.py itself starts N worker processes (one per GPU, RANK /
@@ -14,6 +14,10 @@ the 32-channel DownChannelizer bank (configs[2], 61.44 MS/s-shaped stream) over 
 samples per second that went through BOTH (batch x steps / elapsed).  Every rank owns one GPU and one independent
 stream (streams shard, no collective on the data path); per-GPU work is fixed -> "weak" scaling.
 `also.chan128` is BASELINE configs[4]'s per-GPU share (128 channels per stream), measured with the same protocol.
+`--dump-outputs DIR`: after the K timed steps, what the last of them computed goes to DIR/<name>.npy (decimator output and
+every channel's output as (n, 2) I/Q rows, cfg4's demodulator front per channel; float32, < 64 MB in all, a seeded sample
+of rows where the step computed more).  The input batch is seeded, so two builds run with the same arguments compare output
+for output.
 
 roofline : per kernel, ALGORITHMIC bytes (4 B read + 4/2^n B written per input sample and channel)
            / its average duration from HIP events on the launch stream (sdrx_*_get_timing) against 8 TB/s HBM3E.
@@ -222,6 +226,36 @@ def load_traffic(kernel: str, batch: int, workload: str):
     return best
 
 
+DUMP_BYTES = 60_000_000        # --dump-outputs: data bytes in all (the .npy headers come on top; < 64 MB together)
+DUMP_SEED = 20240611           # the rows kept of an array too large for its share: fixed, so equal lengths give equal rows
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write name -> host array as out_dir/<name>.npy: integer samples as float32 (exact for int16), float64 kept.  The budget is
+    shared out smallest first; an array larger than its share keeps a seeded sample of its rows (axis 0, sorted, so an I/Q pair
+    stays together).  Returns name -> (rows written, rows computed)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = []
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        items.append((name, a))
+    items.sort(key=lambda it: it[1].nbytes)
+    left, written = DUMP_BYTES, {}
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        rows = a.shape[0] if a.ndim else 1
+        row_bytes = max(1, a.nbytes // max(rows, 1))
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, share // row_bytes, replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+        written[name] = (a.shape[0] if a.ndim else 1, rows)
+    return written
+
+
 # ------------------------------------------------------------------------------------------------ N-rank launcher
 def spawn_ranks(n: int, argv) -> int:
     """`python bench.py --gpus N` without torchrun: N worker processes, one per GPU.  Called before this process has
@@ -293,7 +327,12 @@ def main():
                          "(sdrx_decim_process_dev_batch); the bank part keeps one stream")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (decimator output, every channel's "
+                         "output) to DIR/<name>.npy as float32, at most 64 MB in all (a seeded sample of rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))       # nothing above touched HIP
@@ -310,6 +349,8 @@ def main():
         buf = np.arange(1 << 16, dtype=np.int64) + rank
         acc = []
         el = shard.timed_region(lambda: acc.append(int(buf.sum())), args.steps, args.warmup, lambda: None, dist=dist)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {(f"rank{rank}_" if world > 1 else "") + "launchcheck_sum": np.array([acc[-1]], np.float64)})
         if rank == 0:
             print(json.dumps({"metric": "launcher self-test (host-only step, no GPU work)", "value": round(world * args.steps * buf.size / el / 1e6, 1),
                               "unit": "MS/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 4),
@@ -373,6 +414,11 @@ def main():
 
     S = max(1, args.streams_per_gpu)
     timed_handles = {}                          # name -> (handle, algorithmic bytes per sample, samples per step)
+    # --dump-outputs: the device output buffers of the step and the #complex outputs of its last call; `hold` is set for the
+    # last timed step only, whose bank outputs then stay queued (not skipped) until the dump has read them
+    dev_outs = {}
+    n_outs = {}
+    hold = [False]
 
     def make_decim(n):
         """decimate64_cen over n samples as S independent streams, one (batched) launch"""
@@ -380,7 +426,10 @@ def main():
             h = sa.Decimators(6, sa.FC_CEN, 12, device=dev.index)
             out = torch.empty(2 * (n >> 6) + 64, dtype=torch.int16, device=dev)
             h.set_stream(stream)
-            return h, (lambda: h.decimate_dev(x.data_ptr(), 2 * n, out.data_ptr())), [h, out]
+            dev_outs["decim64"] = [out]
+            def run():
+                n_outs["decim64"] = [h.decimate_dev(x.data_ptr(), 2 * n, out.data_ptr())]
+            return h, run, [h, out]
         per = (n // S) & ~1023
         hs = [sa.Decimators(6, sa.FC_CEN, 12, device=dev.index) for _ in range(S)]
         hs[0].set_stream(stream)
@@ -388,7 +437,10 @@ def main():
         ins = [x.data_ptr() + 4 * per * i for i in range(S)]
         optr = [o.data_ptr() for o in outs]
         cnt = [2 * per] * S
-        return hs[0], (lambda: sa.decimate_dev_batch(hs, ins, cnt, optr)), [hs, outs]
+        dev_outs["decim64"] = outs
+        def run_batch():
+            n_outs["decim64"] = sa.decimate_dev_batch(hs, ins, cnt, optr)
+        return hs[0], run_batch, [hs, outs]
 
     def make_bank(n_ch, kind):
         fcs = chan_centres(n_ch, kind)
@@ -397,6 +449,7 @@ def main():
         return b, fcs
 
     be = None
+    bank = None
     fcs = None
     if wl == "fi64":
         # DecimatorsFI::decimate64_cen (AirspyHF thread), float I/Q in, int16 Samples out
@@ -407,7 +460,9 @@ def main():
         h = sa.FloatDecimators("fi", 6, sa.FC_CEN, device=dev.index)
         out = torch.empty(2 * (B >> 6) + 64, dtype=torch.int16, device=dev)
         h.set_stream(stream)
-        step = lambda: h.decimate_dev(x.data_ptr(), 2 * B, out.data_ptr())
+        dev_outs["fdecim64"] = [out]
+        def step():
+            n_outs["fdecim64"] = [h.decimate_dev(x.data_ptr(), 2 * B, out.data_ptr())]
         timed_handles["fdecim"] = (h, 8.0 + 4.0 / 64, None)
         workload = f"8f.4: DecimatorsFI::decimate64_cen (IntHalfbandFilterEOF<64> x 6), one stream per GPU, {B} complex float32 samples per step, device-resident"
     elif wl == "decim64":
@@ -420,8 +475,9 @@ def main():
         def step():
             dstep()
             bank.feed_dev(x.data_ptr(), B)
-            for c in range(32):               # consumer side: drop the queued outputs (host bookkeeping only)
-                bank.skip(c)
+            if not hold[0]:
+                for c in range(32):           # consumer side: drop the queued outputs (host bookkeeping only)
+                    bank.skip(c)
         bps_b, d2_b = bank_figures(bank, 32)
         timed_handles["decim64"] = (h, 4.0 + 4.0 / 64, 32.5)
         timed_handles["chan32"] = (bank, bps_b, d2_b)
@@ -444,8 +500,9 @@ def main():
                 be.feed_bank(bank)               # device-ordered hand-over; the back-end runs on its own stream
                 if os.environ.get("SDRX_BENCH_CFG4_SERIAL"):
                     be.sync()                    # default since round 3: the back-end of step k overlaps the channelizer of step k + 1 (6.29 vs 6.54 ms/step)
-            for c in range(n_ch):
-                bank.skip(c)
+            if not hold[0]:
+                for c in range(n_ch):
+                    bank.skip(c)
         bps_b, d2_b = bank_figures(bank, n_ch)
         if be is not None:
             bps_b += n_ch * 4.0 * 48000 / 61_440_000
@@ -458,7 +515,33 @@ def main():
         step()
     sync = (lambda: (be.sync(), torch.cuda.synchronize(dev))) if be is not None else (lambda: torch.cuda.synchronize(dev))
     sync()
-    elapsed = shard.timed_region(step, args.steps, 0, sync, dist=dist, device=red_dev)
+    timed_step = step
+    if args.dump_outputs:
+        left = [args.steps]
+        def timed_step():
+            left[0] -= 1
+            hold[0] = left[0] == 0
+            step()
+    elapsed = shard.timed_region(timed_step, args.steps, 0, sync, dist=dist, device=red_dev)
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: int16 I/Q rows (I, Q) of the decimator and of every
+        # channel, and for cfg4 the demodulator front's float output per channel
+        hold[0] = False
+        got = {}
+        for name, outs in dev_outs.items():
+            for i, (o, n) in enumerate(zip(outs, n_outs[name])):
+                got[name + (f"_s{i}" if len(outs) > 1 else "")] = o[: 2 * n].view(-1, 2).cpu().numpy()
+        if bank is not None:
+            tag = "chan32" if wl == "headline" else wl
+            for c in range(bank.n_ch):
+                got[f"{tag}_ch{c:03d}"] = bank.read(c).reshape(-1, 2)
+        if be is not None:
+            be.sync()
+            for c in range(be.n_ch):
+                got[f"{wl}_demod_ch{c:03d}"] = be.read(c)
+        pre = f"rank{rank}_" if world > 1 else ""
+        dumped = dump_outputs(args.dump_outputs, {pre + k: v for k, v in got.items()})
     # median of >= 10 individually timed steps (each bracketed by a device synchronisation) next to the mean above
     singles = []
     for _ in range(max(10, args.steps)):
@@ -619,6 +702,9 @@ def main():
         }
         if also:
             line["also"] = also
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": len(dumped),
+                                    "sampled": sum(1 for w, n in dumped.values() if w < n)}
         if n_gpus == 1:
             # the denominator twice -- datasheet (peak/frac above) and a read-only streaming kernel on this box
             del x
