@@ -22,13 +22,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "hb_consts.hpp"
 
 namespace sdrx {
 
 enum { MODE_CEN = 0, MODE_INF = 1, MODE_SUP = 2 };   // == SDRX_MODE_CENTER / LOWER / UPPER
 
 constexpr int HB_SHIFT = 12;
-constexpr int HIST = 32;           // history entries kept in front of every polyphase array
 
 template<int ORDER> __host__ __device__ constexpr int hb_pairs() { return ORDER / 4; }
 
@@ -82,11 +82,6 @@ __device__ __forceinline__ int centre_shl(uint32_t v)
     else
         asm("v_lshlrev_b32_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(r) : "s"(HB_SHIFT - 1), "v"(v));
     return r;
-}
-
-__host__ __device__ constexpr uint32_t pk16(int lo, int hi)
-{
-    return (uint32_t)(uint16_t)(int16_t)lo | ((uint32_t)(uint16_t)(int16_t)hi << 16);
 }
 
 // Packed tap pair for output r (0..7) and window dword d (0..19) of stage_pk16_r8.

@@ -27,8 +27,6 @@ namespace sdrx {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t HBM_BIAS2 = 0x00800080u;      // XORed into every packed odd-arm dword an MFMA stage reads
-
 __host__ __device__ constexpr int tap_lo8(int h) { int l = ((h % 256) + 256) % 256; return l >= 128 ? l - 256 : l; }
 __host__ __device__ constexpr int tap_hi8(int h) { return (h - tap_lo8(h)) / 256; }
 

@@ -12,13 +12,12 @@
 // phase (no drop) and C division toward zero for the channelizer.
 #include "sdrx_common.hpp"
 #include "hb_common.hpp"
+#include "chan_plan.hpp"
 #include <new>
 #include <vector>
 #include <cstring>
 
 using namespace sdrx;
-
-extern "C" int sdrx_chan_plan(int32_t in_rate, int32_t req_rate, int32_t req_fc, uint8_t* modes, int32_t* out_rate, int32_t* residual_ofs);
 
 namespace {
 
@@ -507,7 +506,7 @@ int sdrx_chan24_bank_create(sdrx_chan24_bank_t** out, int device, int32_t in_rat
     rc = w_init(&b->e, device);
     for (int c = 0; c < n_ch && !rc; c++) {
         uint8_t modes[32]; int32_t orate = 0, ofs = 0;
-        const int n = sdrx_chan_plan(in_rate, req_rate[c], req_fc[c], modes, &orate, &ofs);     // the float bisection (downchannelizer.cpp:250-287)
+        const int n = plan_chain(in_rate, req_rate[c], req_fc[c], modes, MAX_STAGES, &orate, &ofs);     // the float bisection (downchannelizer.cpp:250-287)
         w_add_chain(&b->e, n, modes);
         b->e.chains.back().out_rate = orate; b->e.chains.back().ofs = ofs;
     }
