@@ -38,7 +38,7 @@ def _rand_cfg(rng):
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SDRX_FUZZ_SEEDS", "6"))))      # a soak run sets SDRX_FUZZ_SEEDS=200
-def test_random_operation_sequences(seed):
+def test_random_operation_sequences(seed, hb_engine):
     rng = np.random.default_rng(1000 + seed)
     x = synth.noise_iq(600_000, 70 + seed, 32767)
     x[::9] = -32768
@@ -61,6 +61,8 @@ def test_random_operation_sequences(seed):
                 pos = 0
             seg = x[2 * pos: 2 * (pos + n)]; pos += n
             bank.feed(seg)
+            if n and any(len(m.modes) and not m.dead for m in model):     # a live channel with stages: its group launched
+                assert bank.last_launch()["kernel"] == f"tree_kernel<{hb_engine}>", (seed, op_i)
             for m in model:
                 m.feed(seg)
         elif op == "read" and live:

@@ -18,6 +18,11 @@ def cfg3_channels(n_ch=32):
     return [48000] * n_ch, [int(v) for v in fc]
 
 
+def assert_engine(bank, engine):
+    """the engine conftest's hb_engine parameter asked for is the one that ran (the bank reads the switch at plan time)"""
+    assert bank.last_launch()["kernel"] == f"tree_kernel<{engine}>"
+
+
 def oracle_bank(in_rate, rates, fcs):
     chains = []
     for r, f in zip(rates, fcs):
@@ -38,7 +43,7 @@ def test_plan_matches_oracle():
 
 
 @pytest.mark.parametrize("amp,tone", [(2047, (0.0123, 600)), (32767, None), (20000, (0.2501, 12000))])
-def test_bank32_matches_oracle_ragged_feeds(amp, tone):
+def test_bank32_matches_oracle_ragged_feeds(amp, tone, hb_engine):
     rates, fcs = cfg3_channels(32)
     n = 1 << 20
     x = orc.synth_iq(n, seed=21, amp=amp, tone=tone)
@@ -54,6 +59,8 @@ def test_bank32_matches_oracle_ragged_feeds(amp, tone):
     for a, b in zip(cuts[:-1], cuts[1:]):
         seg = x[2 * a: 2 * b]
         bank.feed(seg)
+        if a == 0 and b > 0:
+            assert_engine(bank, hb_engine)
         for c, (chain, *_r) in enumerate(ref):
             want[c].append(chain.feed(seg))
     for c in range(len(ref)):
@@ -64,7 +71,7 @@ def test_bank32_matches_oracle_ragged_feeds(amp, tone):
         assert bank.available(c) == 0
 
 
-def test_mixed_depths_shared_prefixes_and_passthrough():
+def test_mixed_depths_shared_prefixes_and_passthrough(hb_engine):
     # different requested rates -> chains of different length sharing prefixes; one 0-stage channel
     in_rate = 2_400_000
     rates = [48000, 48000, 200000, 12500, 1_200_000, 2_400_000, 300000, 8000, 48000]
@@ -76,18 +83,21 @@ def test_mixed_depths_shared_prefixes_and_passthrough():
     assert any(len(r[1]) == 0 for r in ref)              # the pass-through case is present
     for a, b in [(0, 123457), (123457, 123458), (123458, n)]:
         bank.feed(x[2 * a: 2 * b])
+        if a == 0:
+            assert_engine(bank, hb_engine)
     for c, (chain, modes, *_r) in enumerate(ref):
         w = chain.feed(x)
         got = bank.read(c)
         assert np.array_equal(got, w), (c, modes)
 
 
-def test_partial_reads_and_reconfigure():
+def test_partial_reads_and_reconfigure(hb_engine):
     rates, fcs = cfg3_channels(8)
     x = orc.synth_iq(400_000, seed=4, amp=2047, tone=(0.11, 900))
     bank = sa.ChannelizerBank(FS, rates, fcs)
     ref = oracle_bank(FS, rates, fcs)
     bank.feed(x[: 2 * 250_000])
+    assert_engine(bank, hb_engine)
     w0 = ref[0][0].feed(x[: 2 * 250_000])
     part = bank.read(0, 10)
     assert np.array_equal(part, w0[:20])
@@ -110,14 +120,16 @@ def test_partial_reads_and_reconfigure():
     assert np.array_equal(bank.read(5), orc.Chain(ref[5][1]).feed(x[: 2 * 100_000]))
 
 
-def test_bank256_cfg4_shape_spot_check():
+def test_bank256_cfg4_shape_spot_check(hb_engine):
     """256 channels (SURVEY cfg 4 spacing): planner splits the wide trie over several passes; check a spread of channels"""
     n_ch = 256
     k = np.arange(n_ch)
     fcs = [int(v) for v in (-25_000_000 + k * (50_000_000 / 255))]
     bank = sa.ChannelizerBank(FS, [48000] * n_ch, fcs)
     x = orc.synth_iq(1 << 20, seed=33, amp=2047, tone=(0.07, 700))
-    bank.feed(x[: 2 * 400_003]); bank.feed(x[2 * 400_003:])
+    bank.feed(x[: 2 * 400_003])
+    assert_engine(bank, hb_engine)
+    bank.feed(x[2 * 400_003:])
     for c in (0, 1, 17, 100, 127, 128, 200, 254, 255):
         modes, out_rate, ofs = orc.chan_plan(FS, 48000, fcs[c])
         m, r, o = bank.info(c)
@@ -125,7 +137,7 @@ def test_bank256_cfg4_shape_spot_check():
         assert np.array_equal(bank.read(c), orc.Chain(modes).feed(x)), c
 
 
-def test_retune_fifty_times_stays_exact_and_bounded():
+def test_retune_fifty_times_stays_exact_and_bounded(hb_engine):
     """A live session retunes (DownChannelizer::configure per retune, downchannelizer.cpp:44-48): every reconfigure restarts
     that channel from zero history; the bank must not accumulate dead stage tries (launches and device memory per feed
     stay bounded) and the other channels must never notice."""
@@ -145,6 +157,8 @@ def test_retune_fifty_times_stays_exact_and_bounded():
         m, r, o = bank.info(2)
         assert np.array_equal(m, modes) and (r, o) == (out_rate, ofs)
         bank.feed(seg)
+        if i == 0:
+            assert_engine(bank, hb_engine)
         assert np.array_equal(bank.read(2), orc.Chain(modes).feed(seg)), i     # a FRESH chain each time
         for c in (0, 1, 3, 4, 5):
             other[c].append(bank.read(c))
@@ -156,13 +170,14 @@ def test_retune_fifty_times_stays_exact_and_bounded():
     assert bank.group_count == 6
 
 
-def test_add_and_remove_channel_leave_the_others_alone():
+def test_add_and_remove_channel_leave_the_others_alone(hb_engine):
     rates, fcs = cfg3_channels(4)
     bank = sa.ChannelizerBank(FS, rates, fcs)
     ref = oracle_bank(FS, rates, fcs)
     x = orc.synth_iq(300_000, seed=77, amp=2047, tone=(0.02, 900))
     a, b = x[: 2 * 100_001], x[2 * 100_001:]
     bank.feed(a)
+    assert_engine(bank, hb_engine)
     c_new = bank.add_channel(48000, 7_654_321)                      # addThreadedSink on a running device set
     assert c_new == 4 and bank.group_count == 2
     modes, out_rate, ofs = orc.chan_plan(FS, 48000, 7_654_321)
@@ -181,7 +196,7 @@ def test_add_and_remove_channel_leave_the_others_alone():
 
 
 @pytest.mark.parametrize("levels,lds_kb", [(8, 80), (10, 150)])
-def test_deep_pass_plans_stay_exact(levels, lds_kb, monkeypatch):
+def test_deep_pass_plans_stay_exact(levels, lds_kb, monkeypatch, hb_engine):
     """SDRX_CHAN_MAX_LEVELS / SDRX_CHAN_LDS_KB (the experiment of DESIGN 4.3: deeper first pass, fewer node-stream bytes):
     more than six levels per pass need several warm-up chunks and a longer stream history -- same samples"""
     monkeypatch.setenv("SDRX_CHAN_MAX_LEVELS", str(levels))
@@ -196,6 +211,8 @@ def test_deep_pass_plans_stay_exact(levels, lds_kb, monkeypatch):
     for a, b in zip(cuts[:-1], cuts[1:]):
         seg = x[2 * a: 2 * b]
         bank.feed(seg)
+        if a == 0 and b > 0:
+            assert_engine(bank, hb_engine)
         for c, (chain, *_r) in enumerate(ref):
             got = bank.read(c)
             assert np.array_equal(got, chain.feed(seg)), (levels, c, a, b)

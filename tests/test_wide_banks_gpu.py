@@ -18,6 +18,7 @@ import sdrangel_amd as sa
 from tests import oracle_py as orc
 from tests import synth
 from tests.test_backend_gpu import mk, ulp_diff
+from tests.test_chan_gpu import assert_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +31,7 @@ def spaced(n_ch, lo, span):
     return [int(v) for v in (lo + k * (span / (n_ch - 1)) + 137 * k).astype(np.int64)]
 
 
-def test_cfg5_bank128_all_channels_ragged_feeds():
+def test_cfg5_bank128_all_channels_ragged_feeds(hb_engine):
     n_ch = 128
     fcs = spaced(n_ch, -15_000_000, 30_000_000)            # bench.py --workload chan128 uses exactly these centres
     n = (1 << 20) + 4099
@@ -47,6 +48,8 @@ def test_cfg5_bank128_all_channels_ragged_feeds():
     cuts = [0, 3, 4096, 250_001, 250_001, 777_777, n]
     for a, b in zip(cuts[:-1], cuts[1:]):
         bank.feed(x[2 * a: 2 * b])
+        if a == 0 and b > 0:
+            assert_engine(bank, hb_engine)
     want = list(POOL.map(lambda p: orc.Chain(p[0]).feed(x), plans))
     bad = []
     for c in range(n_ch):
@@ -57,7 +60,7 @@ def test_cfg5_bank128_all_channels_ragged_feeds():
 
 
 @pytest.mark.parametrize("schedule", ["dyadic", "serial"])
-def test_cfg4_full_width_256_channels_bank_to_backend(schedule, monkeypatch):
+def test_cfg4_full_width_256_channels_bank_to_backend(schedule, monkeypatch, hb_engine):
     n_ch = 256
     k = np.arange(n_ch)
     fcs = [int(v) for v in (-25_000_000 + k * (50_000_000 / 255))]            # bench.py --workload cfg4
@@ -82,6 +85,8 @@ def test_cfg4_full_width_256_channels_bank_to_backend(schedule, monkeypatch):
     got = [[] for _ in range(n_ch)]
     for seg in segs:
         bank.feed(seg)
+        if seg is segs[0]:
+            assert_engine(bank, hb_engine)
         be.feed_bank(bank)                                   # device-ordered hand-over, no host sync in between
         for c in range(n_ch):
             bank.skip(c)
