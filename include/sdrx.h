@@ -487,6 +487,73 @@ void* sdrx_fanout_buffer(sdrx_fanout_t* f, int32_t i);
 int sdrx_fanout_wait(sdrx_fanout_t* f, int32_t i);
 int sdrx_fanout_stream_wait(sdrx_fanout_t* f, int32_t i, void* consumer_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SpectrumVis (sdrgui/dsp/spectrumvis.{h,cpp}:70-300, v4.0.6, kissfft engine: sdrbase/dsp/kissfft.h, fftwindow.{h,cpp},
+ * util/movingaverage2d.h, util/fixedaverage2d.h): the spectrum / waterfall sink a device set feeds with every raw span
+ * (dspdevicesourceengine.cpp:360-363).  Each frame the reference hands to GLSpectrum::newSpectrum(powerSpectrum, N) is
+ * queued on the device until read: N floats, fft-shifted (with positive_only: bin i at 2i and 2i+1), dB or linear.
+ *   - frames, linear output and the averaged power are bit-identical to the reference (tests/golden/spectrum_golden.npz
+ *     is recorded from the reference's own SpectrumVis); dB output is m_mult * log2f(v) + m_ofs with log2f evaluated in
+ *     double and rounded once.  That log2f differs from glibc's by 1 ulp on about 1.5e-4 of inputs, and where the sum
+ *     cancels (values near 0 dB) one ulp of log2f becomes several ulps of the dB value: up to 16 ulp measured
+ *   - the 4096-entry buffer and its quirks are kept: with overlap, consecutive frames share no samples and the ends of
+ *     the frame hold the buffer's leftovers (zeros for a fresh object, older samples after a mid-stream configure)
+ *   - deliberate divergences, all rejected with SDRX_EINVAL before any device call: 2 * overlap >= fft_size (the
+ *     reference loops forever at 50 % and writes past its buffer above), a fft_size that is not a power of two after the
+ *     clamp to [64, 4096], a window or avg_mode outside the enums, a zero or non-finite scalef
+ *   - configure that changes fft_size while frames are queued fails with SDRX_ESTATE (read or skip them first)
+ *   - the queue has no cap: it grows by 4 * fft_size bytes per queued frame until the caller reads or skips the frames,
+ *     so a consumer that falls behind must drain it (sdrx_spectrum_read / sdrx_spectrum_skip) after every feed or so
+ * ------------------------------------------------------------------------------------------ */
+/* FFTWindow::Function (fftwindow.h) */
+#define SDRX_SPECTRUM_BARTLETT       0
+#define SDRX_SPECTRUM_BLACKMANHARRIS 1
+#define SDRX_SPECTRUM_FLATTOP        2
+#define SDRX_SPECTRUM_HAMMING        3
+#define SDRX_SPECTRUM_HANNING        4
+#define SDRX_SPECTRUM_RECTANGLE      5
+/* SpectrumVis::AveragingMode */
+#define SDRX_SPECTRUM_AVG_NONE   0
+#define SDRX_SPECTRUM_AVG_MOVING 1
+#define SDRX_SPECTRUM_AVG_FIXED  2
+typedef struct sdrx_spectrum sdrx_spectrum_t;
+typedef struct sdrx_spectrum_cfg {
+    int32_t  fft_size;          /* clamped to [64, 4096] like handleConfigure */
+    int32_t  overlap_percent;   /* clamped to [0, 100]; overlap = fft_size * pct / 100 */
+    uint32_t avg_nb;            /* averaging depth / block size; <= 1: no averaging */
+    int32_t  avg_mode;          /* SDRX_SPECTRUM_AVG_* */
+    int32_t  window;            /* SDRX_SPECTRUM_* window */
+    int32_t  linear;            /* 0: dB, 1: v / N^2 */
+    float    scalef;            /* SpectrumVis(Real scalef): 32768 for the 16-bit build */
+} sdrx_spectrum_cfg;
+/* SpectrumVis(scalef) + handleConfigure(cfg) */
+int sdrx_spectrum_create(sdrx_spectrum_t** out, int device, const sdrx_spectrum_cfg* cfg);
+int sdrx_spectrum_destroy(sdrx_spectrum_t* h);
+/* a freshly constructed object with the current configuration: zero buffer and averages, empty queue */
+int sdrx_spectrum_reset(sdrx_spectrum_t* h);
+/* handleConfigure: keeps the 4096-entry buffer, fill = overlap, zeroes the averages */
+int sdrx_spectrum_configure(sdrx_spectrum_t* h, const sdrx_spectrum_cfg* cfg);
+/* feed(begin, end, positiveOnly): n_cplx `Sample`s; partial frames carry across feeds */
+int sdrx_spectrum_feed(sdrx_spectrum_t* h, const int16_t* iq, int64_t n_cplx, int positive_only);
+/* same on a device pointer (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_spectrum_feed_dev(sdrx_spectrum_t* h, const int16_t* d_iq, int64_t n_cplx, int positive_only);
+/* frames queued (newSpectrum calls not yet read) */
+int64_t sdrx_spectrum_available(sdrx_spectrum_t* h);
+/* copies up to max_frames queued frames (fft_size floats each) in call order; returns the number copied */
+int64_t sdrx_spectrum_read(sdrx_spectrum_t* h, float* out, int64_t max_frames);
+/* drops up to n queued frames (n < 0: all); returns the number dropped */
+int64_t sdrx_spectrum_skip(sdrx_spectrum_t* h, int64_t n);
+/* FFTWindow::m_window of the current configuration; returns fft_size (copies min(cap, fft_size)) */
+int sdrx_spectrum_window(const sdrx_spectrum_t* h, float* out, int32_t cap);
+int sdrx_spectrum_sync(sdrx_spectrum_t* h);
+int sdrx_spectrum_set_stream(sdrx_spectrum_t* h, void* hip_stream);
+int sdrx_spectrum_get_stream(sdrx_spectrum_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels */
+int sdrx_spectrum_set_timing(sdrx_spectrum_t* h, int enabled);
+int sdrx_spectrum_get_timing(sdrx_spectrum_t* h, double* total_ms, int64_t* feeds, int reset);
+int sdrx_spectrum_last_launch(const sdrx_spectrum_t* h, char* kernel_name, int name_cap,
+                              int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

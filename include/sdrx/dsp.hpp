@@ -8,6 +8,7 @@
 //   DownChannelizer               (dsp/downchannelizer.h)  sdrx::DownChannelizerBank (N channels, one stream)
 //   SampleSinkFifo                (dsp/samplesinkfifo.h)   sdrx::SampleSinkFifo
 //   DecimatorsFI / FF / IF<T,B>   (dsp/decimatorsf*.h, decimatorsif.h)  sdrx::DecimatorsFI / DecimatorsFF / DecimatorsIF<T,B>
+//   SpectrumVis                   (sdrgui/dsp/spectrumvis.h)  sdrx::SpectrumVis (frames go to a callback, not a GLSpectrum)
 //
 // The reference keeps ONE set of six stage states per Decimators object, shared by all decimateK_* methods.  Here every
 // (K, fcPos) pair is a handle (created on first use) and the object carries a sdrx_decim_stages_t: when a call names another
@@ -17,8 +18,10 @@
 // Visible difference: DSP calls still return void -- a failing GPU call is logged to stderr and the output iterator does
 // not advance (the reference has no error path at all on these calls).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <vector>
 #include "../sdrx.h"
 
@@ -247,6 +250,63 @@ public:
     }
 private:
     sdrx_chan_bank_t* m_h;
+};
+
+// SpectrumVis (sdrgui/dsp/spectrumvis.{h,cpp}): configure() takes the reference's arguments (applied at once: there is no
+// message queue), feed() computes every frame the span completes and hands each one to the callback in call order, as
+// GLSpectrum::newSpectrum(powerSpectrum, fftSize) would receive it.  Window and averaging mode are the reference's enum values.
+class SpectrumVis {
+public:
+    typedef std::function<void(const std::vector<float>& spectrum, int fftSize)> NewSpectrum;
+
+    explicit SpectrumVis(float scalef, NewSpectrum newSpectrum = NewSpectrum(), int device = 0) : m_h(nullptr), m_cb(newSpectrum)
+    {
+        sdrx_spectrum_cfg c = { 1024, 0, 0, SDRX_SPECTRUM_AVG_NONE, SDRX_SPECTRUM_BLACKMANHARRIS, 0, scalef };   // the constructor's handleConfigure
+        m_cfg = c;
+        if (sdrx_spectrum_create(&m_h, device, &m_cfg) != SDRX_OK)
+            std::fprintf(stderr, "sdrx::SpectrumVis: %s\n", sdrx_last_error());
+    }
+    ~SpectrumVis() { if (m_h) sdrx_spectrum_destroy(m_h); }
+    SpectrumVis(const SpectrumVis&) = delete;
+    SpectrumVis& operator=(const SpectrumVis&) = delete;
+    bool ok() const { return m_h != nullptr; }
+    void setNewSpectrum(NewSpectrum cb) { m_cb = cb; }
+
+    bool configure(int fftSize, int overlapPercent, unsigned int averagingNb, int averagingMode, int window, bool linear)
+    {
+        sdrx_spectrum_cfg c = { fftSize, overlapPercent, averagingNb, averagingMode, window, linear ? 1 : 0, m_cfg.scalef };
+        deliver();                                                  // frames of the old size first
+        if (sdrx_spectrum_configure(m_h, &c) != SDRX_OK) { std::fprintf(stderr, "sdrx::SpectrumVis::configure: %s\n", sdrx_last_error()); return false; }
+        m_cfg = c;
+        return true;
+    }
+
+    void feed(const SampleVector::const_iterator& begin, const SampleVector::const_iterator& end, bool positiveOnly)
+    {
+        if (end == begin) return;
+        if (sdrx_spectrum_feed(m_h, reinterpret_cast<const int16_t*>(&*begin), (int64_t)(end - begin), positiveOnly ? 1 : 0) != SDRX_OK)
+            std::fprintf(stderr, "sdrx::SpectrumVis::feed: %s\n", sdrx_last_error());
+        deliver();
+    }
+private:
+    // all queued frames in one copy, then one callback per frame
+    void deliver()
+    {
+        const int n = sdrx_spectrum_window(m_h, nullptr, 0);
+        const int64_t k = sdrx_spectrum_available(m_h);
+        if (n <= 0 || k <= 0) return;
+        m_all.resize((size_t)k * (size_t)n);
+        const int64_t got = sdrx_spectrum_read(m_h, m_all.data(), k);
+        m_frame.resize((size_t)n);
+        for (int64_t f = 0; f < got; f++) {
+            std::copy(m_all.begin() + f * n, m_all.begin() + (f + 1) * n, m_frame.begin());
+            if (m_cb) m_cb(m_frame, n);
+        }
+    }
+    sdrx_spectrum_t* m_h;
+    sdrx_spectrum_cfg m_cfg;
+    NewSpectrum m_cb;
+    std::vector<float> m_all, m_frame;
 };
 
 class SampleSinkFifo {                             // dsp/samplesinkfifo.h:27-65

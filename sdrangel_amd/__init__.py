@@ -167,6 +167,22 @@ def lib() -> C.CDLL:
         "sdrx_fanout_buffer": (vp, [vp, i32]),
         "sdrx_fanout_wait": (C.c_int, [vp, i32]),
         "sdrx_fanout_stream_wait": (C.c_int, [vp, i32, vp]),
+        "sdrx_spectrum_create": (C.c_int, [pp, C.c_int, vp]),
+        "sdrx_spectrum_destroy": (C.c_int, [vp]),
+        "sdrx_spectrum_reset": (C.c_int, [vp]),
+        "sdrx_spectrum_configure": (C.c_int, [vp, vp]),
+        "sdrx_spectrum_feed": (C.c_int, [vp, vp, i64, C.c_int]),
+        "sdrx_spectrum_feed_dev": (C.c_int, [vp, vp, i64, C.c_int]),
+        "sdrx_spectrum_available": (i64, [vp]),
+        "sdrx_spectrum_read": (i64, [vp, vp, i64]),
+        "sdrx_spectrum_skip": (i64, [vp, i64]),
+        "sdrx_spectrum_window": (C.c_int, [vp, vp, i32]),
+        "sdrx_spectrum_sync": (C.c_int, [vp]),
+        "sdrx_spectrum_set_stream": (C.c_int, [vp, vp]),
+        "sdrx_spectrum_get_stream": (C.c_int, [vp, pp]),
+        "sdrx_spectrum_set_timing": (C.c_int, [vp, C.c_int]),
+        "sdrx_spectrum_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_spectrum_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_fdecim_state_bytes": (i64, [vp]),
         "sdrx_fdecim_get_state": (C.c_int, [vp, vp]),
         "sdrx_fdecim_set_state": (C.c_int, [vp, vp]),
@@ -563,6 +579,108 @@ class DcCorrection:
 
     def set_stream(self, hip_stream: int | None):
         _check(lib().sdrx_dccorr_set_stream(self._h, hip_stream), "sdrx_dccorr_set_stream")
+
+
+# FFTWindow::Function and SpectrumVis::AveragingMode (include/sdrx.h SDRX_SPECTRUM_*)
+WIN_BARTLETT, WIN_BLACKMAN_HARRIS, WIN_FLATTOP, WIN_HAMMING, WIN_HANNING, WIN_RECTANGLE = range(6)
+AVG_NONE, AVG_MOVING, AVG_FIXED = 0, 1, 2
+
+
+class SpectrumCfg(C.Structure):
+    _fields_ = [("fft_size", C.c_int32), ("overlap_percent", C.c_int32), ("avg_nb", C.c_uint32), ("avg_mode", C.c_int32),
+                ("window", C.c_int32), ("linear", C.c_int32), ("scalef", C.c_float)]
+
+
+class SpectrumVis:
+    """SpectrumVis (sdrgui/dsp/spectrumvis.{h,cpp}) on the GPU: every frame the reference hands to
+    GLSpectrum::newSpectrum is queued on the device until read() -> (frames, N) float32."""
+
+    def __init__(self, fft_size: int = 1024, overlap_percent: int = 0, avg_nb: int = 0, avg_mode: int = AVG_NONE,
+                 window: int = WIN_BLACKMAN_HARRIS, linear: bool = False, scalef: float = 32768.0, device: int = 0):
+        self._h = C.c_void_p()
+        cfg = self._cfg(fft_size, overlap_percent, avg_nb, avg_mode, window, linear, scalef)
+        _check(lib().sdrx_spectrum_create(C.byref(self._h), device, C.byref(cfg)), "sdrx_spectrum_create")
+        self.scalef = scalef
+
+    @staticmethod
+    def _cfg(fft_size, overlap_percent, avg_nb, avg_mode, window, linear, scalef) -> SpectrumCfg:
+        return SpectrumCfg(int(fft_size), int(overlap_percent), int(avg_nb), int(avg_mode), int(window), int(bool(linear)), float(scalef))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().sdrx_spectrum_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = _del
+
+    @property
+    def fft_size(self) -> int:
+        return lib().sdrx_spectrum_window(self._h, None, 0)
+
+    def configure(self, fft_size: int, overlap_percent: int, avg_nb: int, avg_mode: int, window: int, linear: bool):
+        """handleConfigure: keeps the 4096-entry buffer, zeroes the averages"""
+        cfg = self._cfg(fft_size, overlap_percent, avg_nb, avg_mode, window, linear, self.scalef)
+        _check(lib().sdrx_spectrum_configure(self._h, C.byref(cfg)), "sdrx_spectrum_configure")
+
+    def reset(self):
+        _check(lib().sdrx_spectrum_reset(self._h), "sdrx_spectrum_reset")
+
+    def feed(self, iq, positive_only: bool = False):
+        iq = _i16(iq)
+        _check(lib().sdrx_spectrum_feed(self._h, iq.ctypes.data, iq.size // 2, int(positive_only)), "sdrx_spectrum_feed")
+
+    def feed_dev(self, t, positive_only: bool = False):
+        """t: a contiguous int16 torch tensor of interleaved I/Q on the handle's device, ordered against the handle's
+        stream by the caller (synchronise, or hand the torch stream over with set_stream)"""
+        if not t.is_contiguous() or str(t.dtype) != "torch.int16":
+            raise TypeError("expected a contiguous int16 tensor")
+        _check(lib().sdrx_spectrum_feed_dev(self._h, t.data_ptr(), t.numel() // 2, int(positive_only)), "sdrx_spectrum_feed_dev")
+
+    def available(self) -> int:
+        return lib().sdrx_spectrum_available(self._h)
+
+    def read(self, max_frames: int | None = None) -> np.ndarray:
+        n = self.fft_size
+        k = self.available() if max_frames is None else min(max_frames, self.available())
+        out = np.empty((k, n), np.float32)
+        got = lib().sdrx_spectrum_read(self._h, out.ctypes.data, k)
+        if got < 0:
+            raise SdrxError(f"sdrx_spectrum_read rc={got}: {lib().sdrx_last_error().decode()}")
+        return out[:got]
+
+    def skip(self, n: int = -1) -> int:
+        return lib().sdrx_spectrum_skip(self._h, n)
+
+    def window(self) -> np.ndarray:
+        n = self.fft_size
+        out = np.empty(n, np.float32)
+        lib().sdrx_spectrum_window(self._h, out.ctypes.data, n)
+        return out
+
+    def sync(self):
+        _check(lib().sdrx_spectrum_sync(self._h), "sdrx_spectrum_sync")
+
+    def set_stream(self, hip_stream: int | None):
+        _check(lib().sdrx_spectrum_set_stream(self._h, hip_stream), "sdrx_spectrum_set_stream")
+
+    def get_stream(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sdrx_spectrum_get_stream(self._h, C.byref(p)), "sdrx_spectrum_get_stream")
+        return p.value or 0
+
+    def set_timing(self, on: bool):
+        _check(lib().sdrx_spectrum_set_timing(self._h, int(on)), "sdrx_spectrum_set_timing")
+
+    def get_timing(self, reset: bool = True):
+        ms, n = C.c_double(), C.c_int64()
+        _check(lib().sdrx_spectrum_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_spectrum_get_timing")
+        return ms.value, n.value
+
+    def last_launch(self) -> dict:
+        name = C.create_string_buffer(128)
+        g, b, l = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().sdrx_spectrum_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
+        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
 
 
 def chan_plan(in_rate: int, req_rate: int, req_fc: int):
