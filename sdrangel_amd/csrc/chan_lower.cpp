@@ -1,0 +1,107 @@
+// libsdrx.so: lowering of the bank plan's matrix-core jobs for tree_mx_kernel (chan_lower.hpp).  Host code only, no HIP
+// headers; sdrx_chan.hip compiles it in next to the planner.
+#include "chan_lower.hpp"
+#include "chan_plan.hpp"
+#include <algorithm>
+
+namespace sdrx {
+
+bool subtree_all_mx(const TkSubtree& st)
+{
+    if (st.n_levels < 1 || st.n_levels > MX_MAX_LEVELS) return false;
+    for (int l = 0; l < st.n_levels; l++) if (!st.lv[l].mfma) return false;
+    return true;
+}
+
+namespace {
+
+// one job; `PI` / `PO` = byte pitch of the arrays the level reads / writes
+std::string lower_job(const TkMJob& j, int PI, int PO, TkLJob& r)
+{
+    r.b = j.bI; r.c = j.mode ? j.cQ : j.cI; r.out0 = j.out0;
+    if (j.bQ != j.bI + PI) return "lower: odd arms not one pitch apart";
+    if ((j.mode ? j.cI - j.cQ : j.cQ - j.cI) != PI) return "lower: even arms not one pitch apart";
+    bool sink = false;
+    int meta = 0;
+    for (int k = 0; k < 2; k++) {
+        const TkMOut& m = j.o[k];
+        const int f = m.flags;
+        r.sink[k] = m.sink;
+        sink |= m.sink >= 0;
+        if (f != 0 && f != (1 | 2) && f != (1 | 4) && f != (1 | 2 | 4)) return "lower: unexpected arm set";
+        r.o[k] = f ? m.E_I : 0;
+        if (f) {
+            // the odd arm at 2 PO whatever its kind (a fast job's O_I already holds the alternating copy's address); a child with
+            // both kinds has the alternating copy at 4 PO
+            if (m.E_Q != m.E_I + PO) return "lower: even arms of a child not one pitch apart";
+            const int odd_I = (f & 2) || j.fast ? m.O_I : m.A_I, odd_Q = (f & 2) || j.fast ? m.O_Q : m.A_Q;
+            if (odd_I != m.E_I + 2 * PO || odd_Q != m.E_I + 3 * PO) return "lower: odd arm of a child not at 2 pitches";
+            if (f == 7 && (m.A_I != m.E_I + 4 * PO || m.A_Q != m.E_I + 5 * PO)) return "lower: alternating arm of a child not at 4 pitches";
+        }
+        meta |= f << (4 + 4 * k);
+    }
+    if (!j.mode && (j.o[1].flags || j.o[1].sink >= 0)) return "lower: centre stage with a second child";
+    if (j.fast && sink) return "lower: branch-free job with a sink";
+    const int cls = j.fast ? MX_FAST : sink ? MX_SINK : MX_ARMS;
+    if (j.mode) meta |= MX_LU_BIT;
+    r.meta = meta | cls;
+    return {};
+}
+
+// one subtree's levels into out.jobs / out.src (their index range, sorted by class inside each level)
+std::string lower_subtree(const BankPlan& plan, const TkSubtree& st, LoweredBank& out)
+{
+    std::string err;
+    for (int l = 0; l < st.n_levels; l++) {
+        const TkLevel& lv = st.lv[l];
+        const int PI = mx_pitch(l), PO = mx_pitch(l + 1);
+        if (lv.in_len * 4 != PI || (lv.arr_cnt && lv.arr_len * 4 != PO)) return "lower: level arrays of another length";
+        std::vector<std::pair<int, int>> order;             // (class, job)
+        std::vector<TkLJob> lowered((size_t)lv.n_mjobs);
+        for (int q = 0; q < lv.n_mjobs; q++) {
+            const int i = lv.mjob_base + q;
+            err = lower_job(plan.mjobs[(size_t)i], PI, PO, lowered[(size_t)q]);
+            if (!err.empty()) return err;
+            order.emplace_back(mx_class(lowered[(size_t)q].meta), q);
+        }
+        std::stable_sort(order.begin(), order.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
+        for (int q = 0; q < lv.n_mjobs; q++) {
+            out.jobs[(size_t)(lv.mjob_base + q)] = lowered[(size_t)order[(size_t)q].second];
+            out.src[(size_t)(lv.mjob_base + q)] = lv.mjob_base + order[(size_t)q].second;
+        }
+    }
+    return {};
+}
+
+} // namespace
+
+std::string lower_bank(const BankPlan& plan, LoweredBank& out)
+{
+    out = LoweredBank{};
+    out.jobs.resize(plan.mjobs.size());
+    out.src.resize(plan.mjobs.size());
+    for (size_t i = 0; i < plan.mjobs.size(); i++) out.src[i] = (int)i;
+    // a subtree the lean kernel cannot take (a level off the matrix cores, or a layout the lowering does not recognise) keeps
+    // tree_kernel<true> for its pass: the first such layout is reported, the bank is planned all the same
+    std::string first_err;
+    std::vector<uint8_t> sub_mx(plan.subtrees.size(), 0);
+    for (size_t s = 0; s < plan.subtrees.size(); s++) {
+        const TkSubtree& st = plan.subtrees[s];
+        if (!plan.mfma || !subtree_all_mx(st)) continue;
+        const std::string err = lower_subtree(plan, st, out);
+        if (err.empty()) sub_mx[s] = 1;
+        else if (first_err.empty()) first_err = err;
+    }
+    out.pass_mx.assign(plan.passes.size(), 0);
+    for (size_t p = 0; p < plan.passes.size(); p++) {
+        bool all = !plan.passes[p].empty();
+        for (int si : plan.passes[p]) {
+            const int s = plan.streams[(size_t)si].subtree;
+            all = all && s >= 0 && sub_mx[(size_t)s];
+        }
+        out.pass_mx[p] = plan.mfma && all ? 1 : 0;
+    }
+    return first_err;
+}
+
+} // namespace sdrx

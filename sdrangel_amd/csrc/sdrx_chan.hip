@@ -1,8 +1,10 @@
 // libsdrx.so: sdrx_chan_* -- a bank of DownChannelizers fed from one device stream
-// (reference: sdrbase/dsp/downchannelizer.{h,cpp}).  Device state + launches; planner in chan_plan.cpp, kernel in tree_kernel.hpp.
+// (reference: sdrbase/dsp/downchannelizer.{h,cpp}).  Device state + launches; planner in chan_plan.cpp, kernels in tree_kernel.hpp
+// and (passes whose every level is a matrix-core level, jobs lowered by chan_lower.cpp) tree_mx_kernel.hpp.
 #include "sdrx_common.hpp"
 #include "chan_plan.hpp"
 #include "tree_kernel.hpp"
+#include "tree_mx_kernel.hpp"
 #include <vector>
 #include <cstring>
 #include <new>
@@ -10,6 +12,7 @@
 // The planner is host-only code of its own (tests compile it with g++ alone); it is built as part of this translation unit
 // so that the bank's host code, planner included, stands on sdrx_common + sdrx_chan (the host-slice sanitizer build)
 #include "chan_plan.cpp"
+#include "chan_lower.cpp"
 
 using namespace sdrx;
 
@@ -38,9 +41,11 @@ struct Group {
     int64_t T = 0;                // samples fed since this group's epoch
     std::vector<int> chans;
     BankPlan plan;
+    LoweredBank low;              // the plan's matrix-core jobs for tree_mx_kernel, and which passes run it
     std::vector<StreamBuf> bufs;  // one per plan stream
-    void* d_static = nullptr;     // subtrees | nodes | arrays | mjobs
+    void* d_static = nullptr;     // subtrees | nodes | arrays | mjobs | lowered jobs
     TkSubtree* d_subtrees = nullptr; TkNode* d_nodes = nullptr; TkArray* d_arrays = nullptr; TkMJob* d_mjobs = nullptr;
+    TkLJob* d_ljobs = nullptr;
 };
 
 } // namespace
@@ -86,18 +91,20 @@ static int upload_group(sdrx_chan_bank* b, Group* g)
         }
     }
     const size_t b0 = p.subtrees.size() * sizeof(TkSubtree), b1 = p.nodes.size() * sizeof(TkNode), b2 = p.arrays.size() * sizeof(TkArray);
-    const size_t b3 = p.mjobs.size() * sizeof(TkMJob);
+    const size_t b3 = p.mjobs.size() * sizeof(TkMJob), b4 = g->low.jobs.size() * sizeof(TkLJob);
     if (b0 + b1 + b2 == 0) return SDRX_OK;
-    SDRX_HIP(hipMalloc(&g->d_static, b0 + b1 + b2 + b3 + 64));
+    SDRX_HIP(hipMalloc(&g->d_static, b0 + b1 + b2 + b3 + b4 + 64));
     char* d = static_cast<char*>(g->d_static);
     g->d_subtrees = reinterpret_cast<TkSubtree*>(d);
     g->d_nodes = reinterpret_cast<TkNode*>(d + b0);
     g->d_arrays = reinterpret_cast<TkArray*>(d + b0 + b1);
     g->d_mjobs = reinterpret_cast<TkMJob*>(d + b0 + b1 + b2);
+    g->d_ljobs = reinterpret_cast<TkLJob*>(d + b0 + b1 + b2 + b3);
     if (b0) SDRX_HIP(hipMemcpy(g->d_subtrees, p.subtrees.data(), b0, hipMemcpyHostToDevice));
     if (b1) SDRX_HIP(hipMemcpy(g->d_nodes, p.nodes.data(), b1, hipMemcpyHostToDevice));
     if (b2) SDRX_HIP(hipMemcpy(g->d_arrays, p.arrays.data(), b2, hipMemcpyHostToDevice));
     if (b3) SDRX_HIP(hipMemcpy(g->d_mjobs, p.mjobs.data(), b3, hipMemcpyHostToDevice));
+    if (b4) SDRX_HIP(hipMemcpy(g->d_ljobs, g->low.jobs.data(), b4, hipMemcpyHostToDevice));
     return SDRX_OK;
 }
 
@@ -117,11 +124,15 @@ static int new_group(sdrx_chan_bank* b, const std::vector<int>& chans)
     BankPlan plan;
     const std::string err = plan_bank(chains, plan_options_from_env(), plan);
     if (!err.empty()) { set_error(err); return SDRX_EINVAL; }
+    // (a pass the lowering does not recognise stays on tree_kernel<true>: not an error)
+    LoweredBank low;
+    (void)lower_bank(plan, low);
     Group* g = new (std::nothrow) Group;
     if (!g) return SDRX_ENOMEM;
     g->chans = chans;
     g->index = (int)b->groups.size();
     g->plan = std::move(plan);
+    g->low = std::move(low);
     int rc = upload_group(b, g);
     if (rc) { free_group(g); return rc; }
     for (int c : chans) b->ch[c].group = g->index;
@@ -270,7 +281,12 @@ static int feed_group(sdrx_chan_bank* b, Group* g, const uint32_t* d_in, int64_t
         const int s0 = ps.front(), cnt = (int)ps.size();
         size_t lds_bytes = 0;                              // per pass: a deep pass must not cost the shallow ones their occupancy
         for (int si : ps) lds_bytes = std::max(lds_bytes, (size_t)plan.subtrees[(size_t)plan.streams[(size_t)si].subtree].lds_dwords * 4);
-        if (plan.mfma)
+        // an all-matrix-core pass (every default pass) runs the lean kernel; deeper passes (SDRX_CHAN_MAX_LEVELS / _LDS_KB)
+        // have dot2 levels and keep tree_kernel<true>.  Both are the matrix-core engine: last_launch() names it tree_kernel<mfma>.
+        if (g->low.pass_mx[p])
+            hipLaunchKernelGGL(tree_mx_kernel, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->stream,
+                               g->d_subtrees, g->d_arrays, d_streams + s0, d_sinks, g->d_ljobs);
+        else if (plan.mfma)
             hipLaunchKernelGGL(tree_kernel<true>, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->stream,
                                g->d_subtrees, g->d_nodes, g->d_arrays, d_streams + s0, d_sinks, g->d_mjobs);
         else
@@ -334,6 +350,7 @@ int sdrx_chan_bank_create(sdrx_chan_bank_t** out, int device, int32_t in_rate, i
     b->stream = b->own_stream;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tree_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tree_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tree_mx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) { sdrx_chan_bank_destroy(b); return hip_fail(e, "hipFuncSetAttribute", __FILE__, __LINE__); }
     b->ch.resize((size_t)n_ch);
     std::vector<int> all;
