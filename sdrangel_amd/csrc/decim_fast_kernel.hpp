@@ -223,12 +223,20 @@ __host__ __device__ constexpr int df_lds_dwords(int L, int S = DF_SUB) { return 
 // The same layout with the pitch the MATRIX-CORE TAIL wants (MXT: single-wave matrix-core flavour, stages 4..6 as one MFMA tile): the
 // int32 arrays then have an even pitch (their windows are read as aligned 16-byte vectors); the dot2 tail keeps the odd one.
 // PAD (matrix-core engine): the packed arrays of stages 1..3 get 16 more dwords, so that their pitch is 32 mod 64 dwords: a tile reads
-// the I and the Q array in ONE wave instruction (columns alternate I / Q) and 128 bytes between the two keep the ds_read_b128 conflict-free.
+// the I and the Q array in ONE wave instruction (columns alternate I / Q) and 128 bytes between the two keep the ds_read_b128 conflict-free
+// -- for the odd arms' windows and for the even arms' centre samples that a centre-mode tile reads in the same instruction.
+// The matrix-core tail (MXT) has 4 more dwords behind the arrays that stay zero: the window slots its tiles must not fill (hb_mfma.hpp, CTR).
 template<bool MXT, bool PAD = false> struct DfLay {
     static __host__ __device__ constexpr int arr(int s, int S = DF_SUB) { return df_in16(s) ? (HIST / 2 + (S >> (s + 1)) + (PAD ? 16 : 0)) : (HIST + (S >> s) + (MXT ? 0 : 1)); }
     static __host__ __device__ constexpr int off(int s, int S = DF_SUB) { int o = 0; for (int u = 1; u < s; u++) o += 4 * arr(u, S); return o; }
     static __host__ __device__ constexpr int total(int L, int S = DF_SUB) { return off(L + 1, S); }
+    static __host__ __device__ constexpr int words(int L, int S = DF_SUB) { return total(L, S) + (MXT ? 4 : 0); }      // the kernel's whole LDS
 };
+// LDS bytes of the matrix-core kernel decim_fast_kernel<L, FC, PRE, U8, NW, true> (the host reports it)
+__host__ __device__ constexpr int df_mx_lds_bytes(int L, int NW) { return 4 * (NW == 1 && L >= 4 ? DfLay<true, true>::words(L, DF_SUB * NW) : DfLay<false, true>::words(L, DF_SUB * NW)); }
+// stage s of a matrix-core chain takes its centre tap into the tile (hb_mfma.hpp, CTR): a centre-mode stage with packed int16 arms.
+// Its even arms are then biased by 0x0080 like the odd arms (the producer XORs HBM_BIAS2 in).
+__host__ __device__ constexpr bool df_ctr(int L, int FC, int s) { return s <= 3 && s <= L && dc_mode(L, FC, s) == MODE_CEN; }
 constexpr uint32_t HBM_BIAS4 = 0x00808080u;       // XORed into every int32 odd-arm entry the matrix-core tail reads (bytes 0..2 as signed)
 
 // NW = waves per workgroup.  NW = 1: the wave-private pipeline described at the top (sub-chunks of 1024 samples, 4 warm-up
@@ -254,20 +262,20 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
     static_assert(NW == 1 || NW == 2 || NW == 4, "warm-up = 4096 samples = a whole number of sub-chunks (2 measured: never the best)");
     constexpr bool MXT = MX && NW == 1 && L >= 4;              // stages 4..L as ONE matrix-core tile per iteration (needs the skewed loop)
     typedef DfLay<MXT, MX> DL;
-    __shared__ __attribute__((aligned(16))) uint32_t lds[DL::total(L, S)];
+    __shared__ __attribute__((aligned(16))) uint32_t lds[DL::words(L, S)];
     const int lane = threadIdx.x;
     const long first = (long)blockIdx.x * spw;
     if (first >= n_sub) return;
     long last = first + spw; if (last > n_sub) last = n_sub;
     const long n_in4 = n_in >> 2, n_out = n_in >> L;
 
-    for (int i = lane; i < DL::total(L, S); i += NT) lds[i] = 0;
+    for (int i = lane; i < DL::words(L, S); i += NT) lds[i] = 0;
     constexpr int MXS = MX ? (L < 3 ? L : 3) : 0;             // stages 1..MXS run on the matrix cores
     if constexpr (MX) {
         __syncthreads();
-        static_for<1, MXS + 1>([&](auto sc) {                  // a zero sample of a biased odd arm is 0x0080
+        static_for<1, MXS + 1>([&](auto sc) {                  // a zero sample of a biased arm is 0x0080
             constexpr int s = decltype(sc)::value;
-            for (int i = lane; i < 2 * DL::arr(s, S); i += NT) lds[DL::off(s, S) + i] = HBM_BIAS2;
+            for (int i = lane; i < (df_ctr(L, FC, s) ? 4 : 2) * DL::arr(s, S); i += NT) lds[DL::off(s, S) + i] = HBM_BIAS2;
         });
     }
 
@@ -277,7 +285,7 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
     // folded into the taps: exact modulo 2^32).  Only the sets the chain's first three stages use are built.
     constexpr bool NEED_CEN = MXT || (MX && (dc_mode(L, FC, 1) == MODE_CEN || (MXS >= 2 && dc_mode(L, FC, 2) == MODE_CEN) || (MXS >= 3 && dc_mode(L, FC, 3) == MODE_CEN)));
     constexpr bool NEED_ROT = MX && (dc_mode(L, FC, 1) != MODE_CEN || (MXS >= 2 && dc_mode(L, FC, 2) != MODE_CEN) || (MXS >= 3 && dc_mode(L, FC, 3) != MODE_CEN));
-    HbMfmaTaps<64, false> taps_cen; HbMfmaTaps<64, true> taps_rot;
+    HbMfmaTaps<64, false, true> taps_cen; HbMfmaTaps<64, true> taps_rot;
     const int wl = lane & 63, n16 = wl & 15, g4 = wl >> 4, comp = n16 & 1, bn = n16 >> 1;      // tile column n: block n / 2 of component n & 1
     const int wv = MX ? __builtin_amdgcn_readfirstlane(lane >> 6) : 0;
     if constexpr (NEED_CEN) taps_cen.init(wl);
@@ -289,7 +297,7 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
     // (4 blocks x I, Q), 8..11 = stage 5, 12..13 = stage 6; the stages work on different sub-chunks (skewed loop), so they are independent.
     // The rotation of an inf/sup stage's odd arm is applied by its PRODUCER (int32: -x is exact modulo 2^32): every column uses the plain taps.
     // Layout of a tail stage (same 4 (32 + n) dwords as four int32 arms): oI.lo oI.hi oQ.lo oQ.hi (16 + n / 2 dwords each) eI eQ (32 + n each).
-    int t_lo = 0, t_pp = 0, t_co = 0, t_no = 0, t_npp = 0, t_ne = 0, t_blk = 0, t_stage = 4;
+    int t_lo = 0, t_l1 = 0, t_h1 = 0, t_pp = 0, t_co = 0, t_no = 0, t_npp = 0, t_ne = 0, t_blk = 0, t_stage = 4;
     uint32_t t_me = 0, t_mo = 0, t_ng = 0;
     bool t_act = false, t_next = false;
     if constexpr (MXT) {
@@ -313,6 +321,9 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
         t_pp = HIST / 2 + tn / 2; t_npp = HIST / 2 + nn / 2;
         const int tec = tmode == MODE_CEN ? tc : 1 - tc;        // inf/sup: the centre tap comes from the other component
         t_lo = toff + 2 * tc * t_pp + 8 * t_blk + 4 * g4;       // window entry 0 of the block = int16 index 16 blk of the low plane
+        // second K-step: entries 48..63 (lane groups 2, 3) meet taps_cen's centre slots, which a tail tile fills with zeros
+        t_l1 = g4 < 2 ? t_lo + 16 : DL::total(L, S);
+        t_h1 = g4 < 2 ? t_lo + t_pp + 16 : DL::total(L, S);
         t_co = toff + 4 * t_pp + tec * (HIST + tn) + 16 * t_blk + 4 * g4 + 16;   // centre taps e[k - 15]: int32 entries 16 blk + 4 g + 17 + i
         t_next = t_act && t_stage < L;
         t_no = noff + 2 * tc * t_npp + HIST / 2 + 4 * t_blk + g4;               // the lane's two odd outputs: one packed dword per plane
@@ -354,7 +365,7 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
             const int q = HIST / 2 + j * NT + lane;
             uint32_t a, b, c, d;
             Quad<U8>::split(pre[j], in_shift, a, b, c, d);
-            eI[q] = a; eQ[q] = b;
+            if constexpr (MX && df_ctr(L, FC, 1)) { eI[q] = a ^ HBM_BIAS2; eQ[q] = b ^ HBM_BIAS2; } else { eI[q] = a; eQ[q] = b; }
             if constexpr (MX) { oI[q] = c ^ HBM_BIAS2; oQ[q] = d ^ HBM_BIAS2; } else { oI[q] = c; oQ[q] = d; }
         }
     };
@@ -378,7 +389,14 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
             const int m_odd = MODE == MODE_CEN ? 2048 : -m_even;
             const uint32_t* ob = iI + comp * arr + 8 * bn + 4 * g4;    // window entry 0 of block bn: int16 index 16 blk
             const uint32_t* eb = jI + ec * arr + 8 * bn + 2 * g4 + 8;  // centre taps e[k - 15]: int16 entries 16 blk + 4 g + 17 + i
-            constexpr int BIASV = MODE == MODE_CEN ? HbMfmaTaps<64, false>::BIAS : HbMfmaTaps<64, true>::BIAS;
+            // centre mode: the centre taps go through the tile (hb_mfma.hpp, CTR).  Lane groups 2, 3 load e[16 blk + 16 + 8 (g - 2) ..] (dword
+            // 8 blk + 4 g of the even arm) as their second K-step; output 15's e[16 blk + 32] (low half of dword 8 blk + 16) replaces slot 0 in
+            // lane group 2.  The other groups' copy of that read goes to a dword pair of their own (conflict-free; their value is not used).
+            constexpr bool CF = MODE == MODE_CEN;
+            const uint32_t* ob1 = (CF && g4 >= 2) ? jI + comp * arr + 8 * bn + 4 * g4 : ob + 16;
+            const uint32_t* e15 = g4 >= 2 ? jI + comp * arr + 8 * bn + 16 : jI + 2 * wl;
+            const uint32_t m15 = g4 == 2 ? 0xffffu : 0u;
+            constexpr int BIASV = MODE == MODE_CEN ? HbMfmaTaps<64, false, true>::CBIAS : HbMfmaTaps<64, true>::BIAS;
             const v4i bias = { BIASV, BIASV, BIASV, BIASV };
             // every load of the stage's tiles first, then the MFMAs, then the epilogues: the stores of one tile must not sit
             // between the loads of the next (same LDS array as far as the compiler can tell)
@@ -391,9 +409,16 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
                 constexpr int tt = decltype(tc)::value;
                 const int t = wv * TPW + g0 + tt;
                 b0[tt] = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(ob + 64 * t, 16));
-                b1[tt] = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(ob + 64 * t + 16, 16));
-                c01[tt] = *reinterpret_cast<const uint2*>(__builtin_assume_aligned(eb + 64 * t, 8));
-                c2[tt] = eb[64 * t + 2];
+                b1[tt] = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(ob1 + 64 * t, 16));
+                if constexpr (CF) {
+                    // a ds_read_b64 (banks mod 64: 2-way among the 16 columns; as a b32 it would be 4-way); the asm keeps both halves
+                    uint64_t c = *reinterpret_cast<const uint64_t*>(__builtin_assume_aligned(e15 + 64 * t, 8));
+                    asm("" : "+v"(c));
+                    b1[tt][0] = (int)(((uint32_t)c & m15) | ((uint32_t)b1[tt][0] & ~m15));
+                } else {
+                    c01[tt] = *reinterpret_cast<const uint2*>(__builtin_assume_aligned(eb + 64 * t, 8));
+                    c2[tt] = eb[64 * t + 2];
+                }
             });
             static_for<0, TG>([&](auto tc) {
                 constexpr int tt = decltype(tc)::value;
@@ -402,12 +427,15 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
             static_for<0, TG>([&](auto tc) {
                 constexpr int tt = decltype(tc)::value;
                 const int t = wv * TPW + g0 + tt;
-                const int e[4] = { (int)c01[tt].x >> 16, (int)(int16_t)c01[tt].y, (int)c01[tt].y >> 16, (int)(int16_t)c2[tt] };
                 int y[4];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
-                    // acc = S +- (e << 11);  y = (acc << SHL) >> 11 with the 32-bit wrap of the reference's accumulator
-                    const int acc = __mul24(e[i], (i & 1) ? m_odd : m_even) + S4[tt][i];
+                    // acc = S +- (e << 11) (centre mode: already in S);  y = (acc << SHL) >> 11 with the 32-bit wrap of the reference's accumulator
+                    int acc = S4[tt][i];
+                    if constexpr (!CF) {
+                        const int e = i == 0 ? (int)c01[tt].x >> 16 : i == 1 ? (int)(int16_t)c01[tt].y : i == 2 ? (int)c01[tt].y >> 16 : (int)(int16_t)c2[tt];
+                        acc += __mul24(e, (i & 1) ? m_odd : m_even);
+                    }
                     y[i] = (int)((uint32_t)acc << SHL) >> (HB_SHIFT - 1);
                 }
                 const int blk = 8 * t + bn;
@@ -417,7 +445,7 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
                         for (int i = 0; i < 4; i++) ovf_or |= (uint32_t)y[i] + 0x8000u;
                         const int p = HIST / 2 + 4 * blk + g4;
                         nI[comp * arr2 + p] = pack_iq(y[1], y[3]) ^ HBM_BIAS2;               // odd arm of the next stage
-                        nI[(2 + comp) * arr2 + p] = pack_iq(y[0], y[2]);                     // even arm
+                        nI[(2 + comp) * arr2 + p] = pack_iq(y[0], y[2]) ^ (df_ctr(L, FC, s + 1) ? HBM_BIAS2 : 0u);   // even arm
                     } else {
                         if constexpr (MXT) {
                             // matrix-core tail: the odd outputs go to stage 4's two packed planes (low halves biased by 0x8000, both by the
@@ -546,9 +574,9 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
                 const long subS = it - (t_stage - 1);                          // the sub-chunk this lane's stage works on
                 const bool on = t_act && subS >= first - WARM && subS < last;
                 const v4i l0 = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(lds + t_lo, 16));
-                const v4i l1 = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(lds + t_lo + 16, 16));
+                const v4i l1 = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(lds + t_l1, 16));
                 const v4i h0 = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(lds + t_lo + t_pp, 16));
-                const v4i h1 = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(lds + t_lo + t_pp + 16, 16));
+                const v4i h1 = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(lds + t_h1, 16));
                 const v4i cq = *reinterpret_cast<const v4i*>(__builtin_assume_aligned(lds + t_co, 16));
                 const uint32_t c4 = lds[t_co + 4];
                 cbar();
@@ -561,7 +589,7 @@ void decim_fast_kernel(const DecimJobs jobs, int spw, int post, int in_shift)
                     a[4 * pp + (lane / 32) * (HIST + n) + (lane % 32)] = keep[s - 1][1];
                 });
                 cbar();
-                constexpr int BV = HbMfmaTaps<64, false>::BIAS;
+                constexpr int BV = HbMfmaTaps<64, false>::BIAS;           // the odd taps only: the centre slots read zeros
                 const v4i biasv = { BV, BV, BV, BV };
                 const v4i SL = taps_cen.tile(l0, l1, biasv), SH = taps_cen.tile(h0, h1, biasv);
                 const uint32_t ce[4] = { (uint32_t)cq[1], (uint32_t)cq[2], (uint32_t)cq[3], c4 };

@@ -20,6 +20,14 @@
 // needs.  The D layout (lane (n, g) holds outputs 4g .. 4g+3 of block n) hands each lane two even- and two odd-indexed
 // outputs = one packed dword for each arm of the next stage.
 // The k <-> (lane group, byte) assignment of the hardware does not matter: A and B use the same one.
+//
+// CTR (centre-mode decimator stages): entries 48..63 of the window carry no odd-arm tap (j < 0 for every output), so the lanes of
+// groups g = 2, 3 load the EVEN arm into the second K-step instead -- slot c = 8 (g - 2) + 2 q + u holds e[16 blk + 16 + c], biased by
+// 0x0080 like the odd arm -- and the operand puts the centre tap 2^11 = 256 * 8 + 0 (hh = 8, hl = 0) at c = m + 1; slot 0 (c = m + 1
+// would be 16 for m = 15) is overwritten by the caller with e[16 blk + 32], output 15's centre sample, and carries its tap.  The bias
+// gains 128 * 2^11 per output.  The limb bound still holds with the extra term: over the 32 odd taps and the centre tap, sum|hh| = 26 and
+// sum|hl| = 1262, so |P1| <= 128 * 26, |P2| <= 128 * 1288 and |P3| <= 128 * 1262 (plus the bias, < 2^19) -- far inside int32 -- and
+// the combination is the same modulo-2^32 arithmetic.
 #pragma once
 #include "hb_common.hpp"
 
@@ -39,12 +47,14 @@ template<int ORDER> __host__ __device__ constexpr int hb_tap_sum()
 
 // ALT: the odd arm is multiplied by (-1)^(index + 1) (the inf/sup rotations of the int32 flavour, folded into the taps;
 // exact modulo 2^32).  The channelizer's int16 flavour stores explicitly wrap-negated copies instead and uses ALT = false.
-template<int ORDER, bool ALT>
+template<int ORDER, bool ALT, bool CTR = false>
 struct HbMfmaTaps {
     static constexpr int T = ORDER / 2;                 // taps of the odd-arm FIR; also the window's lead: entry w = o[16 blk - T + w]
     static constexpr bool P1_STEP2 = (ORDER == 64);     // order 48: the central taps only meet entries 9..31
     static constexpr int BIAS = ALT ? 0 : 128 * hb_tap_sum<ORDER>();   // alternating signs cancel (the taps are symmetric, T even)
     static_assert(T >= 15 && T <= 32, "the 64-lane tap table of init() holds j = -16 .. 47");
+    static_assert(!CTR || (T == 32 && !ALT), "the centre tap takes window entries 48..63: order 64, plain taps");
+    static constexpr int CBIAS = BIAS + (CTR ? 128 * (1 << (HB_SHIFT - 1)) : 0);   // accumulator start of a tile with the centre tap folded in
     v4i p1[2], p2[2], p3[2];
 
     // Every entry of the operand is ONE table value: lane (m, g), K-step s, entry 8 g + 2 q + u carries the tap j = (m - 8 g) + (T - 32 s - 2 q - u),
@@ -77,6 +87,8 @@ struct HbMfmaTaps {
                     int a = base + 4 * (T - 32 * s - 2 * q - u);
                     if (s == 1) a = a < 0 ? 0 : a;                              // j < -16: lane 0 holds a zero
                     x[u] = (uint32_t)__builtin_amdgcn_ds_bpermute(a, u == 0 ? tabn : tab);   // window index parity = parity of u
+                    if (CTR && s == 1 && g >= 2)                                // centre slot c = 8 (g - 2) + 2 q + u: tap 2^11 at c = (m + 1) mod 16
+                        x[u] = (8 * (g - 2) + 2 * q + u) == ((m + 1) & 15) ? (uint32_t)(8 << 8) : 0u;
                 }
                 const uint32_t y = x[0] | (x[1] << 16);
                 d3[q] = y & 0x00ff00ffu;                                        // hl

@@ -124,7 +124,8 @@ typedef void (*chain_fn)(const DecimJobs, int, int, int);
 typedef void (*fast_fn)(const DecimJobs, int, int, int);
 
 struct ChainEntry { chain_fn fn; fast_fn fast; const char* name; const char* fast_name; int lds; int fast_lds; fast_fn fast4; const char* fast4_name; int fast4_lds;
-                    fast_fn fast_mx; fast_fn fast4_mx; };      // the FAST kernels with stages 1-3 on the matrix cores (the default engine)
+                    fast_fn fast_mx; fast_fn fast4_mx;         // the FAST kernels with stages 1-3 on the matrix cores (the default engine)
+                    int fast_mx_lds; int fast4_mx_lds; };      // their LDS bytes (padded layout, not the dot2 kernels')
 
 template<int L, int FC, int PRE, bool U8> static ChainEntry entry()
 {
@@ -135,7 +136,8 @@ template<int L, int FC, int PRE, bool U8> static ChainEntry entry()
     return ChainEntry{ &decim_chain_kernel<L, FC, PRE, U8>, &decim_fast_kernel<L, FC, PRE, U8, 1, false>, name, fname,
                        dc_lds_dwords(L) * 4, df_lds_dwords(L) * 4,
                        &decim_fast_kernel<L, FC, PRE, U8, 4, false>, f4name, df_lds_dwords(L, 4 * DF_SUB) * 4,
-                       &decim_fast_kernel<L, FC, PRE, U8, 1, true>, &decim_fast_kernel<L, FC, PRE, U8, 4, true> };
+                       &decim_fast_kernel<L, FC, PRE, U8, 1, true>, &decim_fast_kernel<L, FC, PRE, U8, 4, true>,
+                       df_mx_lds_bytes(L, 1), df_mx_lds_bytes(L, 4) };
 }
 
 // decimation_shifts<16,InputBits> (decimators.h:25-185)
@@ -198,7 +200,7 @@ struct sdrx_decim {
     bool rings_live = false;
     long since_load = 0;
     int path = 0;                 // 0 auto (FAST + flagged EXACT), 1 exact only, 2 fast only (debug: no fallback)
-    ChainEntry k{ nullptr, nullptr, "", "", 0, 0, nullptr, "", 0, nullptr, nullptr };
+    ChainEntry k{ nullptr, nullptr, "", "", 0, 0, nullptr, "", 0, nullptr, nullptr, 0, 0 };
     bool mfma = true;             // half-band engine of the FAST kernel: matrix cores unless SDRX_DECIM_ENGINE=valu (read at create)
     char last_name[96] = "";
     int last_grid = 0, last_block = 0, last_lds = 0;
@@ -413,7 +415,8 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
                            dim3((unsigned)segs, (unsigned)n), dim3(64 * nw), 0, h->stream, jobs, (int)spw, h->post, h->in_shift);
         SDRX_HIP(hipGetLastError());
         snprintf(h->last_name, sizeof h->last_name, "%s%s", nw == 1 ? h->k.fast_name : h->k.fast4_name, h->mfma ? "+mfma" : "");
-        h->last_grid = (int)(segs * n); h->last_block = 64 * nw; h->last_lds = nw == 1 ? h->k.fast_lds : h->k.fast4_lds;
+        h->last_grid = (int)(segs * n); h->last_block = 64 * nw;
+        h->last_lds = h->mfma ? (nw == 1 ? h->k.fast_mx_lds : h->k.fast4_mx_lds) : (nw == 1 ? h->k.fast_lds : h->k.fast4_lds);
     }
     if (h->path != 2) {
         for (int i = 0; i < n; i++) jobs.j[i].n_units = (int)((jobs.j[i].n_in + DC_CHUNK - 1) / DC_CHUNK);
