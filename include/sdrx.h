@@ -136,6 +136,12 @@ int sdrx_decim_get_timing(sdrx_decim_t* h, double* total_ms, int64_t* launches, 
 /* name + launch geometry of the kernel the last process call launched (for profiling/bench) */
 int sdrx_decim_last_launch(const sdrx_decim_t* h, char* kernel_name, int name_cap,
                            int* grid, int* block, int* lds_bytes);
+/* Fallback report of the most recent process call of this handle (auto path: FAST kernel + flagged EXACT recompute).  Synchronises
+ * the handle's stream and reads back the per-chunk overflow flags the call's FAST launch wrote: one per 4096 consumed input
+ * samples, 1 = the EXACT kernel recomputed that chunk.  flags_out (may be NULL) receives min(cap, total) bytes of 0 / 1.
+ * Reports 0, 0 when that call ran no FAST launch (log2 = 0, SDRX_DECIM_PATH=exact, or only the serial hand-over after
+ * sdrx_decim_load_stages).  In a batch every handle reports its own stream.  Nothing on the launch path depends on it. */
+int sdrx_decim_last_fallback(sdrx_decim_t* h, int64_t* flagged_chunks, int64_t* total_chunks, uint8_t* flags_out, int64_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * DownChannelizer bank  (sdrbase/dsp/downchannelizer.{h,cpp}) -- N channels fed from ONE device

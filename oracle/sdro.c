@@ -238,6 +238,58 @@ int32_t sdro_decimu_process(sdro_decim* d, const uint8_t* iq, int32_t n_u8, int1
     return n_out;
 }
 
+/* Stage-range probe: the same walk as sdro_decim_process / sdro_decimu_process, which also records what every stage emitted.
+ * A stage-s output (s = 1 .. log2) is attributed to the input sample whose arrival emits it; chunk = that sample's index in
+ * THIS call / 4096.  chunk_bad[c] = 1 when an output of stage 1 (log2 >= 2) or of stage 2 (log2 >= 3) emitted in chunk c lies
+ * outside [-32768, 32767]: the values a pipeline that stores those two stages' outputs as int16 cannot hold. */
+static int32_t decim_probe(sdro_decim* d, const int16_t* iq16, const uint8_t* iq8, int32_t n_elems, int16_t* out,
+                           int32_t* lo, int32_t* hi, uint8_t* chunk_bad, int32_t n_chunks)
+{
+    for (int k = 0; k < 12; k++) { if (lo) lo[k] = INT32_MAX; if (hi) hi[k] = INT32_MIN; }
+    if (chunk_bad) memset(chunk_bad, 0, (size_t)(n_chunks > 0 ? n_chunks : 0));
+    if (n_elems < d->group) return 0;
+    const int32_t n_cplx = (n_elems / d->group) * (d->group / 2);
+    int32_t n_out = 0;
+    for (int32_t i = 0; i < n_cplx; i++) {
+        int32_t re, im;
+        if (iq8) {
+            re = (int32_t)((uint32_t)((int32_t)iq8[2*i]   - d->ushift) << d->pre);
+            im = (int32_t)((uint32_t)((int32_t)iq8[2*i+1] - d->ushift) << d->pre);
+        } else {
+            re = (int32_t)((uint32_t)(int32_t)iq16[2*i]   << d->pre);
+            im = (int32_t)((uint32_t)(int32_t)iq16[2*i+1] << d->pre);
+        }
+        int s = 0;
+        for (; s < d->log2; s++) {
+            if (!hb_push(&d->st[s], &re, &im)) break;
+            if (lo) { if (re < lo[2*s]) lo[2*s] = re; if (im < lo[2*s+1]) lo[2*s+1] = im; }
+            if (hi) { if (re > hi[2*s]) hi[2*s] = re; if (im > hi[2*s+1]) hi[2*s+1] = im; }
+            if (s < 2 && s + 1 < d->log2 && (re < -32768 || re > 32767 || im < -32768 || im > 32767)) {
+                const int32_t c = i / 4096;
+                if (chunk_bad && c < n_chunks) chunk_bad[c] = 1;
+            }
+        }
+        if (s == d->log2) {
+            out[2*n_out]   = (int16_t)(re >> d->post);
+            out[2*n_out+1] = (int16_t)(im >> d->post);
+            n_out++;
+        }
+    }
+    return n_out;
+}
+
+int32_t sdro_decim_probe(sdro_decim* d, const int16_t* iq, int32_t n_int16, int16_t* out,
+                         int32_t* lo, int32_t* hi, uint8_t* chunk_bad, int32_t n_chunks)
+{
+    return decim_probe(d, iq, 0, n_int16, out, lo, hi, chunk_bad, n_chunks);
+}
+
+int32_t sdro_decimu_probe(sdro_decim* d, const uint8_t* iq, int32_t n_u8, int16_t* out,
+                          int32_t* lo, int32_t* hi, uint8_t* chunk_bad, int32_t n_chunks)
+{
+    return decim_probe(d, 0, iq, n_u8, out, lo, hi, chunk_bad, n_chunks);
+}
+
 /* ------------------------------------------------------------------ 24-bit sample build (SDR_RX_SAMPLE_24BIT)
  * Decimators<qint32, qint16, 24, InputBits> (decimators.h): same cascades, strides and stage modes, the six filters are
  * IntHalfbandFilterEO<qint64,qint64,64>, shifts are decimation_shifts<24,InputBits> (:62-185), the Sample is {qint32, qint32}. */

@@ -36,6 +36,15 @@ int32_t     sdro_decim_process(sdro_decim*, const int16_t* iq, int32_t n_int16, 
 /* DecimatorsU<qint32, quint8, 16, 8, Shift> (decimatorsu.h:175-216): unsigned 8-bit I/Q, value = buf - Shift */
 sdro_decim* sdro_decimu_new(int log2_decim, int fcpos, int shift);
 int32_t     sdro_decimu_process(sdro_decim*, const uint8_t* iq, int32_t n_uint8, int16_t* out_iq);
+/* Stage-range probe (for tests of pipelines that keep intermediate stages in int16): same outputs and state updates as
+ * sdro_decim_process / sdro_decimu_process.  lo / hi (12 entries each, index 2 * (stage - 1) + {0: I, 1: Q}; INT32_MAX /
+ * INT32_MIN where a stage emitted nothing) = range of every stage's outputs in this call.  chunk_bad[c] (n_chunks bytes,
+ * cleared first) = 1 when an output of stage 1 (log2 >= 2) or stage 2 (log2 >= 3) left [-32768, 32767] and was emitted by
+ * the arrival of an input sample of chunk c = (complex sample index in this call) / 4096.  Any pointer may be NULL. */
+int32_t     sdro_decim_probe(sdro_decim*, const int16_t* iq, int32_t n_int16, int16_t* out_iq,
+                             int32_t* lo, int32_t* hi, uint8_t* chunk_bad, int32_t n_chunks);
+int32_t     sdro_decimu_probe(sdro_decim*, const uint8_t* iq, int32_t n_uint8, int16_t* out_iq,
+                              int32_t* lo, int32_t* hi, uint8_t* chunk_bad, int32_t n_chunks);
 /* #int16 consumed per loop iteration of the reference function (its `pos +=` stride). */
 int32_t     sdro_decim_group_int16(int log2_decim, int fcpos);
 

@@ -88,6 +88,7 @@ def lib() -> C.CDLL:
         "sdrx_decim_set_timing": (C.c_int, [vp, C.c_int]),
         "sdrx_decim_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_decim_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "sdrx_decim_last_fallback": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), vp, i64]),
         "sdrx_chan_bank_create": (C.c_int, [pp, C.c_int, i32, i32, vp, vp]),
         "sdrx_chan_bank_destroy": (C.c_int, [vp]),
         "sdrx_chan_bank_info": (C.c_int, [vp, i32, C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(i32)]),
@@ -347,6 +348,16 @@ class Decimators:
         g, b, l = C.c_int(), C.c_int(), C.c_int()
         _check(lib().sdrx_decim_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
         return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
+
+    def last_fallback(self) -> dict:
+        """chunks (4096 input samples) of the most recent call that the FAST kernel flagged for the EXACT recompute;
+        total = 0 when that call ran no FAST launch.  Synchronises the handle's stream."""
+        f, t = C.c_int64(), C.c_int64()
+        _check(lib().sdrx_decim_last_fallback(self._h, C.byref(f), C.byref(t), None, 0), "last_fallback")
+        flags = np.zeros(t.value, np.uint8)
+        if t.value:
+            _check(lib().sdrx_decim_last_fallback(self._h, C.byref(f), C.byref(t), flags.ctypes.data, flags.size), "last_fallback")
+        return {"flagged": f.value, "total": t.value, "flags": flags}
 
 
 def decimate_dev_batch(handles, d_in_ptrs, n_elems, d_out_ptrs) -> list:

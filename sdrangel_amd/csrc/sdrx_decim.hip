@@ -195,6 +195,7 @@ struct sdrx_decim {
     uint32_t* d_hist[2] = { nullptr, nullptr };
     int cur = 0;
     DevBuf d_in, d_out, d_flags;
+    long flag_chunks = 0;         // chunks the most recent call's FAST launch wrote flags for (0: that call ran no FAST launch)
     // after sdrx_decim_load_stages: explicit rings, current while `since_load` < DC_CHUNK samples have been processed
     int32_t* d_rings = nullptr;
     bool rings_live = false;
@@ -314,6 +315,7 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
     const void* d_iq[DJ_MAX]; long n_cplx[DJ_MAX]; int16_t* d_out[DJ_MAX];
     for (int i = 0; i < n; i++) {
         d_iq[i] = d_iq_in[i]; n_cplx[i] = n_cplx_in[i]; d_out[i] = d_out_in[i];
+        hs[i]->flag_chunks = 0;
         long used = 0;
         int rc = run_transition(hs[i], h->stream, d_iq[i], n_cplx[i], d_out[i], &used); if (rc) return rc;
         if (used) {
@@ -365,6 +367,7 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
             const long chunks = (jobs.j[i].n_in + DC_CHUNK - 1) / DC_CHUNK;
             trc = hs[i]->d_flags.reserve((size_t)(chunks > 0 ? chunks : 1) * 4); if (trc) return trc;
             jobs.j[i].flags = static_cast<uint32_t*>(hs[i]->d_flags.p);
+            hs[i]->flag_chunks = chunks > 0 ? chunks : 0;
             const long ns = (jobs.j[i].n_in + sub_len - 1) / sub_len;
             jobs.j[i].n_units = (int)ns; tot_sub += ns; if (ns > max_sub) max_sub = ns;
         }
@@ -451,7 +454,7 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
 static int launch(sdrx_decim* h, const void* d_iq, long n_cplx, int16_t* d_out)
 {
     // n_cplx: whole groups only (caller truncated)
-    if (n_cplx <= 0) return SDRX_OK;
+    if (n_cplx <= 0) { h->flag_chunks = 0; return SDRX_OK; }
     return launch_batch(&h, 1, &d_iq, &n_cplx, &d_out);
 }
 
@@ -690,7 +693,7 @@ int sdrx_decim_process_u8(sdrx_decim_t* h, const uint8_t* iq, int32_t n_uint8, i
     const int64_t n_cplx = groups * (h->group / 2);
     const int64_t n_out = n_cplx >> h->log2;
     if (n_out_cplx) *n_out_cplx = (int32_t)n_out;
-    if (n_cplx == 0) return SDRX_OK;
+    if (n_cplx == 0) { h->flag_chunks = 0; return SDRX_OK; }
     int rc = h->d_in.reserve((size_t)n_cplx * 2); if (rc) return rc;
     rc = h->d_out.reserve((size_t)n_out * 4); if (rc) return rc;
     SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 2, hipMemcpyHostToDevice, h->stream));
@@ -784,7 +787,7 @@ int sdrx_decim_process(sdrx_decim_t* h, const int16_t* iq, int32_t n_int16, int1
     const int64_t n_cplx = groups * (h->group / 2);
     const int64_t n_out = n_cplx >> h->log2;
     if (n_out_cplx) *n_out_cplx = (int32_t)n_out;
-    if (n_cplx == 0) return SDRX_OK;
+    if (n_cplx == 0) { h->flag_chunks = 0; return SDRX_OK; }
     int rc = h->d_in.reserve((size_t)n_cplx * 4); if (rc) return rc;
     rc = h->d_out.reserve((size_t)n_out * 4); if (rc) return rc;
     SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, h->stream));
@@ -842,6 +845,27 @@ int sdrx_decim_last_launch(const sdrx_decim_t* h, char* kernel_name, int name_ca
     if (grid) *grid = h->last_grid;
     if (block) *block = h->last_block;
     if (lds_bytes) *lds_bytes = h->last_lds;
+    return SDRX_OK;
+}
+
+int sdrx_decim_last_fallback(sdrx_decim_t* h, int64_t* flagged_chunks, int64_t* total_chunks, uint8_t* flags_out, int64_t cap)
+{
+    if (!h || cap < 0) { set_error("sdrx_decim_last_fallback: bad argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipStreamSynchronize(h->stream));
+    const long total = h->flag_chunks;
+    long flagged = 0;
+    if (total > 0) {
+        std::vector<uint32_t> f((size_t)total);
+        SDRX_HIP(hipMemcpy(f.data(), h->d_flags.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+        for (long c = 0; c < total; c++) {
+            const bool on = f[(size_t)c] != 0;
+            flagged += on ? 1 : 0;
+            if (flags_out && c < cap) flags_out[c] = on ? 1 : 0;
+        }
+    }
+    if (flagged_chunks) *flagged_chunks = flagged;
+    if (total_chunks) *total_chunks = total;
     return SDRX_OK;
 }
 

@@ -31,6 +31,8 @@ def _sig(L):
     L.sdro_decim_switch.argtypes = [vp, C.c_int, C.c_int]
     L.sdro_decimu_new.restype = vp; L.sdro_decimu_new.argtypes = [C.c_int] * 3
     L.sdro_decimu_process.restype = i32; L.sdro_decimu_process.argtypes = [vp, vp, i32, vp]
+    L.sdro_decim_probe.restype = i32; L.sdro_decim_probe.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32]
+    L.sdro_decimu_probe.restype = i32; L.sdro_decimu_probe.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32]
     L.sdro_decim_group_int16.restype = i32; L.sdro_decim_group_int16.argtypes = [C.c_int] * 2
     L.sdro_chan_plan.restype = i32; L.sdro_chan_plan.argtypes = [i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
     L.sdro_chain_new.restype = vp; L.sdro_chain_new.argtypes = [i32, vp]
@@ -164,7 +166,7 @@ class Decim:
         self.L = lib(fast)
         self.h = self.L.sdro_decim_new(log2, fcpos, bits)
         assert self.h
-        self.log2 = log2
+        self.log2, self.fcpos = log2, fcpos
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -177,11 +179,30 @@ class Decim:
         return out[: 2 * n].copy()
 
 
+    def probe(self, buf):
+        """process(buf) plus what the stages emitted: (out, lo, hi, chunk_bad).  lo / hi: int32 [6, 2] (stage - 1, I / Q) range of
+        every stage's outputs in this call; chunk_bad: one byte per 4096 consumed complex samples, 1 = an output of stage 1
+        (log2 >= 2) or stage 2 (log2 >= 3) emitted in that chunk lies outside int16 (oracle/sdro.h)."""
+        return _probe(self, self.L.sdro_decim_probe, np.int16, buf)
+
+
+def _probe(o, fn, dtype, buf):
+    buf = np.ascontiguousarray(buf, dtype=dtype)
+    group = o.L.sdro_decim_group_int16(o.log2, o.fcpos)
+    n_cplx = (buf.size // group) * (group // 2)
+    out = np.empty(buf.size + 8, np.int16)
+    lo, hi = np.empty((6, 2), np.int32), np.empty((6, 2), np.int32)
+    bad = np.zeros((n_cplx + 4095) // 4096, np.uint8)
+    n = fn(o.h, buf.ctypes.data, buf.size, out.ctypes.data, lo.ctypes.data, hi.ctypes.data, bad.ctypes.data if bad.size else None, bad.size)
+    return out[: 2 * n].copy(), lo, hi, bad
+
+
 class DecimU:
     def __init__(self, log2, fcpos, shift=127):
         self.L = lib()
         self.h = self.L.sdro_decimu_new(log2, fcpos, shift)
         assert self.h
+        self.log2, self.fcpos = log2, fcpos
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -192,6 +213,10 @@ class DecimU:
         out = np.empty(buf.size + 8, np.int16)
         n = self.L.sdro_decimu_process(self.h, buf.ctypes.data, buf.size, out.ctypes.data)
         return out[: 2 * n].copy()
+
+    def probe(self, buf):
+        """as Decim.probe, unsigned 8-bit input"""
+        return _probe(self, self.L.sdro_decimu_probe, np.uint8, buf)
 
 
 def chan_plan(in_rate, req_rate, req_fc):

@@ -48,7 +48,10 @@ def test_centre_fold_ragged_calls(log2, fcpos, nw, monkeypatch):
 @pytest.mark.parametrize("nw", ("1", "4"))
 @pytest.mark.parametrize("log2", (3, 6))
 def test_centre_fold_full_scale(log2, nw, monkeypatch):
-    """int16 extremes in both components: the biased even arm and the extra centre term at the ends of the int16 range"""
+    """int16 extremes in both components.  This is the ALL-FLAGGED end of the FAST / EXACT pair: every one of the 25 chunks overflows an
+    int16-stored stage (tests/test_decim_fallback.py counts them with the oracle's probe), so the outputs compared here are the EXACT
+    kernel's; what the matrix-core FAST kernel contributes is the flag of every chunk, with full-scale entries in its biased even arm
+    and extra centre term.  The FAST outputs that are KEPT on full-range data are pinned by tests/test_decim_fallback_gpu.py."""
     monkeypatch.setenv("SDRX_DECIM_NW", nw)
     n = 3 * 32768 + 500
     x = np.empty(2 * n, np.int16)
@@ -58,3 +61,5 @@ def test_centre_fold_full_scale(log2, nw, monkeypatch):
     o = orc.Decim(log2, sa.FC_CEN, 16)
     got, want = g.decimate(x), o.process(x)
     assert got.size == want.size and np.array_equal(got, want), (log2, nw, int((got != want).sum()))
+    rep = g.last_fallback()
+    assert rep["flagged"] == rep["total"] == 25, (log2, nw, rep["flagged"], rep["total"])

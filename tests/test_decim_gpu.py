@@ -54,7 +54,10 @@ def test_each_kernel_path_alone(log2, fcpos, path, monkeypatch):
 
 @pytest.mark.parametrize("fcpos", (sa.FC_CEN, sa.FC_INF))
 def test_decim64_full_scale_wrap(fcpos):
-    """int16 extremes (-32768 everywhere, alternating full scale): exercises int32 wrap + non-mad24 stages."""
+    """int16 extremes (-32768 everywhere, alternating full scale): exercises int32 wrap + non-mad24 stages.
+    This is the ALL-FLAGGED end of the FAST / EXACT pair: every chunk overflows stage 1 (the oracle's probe counts 32 of 32 for each
+    input width), so the outputs compared here are the EXACT kernel's (decim_kernel.hpp) and the FAST kernel's part is to flag every
+    chunk.  The FAST kernel's own outputs on full-range data are pinned by tests/test_decim_fallback_gpu.py."""
     n = 2 * 65536
     x = np.empty(2 * n, np.int16)
     x[0::2] = -32768
@@ -64,6 +67,8 @@ def test_decim64_full_scale_wrap(fcpos):
         g = sa.Decimators(6, fcpos, bits)
         o = orc.Decim(6, fcpos, bits)
         assert np.array_equal(g.decimate(x), o.process(x))
+        rep = g.last_fallback()
+        assert rep["flagged"] == rep["total"] == 32, (bits, rep["flagged"], rep["total"])
 
 
 def test_decim_reset_and_state_roundtrip():

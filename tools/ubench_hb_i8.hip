@@ -1,6 +1,8 @@
 // Check + rate of the i8 matrix-core half-band primitive (sdrangel_amd/csrc/hb_mfma.hpp) on gfx950.
 //   1. exactness: random int16 odd arms (full range, incl. -32768 / 32767 runs) -> S = sum_j h_j o[k-j] for every output
 //      of a tile, orders 48 and 64, plain and alternating-sign taps, against a host loop (int64, wrapped to int32);
+//      and the centre-tap flavour (CTR, order 64): even arm in lane groups 2, 3 of the second K-step, slot 0 overwritten with
+//      output 15's centre sample, accumulator start CBIAS -> S + 2^11 e, same host loop;
 //   2. rate: every SIMD loops over tiles read from LDS (2 x ds_read_b128 + 5 or 6 MFMA + the limb combine).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I sdrangel_amd/csrc tools/ubench_hb_i8.hip -o tools/ubench_hb_i8
 #include "hb_mfma.hpp"
@@ -31,6 +33,32 @@ __global__ __launch_bounds__(64) void check_kernel(const int16_t* __restrict__ a
         const int idx = HIST - ORDER / 2 + 16 * blk + 8 * g;          // int16 index of the lane's 8 entries, K-step 0
         const v4i b0 = *reinterpret_cast<const v4i*>(lds + idx / 2);
         const v4i b1 = *reinterpret_cast<const v4i*>(lds + idx / 2 + 16);
+        const v4i S = taps.tile(b0, b1, bias);
+#pragma unroll
+        for (int i = 0; i < 4; i++) out[16 * blk + 4 * g + i] = S[i];
+    }
+}
+
+// HbMfmaTaps<64, false, true>: the operands as decim_fast_kernel.hpp's centre-mode stages build them
+__global__ __launch_bounds__(64) void check_ctr_kernel(const int16_t* __restrict__ arm, const int16_t* __restrict__ even, int* __restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[ARR / 2], lde[ARR / 2];
+    const int lane = threadIdx.x, n = lane & 15, g = lane >> 4;
+    for (int i = lane; i < ARR / 2; i += 64) {
+        lds[i] = reinterpret_cast<const uint32_t*>(arm)[i] ^ HBM_BIAS2;
+        lde[i] = reinterpret_cast<const uint32_t*>(even)[i] ^ HBM_BIAS2;
+    }
+    HbMfmaTaps<64, false, true> taps; taps.init(lane);
+    __syncthreads();
+    const int B = HbMfmaTaps<64, false, true>::CBIAS;
+    const v4i bias = { B, B, B, B };
+    for (int t = 0; t < NBLK / 16; t++) {
+        const int blk = 16 * t + n;
+        const int idx = 16 * blk + 8 * g;                              // window entry 8 g of the block (HIST - T = 0)
+        const v4i b0 = *reinterpret_cast<const v4i*>(lds + idx / 2);
+        // second K-step: odd-arm entries 32 .. 47 (groups 0, 1); even-arm slots c = 8 (g - 2) .. + 7 = e[16 blk + 16 + c] (groups 2, 3)
+        v4i b1 = g < 2 ? *reinterpret_cast<const v4i*>(lds + idx / 2 + 16) : *reinterpret_cast<const v4i*>(lde + idx / 2);
+        if (g == 2) b1[0] = (int)((lde[8 * blk + 16] & 0xffffu) | ((uint32_t)b1[0] & 0xffff0000u));   // slot 0 := e[16 blk + 32]
         const v4i S = taps.tile(b0, b1, bias);
 #pragma unroll
         for (int i = 0; i < 4; i++) out[16 * blk + 4 * g + i] = S[i];
@@ -110,6 +138,45 @@ static int check(unsigned seed)
     return bad;
 }
 
+static void fill_full_range(std::vector<int16_t>& a, unsigned seed)
+{
+    srand(seed);
+    for (size_t i = 0; i < a.size(); i++) {
+        const int r = rand() % 16;
+        a[i] = r == 0 ? -32768 : r == 1 ? 32767 : (int16_t)(rand() & 0xffff);
+    }
+}
+
+static int check_ctr(unsigned seed)
+{
+    std::vector<int16_t> arm(ARR), even(ARR);
+    fill_full_range(arm, seed); fill_full_range(even, seed + 100);
+    for (int i = 200; i < 280; i++) arm[i] = -32768;
+    for (int i = 400; i < 480; i++) arm[i] = (i & 1) ? 32767 : -32768;
+    for (int i = 100; i < 180; i++) even[i] = -32768;                // runs of both ends under the centre tap, alone and
+    for (int i = 210; i < 290; i++) even[i] = 32767;                 // over the odd arm's worst-case runs (entry k + 17 meets o[k])
+    for (int i = 400; i < 500; i++) even[i] = (i & 1) ? -32768 : 32767;
+    for (int i = 600; i < 700; i++) even[i] = (i % 16 == 0) ? 32767 : -32768;    // the overwritten slot differs from its neighbours
+    int16_t* d_arm; int16_t* d_even; int* d_out;
+    CK(hipMalloc(&d_arm, ARR * 2)); CK(hipMalloc(&d_even, ARR * 2)); CK(hipMalloc(&d_out, 16 * NBLK * 4));
+    CK(hipMemcpy(d_arm, arm.data(), ARR * 2, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_even, even.data(), ARR * 2, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(check_ctr_kernel, dim3(1), dim3(64), 0, 0, d_arm, d_even, d_out);
+    CK(hipDeviceSynchronize());
+    std::vector<int> got(16 * NBLK);
+    CK(hipMemcpy(got.data(), d_out, got.size() * 4, hipMemcpyDeviceToHost));
+    int bad = 0;
+    for (int k = 0; k < 16 * NBLK; k++) {
+        long s = 0;
+        for (int j = 0; j < 32; j++) s += (long)hb_tap<64>(j) * (long)arm[HIST + k - j];
+        s += 2048L * (long)even[k + 17];                              // centre tap: e[k - 15], array entry HIST + k - 15
+        if ((int)s != got[k]) { if (bad < 5) printf("  order 64 ctr: k %d want %ld got %d\n", k, s, got[k]); bad++; }
+    }
+    printf("order 64 ctr: %d outputs, %d mismatches\n", 16 * NBLK, bad);
+    CK(hipFree(d_arm)); CK(hipFree(d_even)); CK(hipFree(d_out));
+    return bad;
+}
+
 template<int ORDER, int VAR>
 static void rate()
 {
@@ -130,7 +197,7 @@ static void rate()
 int main()
 {
     int bad = 0;
-    bad += check<48, false>(1); bad += check<48, true>(2); bad += check<64, false>(3); bad += check<64, true>(4);
+    bad += check<48, false>(1); bad += check<48, true>(2); bad += check<64, false>(3); bad += check<64, true>(4); bad += check_ctr(5);
     rate<48, 0>(); rate<64, 0>(); rate<48, 1>(); rate<48, 2>(); rate<48, 3>(); rate<64, 1>();
     printf(bad ? "FAILED\n" : "ALL EXACT\n");
     return bad ? 1 : 0;
