@@ -560,6 +560,65 @@ int sdrx_spectrum_get_timing(sdrx_spectrum_t* h, double* total_ms, int64_t* feed
 int sdrx_spectrum_last_launch(const sdrx_spectrum_t* h, char* kernel_name, int name_cap,
                               int* grid, int* block, int* lds_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * Wideband (broadcast) FM demodulator bank: WFMDemod::feed (plugins/channelrx/demodwfm/wfmdemod.cpp:90-183), N channels
+ * per handle, each fed with int16 I/Q at the channelizer's output rate:
+ *     c = Complex(re, im) * m_nco.nextIQ();                               NCO (sdrbase/dsp/nco.cpp:30-64)
+ *     rf_out = m_rfFilter->runFilt(c, &rf);                                fftfilt 1024 at the CHANNEL rate (fftfilt.cpp:261-282)
+ *     per rf[i]: magsq + level sums, squelch counter, phaseDiscriminatorDelta only while the squelch is open
+ *                (m_prevArg survives closed stretches), m_interpolator.decimate on Complex(demod, 0),
+ *                (qint16)(ci.real() * 3276.8f * volume)
+ * Output: mono qint16 audio, the value the reference writes to .l and .r, bit-identical to the strict-IEEE scalar
+ * reference build with m_prevArg starting at 0 (as sdrx_audiotail_*).  Any feed length is valid (0 and < 512 included:
+ * a feed that completes no 512-sample block produces no audio); NCO phase, pending samples, ovlbuf, squelch counter,
+ * m_prevArg, resampler window and distance, and the level accumulators carry across feeds.  m_movingAverage (GUI only)
+ * is left out.  A channel is configured at creation; there is no mid-stream retune.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_wfm sdrx_wfm_t;
+typedef struct sdrx_wfm_cfg {
+    int32_t in_rate;        /* channelizer output rate (m_inputSampleRate) */
+    int32_t nco_freq;       /* m_nco.setFreq(nco_freq, in_rate): the demod passes -frequencyOffset */
+    int32_t audio_rate;     /* m_audioSampleRate; <= in_rate; distance = step = (Real) in_rate / (Real) audio_rate */
+    float   rf_bandwidth;   /* m_rfBandwidth: create_filter(-(rfBW / 2.0) / in_rate, +...), fmScaling = 1.0f / (rfBW / (Real) in_rate),
+                             * squelch counter cap rfBW / 10, open above rfBW / 20 */
+    float   af_bandwidth;   /* m_afBandwidth: m_interpolator.create(16, in_rate, afBW) */
+    float   volume;         /* m_volume */
+    float   squelch_db;     /* m_squelch: m_squelchLevel = pow(10.0, squelch / 10.0) */
+    int32_t audio_mute;     /* m_audioMute */
+} sdrx_wfm_cfg;
+int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_cfg* cfg);
+int sdrx_wfm_destroy(sdrx_wfm_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_wfm_reset(sdrx_wfm_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to WFMDemod::feed) */
+int sdrx_wfm_feed(sdrx_wfm_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_wfm_feed_dev(sdrx_wfm_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank: the readers
+ * of the samples wait for the bank's stream, and the bank's stream waits until they have consumed the samples */
+int sdrx_wfm_feed_bank(sdrx_wfm_t* h, sdrx_chan_bank_t* bank);
+/* audio of the last feed for channel ch; returns the number of samples written (<0: error) */
+int64_t sdrx_wfm_read(sdrx_wfm_t* h, int32_t ch, int16_t* audio, int64_t cap);
+/* device-side view of the same (valid until the next feed) */
+int sdrx_wfm_last_dev(sdrx_wfm_t* h, int32_t ch, const int16_t** d_audio, int64_t* n);
+/* m_squelchOpen after the last feed: 1 / 0 (<0: error) */
+int sdrx_wfm_squelch_open(sdrx_wfm_t* h, int32_t ch);
+/* m_magsqSum / m_magsqPeak / m_magsqCount of getMagSqLevels; reset != 0 zeroes them as getMagSqLevels does.
+ * peak and count are exact; sum is a parallel double reduction (relative difference <= 2 * count * 2^-53) */
+int sdrx_wfm_levels(sdrx_wfm_t* h, int32_t ch, double* sum, double* peak, int64_t* count, int reset);
+/* design products, for inspection: polyphase taps [16][ntaps], filter spectrum (1024 complex), NCO increment, m_squelchLevel */
+int sdrx_wfm_get_design(sdrx_wfm_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
+                        float* filter_iq, int32_t* nco_inc, float* squelch_level);
+int sdrx_wfm_sync(sdrx_wfm_t* h);
+int sdrx_wfm_set_stream(sdrx_wfm_t* h, void* hip_stream);
+int sdrx_wfm_get_stream(sdrx_wfm_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels */
+int sdrx_wfm_set_timing(sdrx_wfm_t* h, int enabled);
+int sdrx_wfm_get_timing(sdrx_wfm_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the filter-block kernel of the last feed (the feed's largest launch): wfm_fft_kernel, its grid, block and LDS bytes */
+int sdrx_wfm_last_launch(const sdrx_wfm_t* h, char* kernel_name, int name_cap,
+                         int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

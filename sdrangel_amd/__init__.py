@@ -184,6 +184,23 @@ def lib() -> C.CDLL:
         "sdrx_spectrum_set_timing": (C.c_int, [vp, C.c_int]),
         "sdrx_spectrum_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_spectrum_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "sdrx_wfm_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_wfm_destroy": (C.c_int, [vp]),
+        "sdrx_wfm_reset": (C.c_int, [vp]),
+        "sdrx_wfm_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_wfm_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_wfm_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_wfm_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_wfm_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_wfm_squelch_open": (C.c_int, [vp, i32]),
+        "sdrx_wfm_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_wfm_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
+        "sdrx_wfm_sync": (C.c_int, [vp]),
+        "sdrx_wfm_set_stream": (C.c_int, [vp, vp]),
+        "sdrx_wfm_get_stream": (C.c_int, [vp, pp]),
+        "sdrx_wfm_set_timing": (C.c_int, [vp, C.c_int]),
+        "sdrx_wfm_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_wfm_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_fdecim_state_bytes": (i64, [vp]),
         "sdrx_fdecim_get_state": (C.c_int, [vp, vp]),
         "sdrx_fdecim_set_state": (C.c_int, [vp, vp]),
@@ -908,6 +925,116 @@ class BackendBank:
         _check(lib().sdrx_backend_get_design(self._h, ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc)),
                "sdrx_backend_get_design")
         return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value
+
+
+class WfmCfg(C.Structure):
+    """sdrx_wfm_cfg: one WFMDemod (in_rate, nco_freq = -frequencyOffset, audio_rate, WFMDemodSettings)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
+                ("rf_bandwidth", C.c_float), ("af_bandwidth", C.c_float), ("volume", C.c_float), ("squelch_db", C.c_float),
+                ("audio_mute", C.c_int32)]
+
+
+def wfm_required_bw(rf_bw: int) -> int:
+    """WFMDemod::requiredBW: the rate the demodulator asks its channelizer for"""
+    return 48000 if rf_bw <= 48000 else (3 * rf_bw) // 2
+
+
+class WfmDemodBank:
+    """N wideband-FM demodulators (WFMDemod::feed): int16 I/Q at the channelizer's output rate in, mono qint16 audio out."""
+
+    def __init__(self, cfgs, device: int = 0):
+        self.n_ch = len(cfgs)
+        arr = (WfmCfg * self.n_ch)(*cfgs)
+        self._h = C.c_void_p()
+        _check(lib().sdrx_wfm_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_wfm_create")
+        self.cfgs = list(cfgs)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().sdrx_wfm_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = _del
+
+    def reset(self):
+        _check(lib().sdrx_wfm_reset(self._h), "sdrx_wfm_reset")
+
+    def feed(self, per_channel_iq):
+        bufs = [_i16(x) for x in per_channel_iq]
+        ptrs = (C.c_void_p * self.n_ch)(*[b.ctypes.data for b in bufs])
+        ns = (C.c_int64 * self.n_ch)(*[b.size // 2 for b in bufs])
+        _check(lib().sdrx_wfm_feed(self._h, ptrs, ns), "sdrx_wfm_feed")
+
+    def feed_dev(self, ptrs, counts):
+        """device pointers (4-byte aligned) and complex sample counts per channel; asynchronous on the handle's stream"""
+        p = (C.c_void_p * self.n_ch)(*ptrs)
+        n = (C.c_int64 * self.n_ch)(*counts)
+        _check(lib().sdrx_wfm_feed_dev(self._h, p, n), "sdrx_wfm_feed_dev")
+
+    def feed_bank(self, bank: "ChannelizerBank"):
+        """channel c takes what the bank's last feed produced for its channel c; ordered on the device, no host sync"""
+        _check(lib().sdrx_wfm_feed_bank(self._h, bank._h), "sdrx_wfm_feed_bank")
+
+    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
+        if cap is None:
+            cap = self.last_dev(ch)[1]
+        out = np.empty(max(cap, 1), np.int16)
+        n = lib().sdrx_wfm_read(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_wfm_read rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def last_dev(self, ch: int):
+        """(device pointer, count) of the last feed's audio of channel ch"""
+        p, n = C.c_void_p(), C.c_int64()
+        _check(lib().sdrx_wfm_last_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_wfm_last_dev")
+        return p.value or 0, n.value
+
+    def squelch_open(self, ch: int) -> bool:
+        rc = lib().sdrx_wfm_squelch_open(self._h, ch)
+        if rc < 0:
+            raise SdrxError(f"sdrx_wfm_squelch_open rc={rc}: {lib().sdrx_last_error().decode()}")
+        return bool(rc)
+
+    def levels(self, ch: int, reset: bool = False):
+        """(m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
+        s, p, n = C.c_double(), C.c_double(), C.c_int64()
+        _check(lib().sdrx_wfm_levels(self._h, ch, C.byref(s), C.byref(p), C.byref(n), int(reset)), "sdrx_wfm_levels")
+        return s.value, p.value, n.value
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], filter spectrum as 2048 floats, NCO increment, squelch level)"""
+        nt, inc, lvl = C.c_int32(), C.c_int32(), C.c_float()
+        taps = np.zeros(16 * 128, np.float32)
+        filt = np.zeros(2048, np.float32)
+        _check(lib().sdrx_wfm_get_design(self._h, ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc), C.byref(lvl)),
+               "sdrx_wfm_get_design")
+        return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value, lvl.value
+
+    def sync(self):
+        _check(lib().sdrx_wfm_sync(self._h), "sdrx_wfm_sync")
+
+    def set_stream(self, hip_stream: int | None):
+        _check(lib().sdrx_wfm_set_stream(self._h, hip_stream), "sdrx_wfm_set_stream")
+
+    def get_stream(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sdrx_wfm_get_stream(self._h, C.byref(p)), "sdrx_wfm_get_stream")
+        return p.value or 0
+
+    def set_timing(self, on: bool):
+        _check(lib().sdrx_wfm_set_timing(self._h, int(on)), "sdrx_wfm_set_timing")
+
+    def get_timing(self, reset: bool = True):
+        ms, n = C.c_double(), C.c_int64()
+        _check(lib().sdrx_wfm_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_wfm_get_timing")
+        return ms.value, n.value
+
+    def last_launch(self) -> dict:
+        name = C.create_string_buffer(128)
+        g, b, l = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().sdrx_wfm_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
+        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
 
 
 class AudioTailCfg(C.Structure):

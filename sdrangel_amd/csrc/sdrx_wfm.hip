@@ -1,0 +1,521 @@
+// libsdrx.so: sdrx_wfm_* -- N wideband-FM demodulators (WFMDemod::feed, plugins/channelrx/demodwfm/wfmdemod.cpp:90-183) on
+// one device: int16 I/Q at the channelizer's output rate in, mono qint16 audio out.  Kernels: wfm_kernels.hpp.
+// Host side: the design products exactly as applyChannelSettings / applySettings derive them (wfmdemod.cpp:277-345),
+// launches, buffer bookkeeping.
+#include "sdrx_common.hpp"
+#include "wfm_kernels.hpp"
+#include "backend_design.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+using namespace sdrx;
+
+namespace {
+
+struct WfmHost {
+    DevBuf head, tail, arg, flag, blk, dem, sched, audio, stage_in;
+    uint32_t* pend[2] = { nullptr, nullptr };
+    int cur = 0;
+    int64_t cap_in = 0;
+    int pending = 0;              // host mirror of WfmChan::pending (a function of the feed lengths only)
+};
+
+// per-block scratch of one channel, carved out of one allocation
+constexpr size_t BLK_BYTES = sizeof(WfmClamp) + sizeof(double) + sizeof(float) + 3 * sizeof(int);
+
+} // namespace
+
+struct sdrx_wfm {
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    int n_ch = 0;
+    std::vector<sdrx_wfm_cfg> cfg;
+    std::vector<WfmHost> ch;
+    std::vector<WfmChan> h_chan;  // configuration and the state of a fresh handle
+    WfmChan* d_chan = nullptr;
+    WfmBufs* d_bufs = nullptr;
+    WfmBufs* h_bufs = nullptr;    // pinned: the per-feed table goes to the device in one async copy
+    hipEvent_t bufs_ev = nullptr, prod_ev = nullptr, cons_ev = nullptr;
+    float* d_nco = nullptr; float* d_taps = nullptr; float2* d_filters = nullptr; float* d_utbl = nullptr;
+    std::vector<float> taps_all, filters_all;
+    std::vector<int> taps_off, ntaps;
+    bool any_dyadic = false, any_serial = false;
+    EventTimer timer;
+    char last_name[64] = "";
+    int last_grid = 0, last_block = 0, last_lds = 0;
+};
+
+static int validate(int32_t n_ch, const sdrx_wfm_cfg* cfg)
+{
+    if (n_ch <= 0 || !cfg) { set_error("sdrx_wfm_create: bad argument"); return SDRX_EINVAL; }
+    for (int c = 0; c < n_ch; c++) {
+        const sdrx_wfm_cfg& k = cfg[c];
+        if (k.in_rate <= 0 || k.audio_rate <= 0 || k.audio_rate > k.in_rate) {
+            set_error("sdrx_wfm_create: bad channel configuration (need 0 < audio_rate <= in_rate)"); return SDRX_EINVAL;
+        }
+        if (!(k.rf_bandwidth > 0.0f) || !(k.rf_bandwidth <= 1.0e7f) || !(k.af_bandwidth > 0.0f) || !std::isfinite(k.af_bandwidth)) {
+            set_error("sdrx_wfm_create: bad channel configuration (need 0 < rf_bandwidth <= 1e7 and af_bandwidth > 0)"); return SDRX_EINVAL;
+        }
+        if (!std::isfinite(k.volume) || !std::isfinite(k.squelch_db)) {
+            set_error("sdrx_wfm_create: bad channel configuration (volume and squelch_db must be finite)"); return SDRX_EINVAL;
+        }
+    }
+    return SDRX_OK;
+}
+
+static int ensure_capacity(sdrx_wfm* b, int c, int64_t n_in)
+{
+    WfmHost& h = b->ch[(size_t)c];
+    if (n_in <= h.cap_in) return SDRX_OK;
+    int64_t cap = h.cap_in ? h.cap_in : 4096;
+    while (cap < n_in) cap *= 2;
+    const size_t n_blk = (size_t)(cap + WFM_H) / WFM_H + 1;          // pending (< 512) + new
+    const size_t n_s = n_blk * WFM_H;
+    // tail slot 0 (ovlbuf) and the front of dem (the resampler window) carry state: keep them
+    auto grow_keep = [&](DevBuf& buf, size_t bytes, size_t keep) -> int {
+        if (bytes <= buf.cap) return SDRX_OK;
+        void* np = nullptr;
+        SDRX_HIP(hipMalloc(&np, bytes));
+        SDRX_HIP(hipMemsetAsync(np, 0, bytes, b->stream));
+        if (buf.p && keep) SDRX_HIP(hipMemcpyAsync(np, buf.p, keep, hipMemcpyDeviceToDevice, b->stream));
+        SDRX_HIP(hipStreamSynchronize(b->stream));
+        if (buf.p) (void)hipFree(buf.p);
+        buf.p = np; buf.cap = bytes;
+        return SDRX_OK;
+    };
+    int rc;
+    if ((rc = grow_keep(h.head, n_s * 8, 0))) return rc;
+    if ((rc = grow_keep(h.tail, (n_s + WFM_H) * 8, WFM_H * 8))) return rc;
+    if ((rc = grow_keep(h.arg, n_s * 4, 0))) return rc;
+    if ((rc = grow_keep(h.flag, n_s, 0))) return rc;
+    if ((rc = grow_keep(h.blk, n_blk * BLK_BYTES + 64, 0))) return rc;
+    if ((rc = grow_keep(h.dem, (WFM_HIST + n_s + WFM_HIST) * 4, WFM_HIST * 4))) return rc;
+    // every audio sample consumes at least one demodulated sample (step >= 1)
+    if ((rc = grow_keep(h.sched, (n_s + 8) * 8, 0))) return rc;
+    if ((rc = grow_keep(h.audio, (n_s + 8) * 2, 0))) return rc;
+    h.cap_in = cap;
+    return SDRX_OK;
+}
+
+static int upload_fresh_state(sdrx_wfm* b)
+{
+    SDRX_HIP(hipMemcpyAsync(b->d_chan, b->h_chan.data(), (size_t)b->n_ch * sizeof(WfmChan), hipMemcpyHostToDevice, b->stream));
+    for (auto& h : b->ch) {
+        for (int i = 0; i < 2; i++) SDRX_HIP(hipMemsetAsync(h.pend[i], 0, WFM_H * 4, b->stream));
+        if (h.tail.p) SDRX_HIP(hipMemsetAsync(h.tail.p, 0, WFM_H * 8, b->stream));
+        if (h.dem.p) SDRX_HIP(hipMemsetAsync(h.dem.p, 0, WFM_HIST * 4, b->stream));
+        h.pending = 0;
+    }
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    return SDRX_OK;
+}
+
+extern "C" {
+
+int sdrx_wfm_destroy(sdrx_wfm_t* b)
+{
+    if (!b) return SDRX_OK;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    for (auto& h : b->ch) {
+        h.head.release(); h.tail.release(); h.arg.release(); h.flag.release(); h.blk.release();
+        h.dem.release(); h.sched.release(); h.audio.release(); h.stage_in.release();
+        for (int i = 0; i < 2; i++) if (h.pend[i]) (void)hipFree(h.pend[i]);
+    }
+    if (b->d_chan) (void)hipFree(b->d_chan);
+    if (b->d_bufs) (void)hipFree(b->d_bufs);
+    if (b->h_bufs) (void)hipHostFree(b->h_bufs);
+    if (b->bufs_ev) (void)hipEventDestroy(b->bufs_ev);
+    if (b->prod_ev) (void)hipEventDestroy(b->prod_ev);
+    if (b->cons_ev) (void)hipEventDestroy(b->cons_ev);
+    if (b->d_nco) (void)hipFree(b->d_nco);
+    if (b->d_taps) (void)hipFree(b->d_taps);
+    if (b->d_filters) (void)hipFree(b->d_filters);
+    if (b->d_utbl) (void)hipFree(b->d_utbl);
+    b->timer.release();
+    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+    delete b;
+    return SDRX_OK;
+}
+
+int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_cfg* cfg)
+{
+    if (!out) { set_error("sdrx_wfm_create: null out"); return SDRX_EINVAL; }
+    *out = nullptr;
+    int rc = validate(n_ch, cfg); if (rc) return rc;
+    rc = check_device(device); if (rc) return rc;
+    SDRX_HIP(hipSetDevice(device));
+    sdrx_wfm* b = new (std::nothrow) sdrx_wfm;
+    if (!b) return SDRX_ENOMEM;
+    b->device = device; b->n_ch = n_ch;
+    hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { delete b; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
+    b->stream = b->own_stream;
+    b->cfg.assign(cfg, cfg + n_ch);
+    b->ch.resize((size_t)n_ch); b->h_chan.resize((size_t)n_ch);
+    b->taps_off.resize((size_t)n_ch); b->ntaps.resize((size_t)n_ch);
+
+#define WFM_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = hip_fail(e_, #call, __FILE__, __LINE__); sdrx_wfm_destroy(b); return r_; } } while (0)
+    // NCO table (nco.cpp:30-39) and g_fft cosine table (gfft.h:141-150)
+    std::vector<float> nco(WFM_NCO_N);
+    for (int i = 0; i < WFM_NCO_N; i++) nco[(size_t)i] = (float)std::cos((2.0 * PI_D * i) / WFM_NCO_N);
+    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_nco), WFM_NCO_N * 4));
+    WFM_TRY(hipMemcpy(b->d_nco, nco.data(), WFM_NCO_N * 4, hipMemcpyHostToDevice));
+    {
+        const int n = WFM_FFT;
+        std::vector<float> utbl((size_t)n / 4 + 1);
+        utbl[0] = 1.0f;
+        for (int i = 1; i < n / 4; i++) utbl[(size_t)i] = (float)std::cos((2.0 * 3.141592653589793238462643383279502884197 * (float)i) / (float)n);
+        utbl[(size_t)n / 4] = 0.0f;
+        WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_utbl), ((size_t)n / 4 + 1) * 4));
+        WFM_TRY(hipMemcpy(b->d_utbl, utbl.data(), ((size_t)n / 4 + 1) * 4, hipMemcpyHostToDevice));
+    }
+    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_filters), (size_t)n_ch * WFM_FFT * 8));
+    b->filters_all.assign((size_t)n_ch * WFM_FFT * 2, 0.0f);
+    for (int c = 0; c < n_ch; c++) {
+        const sdrx_wfm_cfg& k = cfg[c];
+        WfmHost& h = b->ch[(size_t)c];
+        // m_interpolator.create(16, inputSampleRate, afBandwidth): channels with the same arguments share one tap table
+        int same = -1;
+        for (int p = 0; p < c && same < 0; p++) if (cfg[p].in_rate == k.in_rate && cfg[p].af_bandwidth == k.af_bandwidth) same = p;
+        if (same >= 0) {
+            b->taps_off[(size_t)c] = b->taps_off[(size_t)same]; b->ntaps[(size_t)c] = b->ntaps[(size_t)same];
+        } else {
+            std::vector<float> poly; int nt = 0;
+            design_interp(16, (double)k.in_rate, (double)k.af_bandwidth, 4.5, poly, &nt);
+            b->taps_off[(size_t)c] = (int)b->taps_all.size(); b->ntaps[(size_t)c] = nt;
+            b->taps_all.insert(b->taps_all.end(), poly.begin(), poly.end());
+        }
+        // Real lowCut = -(rfBandwidth / 2.0) / inputSampleRate, hiCut = +...; m_rfFilter->create_filter(lowCut, hiCut):
+        // windowed sinc in the first 512 bins, forward FFT (the kernel code of the data path), normalised to max |H| over
+        // bins 0..511 (fftfilt.cpp:108-146)
+        const float f1 = (float)(-((double)k.rf_bandwidth / 2.0) / (double)k.in_rate);
+        const float f2 = (float)(((double)k.rf_bandwidth / 2.0) / (double)k.in_rate);
+        {
+            const int flen = WFM_FFT, h2 = flen / 2;
+            std::vector<float> f((size_t)flen * 2, 0.0f);
+            const bool lp = f2 != 0, hp = f1 != 0;
+            for (int i = 0; i < h2; i++) {
+                float v = 0;
+                if (lp) v += fsinc(f2, i, h2);
+                if (hp) v -= fsinc(f1, i, h2);
+                f[(size_t)(2 * i)] = v;
+            }
+            if (hp && f2 < f1) f[(size_t)(2 * (h2 / 2))] += 1;
+            for (int i = 0; i < h2; i++) { const float w = blackman(i, h2); f[(size_t)(2 * i)] *= w; f[(size_t)(2 * i + 1)] *= w; }
+            float2* dst = b->d_filters + (size_t)c * WFM_FFT;
+            WFM_TRY(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(be_fft_design_kernel<WFM_FFT>, dim3(1), dim3(WFM_FFT / 8), 0, b->stream, dst, b->d_utbl);
+            WFM_TRY(hipGetLastError());
+            WFM_TRY(hipStreamSynchronize(b->stream));
+            WFM_TRY(hipMemcpy(f.data(), dst, (size_t)flen * 8, hipMemcpyDeviceToHost));
+            float scale = 0;
+            for (int i = 0; i < h2; i++) { const float mag = hypotf(f[(size_t)(2 * i)], f[(size_t)(2 * i + 1)]); if (mag > scale) scale = mag; }
+            if (scale != 0) for (int i = 0; i < flen * 2; i++) f[(size_t)i] /= scale;
+            WFM_TRY(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice));
+            std::memcpy(&b->filters_all[(size_t)c * WFM_FFT * 2], f.data(), (size_t)flen * 8);
+        }
+        WfmChan& s = b->h_chan[(size_t)c];
+        std::memset(&s, 0, sizeof s);
+        s.nco_inc = (int)(((float)k.nco_freq * WFM_NCO_N) / (float)k.in_rate);          // NCO::setFreq (float math, truncation)
+        s.step = (float)k.in_rate / (float)k.audio_rate;
+        s.ntaps = b->ntaps[(size_t)c]; s.taps_off = b->taps_off[(size_t)c];
+        s.filt_off = c * WFM_FFT;
+        const float excursion = k.rf_bandwidth / (float)k.in_rate;                        // m_fmExcursion
+        s.fm_scaling = 1.0f / excursion;
+        s.squelch_level = (float)std::pow(10.0, (double)k.squelch_db / 10.0);
+        s.cap_f = k.rf_bandwidth / 10; s.open_f = k.rf_bandwidth / 20;
+        s.cap = wfm_counter_cap(s.cap_f);
+        s.volume = k.volume; s.mute = k.audio_mute ? 1 : 0;
+        s.dy_q = -1; s.dy_S = 0;
+        if (!getenv("SDRX_WFM_SERIAL_SCHEDULE"))
+            for (int q = 0; q <= 10; q++) {
+                const float v = s.step * (float)(1 << q);                                  // exact (power of two)
+                if (v == std::floor(v) && v < (float)(1 << 20)) { s.dy_q = q; s.dy_S = (int)v; break; }
+            }
+        (s.dy_q >= 0 ? b->any_dyadic : b->any_serial) = true;
+        s.distance = s.step;                                                               // m_interpolatorDistanceRemain starts at in / audio
+        if (s.ntaps > WFM_HIST) { set_error("sdrx_wfm_create: resampler window does not fit"); sdrx_wfm_destroy(b); return SDRX_EINVAL; }
+        for (int i = 0; i < 2; i++) WFM_TRY(hipMalloc(reinterpret_cast<void**>(&h.pend[i]), WFM_H * 4));
+    }
+    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_taps), b->taps_all.size() * 4));
+    WFM_TRY(hipMemcpy(b->d_taps, b->taps_all.data(), b->taps_all.size() * 4, hipMemcpyHostToDevice));
+    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(WfmChan)));
+    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(WfmBufs)));
+    WFM_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(WfmBufs), hipHostMallocDefault));
+    WFM_TRY(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming));
+    WFM_TRY(hipEventRecord(b->bufs_ev, b->stream));
+    WFM_TRY(hipEventCreateWithFlags(&b->prod_ev, hipEventDisableTiming));
+    WFM_TRY(hipEventCreateWithFlags(&b->cons_ev, hipEventDisableTiming));
+#undef WFM_TRY
+    rc = upload_fresh_state(b);
+    if (rc) { sdrx_wfm_destroy(b); return rc; }
+    *out = b;
+    return SDRX_OK;
+}
+
+int sdrx_wfm_reset(sdrx_wfm_t* b)
+{
+    if (!b) { set_error("sdrx_wfm_reset: null handle"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    return upload_fresh_state(b);
+}
+
+// producer != nullptr: the input samples are being written on that stream.  The schedule kernels (they need the counts
+// only) are launched first and overlap the producer; the readers of `in` (wfm_fft: NCO mix on load, wfm_pend: the raw
+// remainder) wait for the producer on the device, and the producer's stream waits until they are done before it may run
+// anything queued after this call.
+static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n_per_ch, hipStream_t producer = nullptr)
+{
+    int64_t max_blocks = 0, max_out = 0;
+    for (int c = 0; c < b->n_ch; c++) {
+        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff) { set_error("sdrx_wfm_feed: bad length"); return SDRX_EINVAL; }
+        if (n_per_ch[c] > 0 && (!d_iq[c] || (reinterpret_cast<uintptr_t>(d_iq[c]) & 3u))) { set_error("sdrx_wfm_feed: null or misaligned channel pointer"); return SDRX_EINVAL; }
+    }
+    for (int c = 0; c < b->n_ch; c++) {
+        int rc = ensure_capacity(b, c, std::max<int64_t>(n_per_ch[c], 1)); if (rc) return rc;
+        const int64_t nb = (b->ch[(size_t)c].pending + n_per_ch[c]) / WFM_H;
+        max_blocks = std::max(max_blocks, nb);
+        // every audio sample after the first of a feed consumes >= floor(step) demodulated samples
+        const int64_t per_out = std::max<int64_t>(1, (int64_t)std::floor(b->h_chan[(size_t)c].step));
+        max_out = std::max(max_out, std::min<int64_t>(nb * WFM_H, nb * WFM_H / per_out + 4));
+    }
+    SDRX_HIP(hipEventSynchronize(b->bufs_ev));            // previous feed's copy has read the table
+    for (int c = 0; c < b->n_ch; c++) {
+        WfmHost& h = b->ch[(size_t)c];
+        WfmBufs& u = b->h_bufs[c];
+        const size_t n_blk = (size_t)(h.cap_in + WFM_H) / WFM_H + 1;
+        u.in = reinterpret_cast<const uint32_t*>(d_iq[c]);
+        u.pend = h.pend[h.cur]; u.pend_next = h.pend[h.cur ^ 1];
+        u.head = static_cast<float2*>(h.head.p); u.tail = static_cast<float2*>(h.tail.p);
+        u.arg = static_cast<float*>(h.arg.p); u.flag = static_cast<uint8_t*>(h.flag.p);
+        char* p = static_cast<char*>(h.blk.p);
+        u.blk_sum = reinterpret_cast<double*>(p); p += n_blk * sizeof(double);
+        u.blk_map = reinterpret_cast<WfmClamp*>(p); p += n_blk * sizeof(WfmClamp);
+        u.blk_peak = reinterpret_cast<float*>(p); p += n_blk * sizeof(float);
+        u.blk_state = reinterpret_cast<int*>(p); p += n_blk * sizeof(int);
+        u.blk_first = reinterpret_cast<int*>(p); p += n_blk * sizeof(int);
+        u.blk_last = reinterpret_cast<int*>(p);
+        u.dem = static_cast<float*>(h.dem.p); u.sched = static_cast<uint2*>(h.sched.p); u.audio = static_cast<int16_t*>(h.audio.p);
+        u.n_in = n_per_ch[c];
+    }
+    int rc = b->timer.begin(b->stream); if (rc) return rc;
+    SDRX_HIP(hipMemcpyAsync(b->d_bufs, b->h_bufs, (size_t)b->n_ch * sizeof(WfmBufs), hipMemcpyHostToDevice, b->stream));
+    SDRX_HIP(hipEventRecord(b->bufs_ev, b->stream));
+    const unsigned nc = (unsigned)b->n_ch, gc = (nc + 63) / 64, nblk = (unsigned)max_blocks;
+    hipLaunchKernelGGL(wfm_prep_kernel, dim3(gc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->n_ch);
+    SDRX_HIP(hipGetLastError());
+    if (nblk && b->any_dyadic) {
+        hipLaunchKernelGGL(wfm_sched_fill_kernel, dim3((unsigned)((max_out + 255) / 256), nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+        SDRX_HIP(hipGetLastError());
+    }
+    // lanes whose channel the closed form took exit at once (prep's off-grid guard can hand a channel back)
+    hipLaunchKernelGGL(wfm_sched_walk_kernel, dim3(gc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->n_ch);
+    SDRX_HIP(hipGetLastError());
+    const bool cross = producer && producer != b->stream;
+    if (cross) {
+        SDRX_HIP(hipEventRecord(b->prod_ev, producer));
+        SDRX_HIP(hipStreamWaitEvent(b->stream, b->prod_ev, 0));
+    }
+    if (nblk) {
+        hipLaunchKernelGGL(wfm_fft_kernel, dim3(nblk, nc), dim3(WFM_FFT / 8), 0, b->stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl, b->d_nco);
+        SDRX_HIP(hipGetLastError());
+        snprintf(b->last_name, sizeof(b->last_name), "%s", "wfm_fft_kernel");
+        b->last_grid = (int)(nblk * nc); b->last_block = WFM_FFT / 8; b->last_lds = (int)(2 * WFM_FFT * sizeof(float2) + (WFM_FFT / 4 + 1) * sizeof(float));
+    }
+    hipLaunchKernelGGL(wfm_pend_kernel, dim3(nc), dim3(WFM_H), 0, b->stream, b->d_chan, b->d_bufs);
+    SDRX_HIP(hipGetLastError());
+    if (cross) {
+        SDRX_HIP(hipEventRecord(b->cons_ev, b->stream));
+        SDRX_HIP(hipStreamWaitEvent(producer, b->cons_ev, 0));
+    }
+    if (nblk) {
+        hipLaunchKernelGGL(wfm_level_kernel, dim3(nblk, nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(wfm_blockscan_kernel, dim3(nc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(wfm_demod_kernel, dim3(nblk, nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(wfm_fixup_kernel, dim3(nc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(wfm_fir_kernel, dim3((unsigned)((max_out + 255) / 256), nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs, b->d_taps);
+        SDRX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(wfm_carry_kernel, dim3(nc), dim3(WFM_H), 0, b->stream, b->d_chan, b->d_bufs);
+    SDRX_HIP(hipGetLastError());
+    rc = b->timer.end(b->stream); if (rc) return rc;
+    for (int c = 0; c < b->n_ch; c++) {
+        WfmHost& h = b->ch[(size_t)c];
+        h.cur ^= 1;
+        h.pending = (int)((h.pending + n_per_ch[c]) % WFM_H);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_wfm_feed_dev(sdrx_wfm_t* b, const int16_t* const* d_iq, const int64_t* n_per_ch)
+{
+    if (!b || !d_iq || !n_per_ch) { set_error("sdrx_wfm_feed_dev: null argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->device));
+    return feed_common(b, d_iq, n_per_ch);
+}
+
+int sdrx_wfm_feed_bank(sdrx_wfm_t* b, sdrx_chan_bank_t* bank)
+{
+    if (!b || !bank) { set_error("sdrx_wfm_feed_bank: null argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->device));
+    void* ps = nullptr;
+    int rc = sdrx_chan_bank_get_stream(bank, &ps); if (rc) return rc;
+    std::vector<const int16_t*> d((size_t)b->n_ch);
+    std::vector<int64_t> n((size_t)b->n_ch);
+    for (int c = 0; c < b->n_ch; c++) {
+        rc = sdrx_chan_bank_last_dev(bank, c, &d[(size_t)c], &n[(size_t)c]);
+        if (rc) { set_error("sdrx_wfm_feed_bank: the bank has fewer channels than the demodulator bank"); return rc; }
+    }
+    return feed_common(b, d.data(), n.data(), static_cast<hipStream_t>(ps));
+}
+
+int sdrx_wfm_feed(sdrx_wfm_t* b, const int16_t* const* iq, const int64_t* n_per_ch)
+{
+    if (!b || !iq || !n_per_ch) { set_error("sdrx_wfm_feed: null argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    std::vector<const int16_t*> d((size_t)b->n_ch);
+    for (int c = 0; c < b->n_ch; c++) {
+        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff || (n_per_ch[c] > 0 && !iq[c])) { set_error("sdrx_wfm_feed: bad length or null channel pointer"); return SDRX_EINVAL; }
+        WfmHost& h = b->ch[(size_t)c];
+        int rc = h.stage_in.reserve((size_t)std::max<int64_t>(n_per_ch[c], 1) * 4); if (rc) return rc;
+        if (n_per_ch[c] > 0) SDRX_HIP(hipMemcpyAsync(h.stage_in.p, iq[c], (size_t)n_per_ch[c] * 4, hipMemcpyHostToDevice, b->stream));
+        d[(size_t)c] = static_cast<const int16_t*>(h.stage_in.p);
+    }
+    int rc = feed_common(b, d.data(), n_per_ch); if (rc) return rc;
+    SDRX_HIP(hipStreamSynchronize(b->stream));            // the caller's buffers are free again on return
+    return SDRX_OK;
+}
+
+static int fetch_state(sdrx_wfm* b, int32_t c, WfmChan* s)
+{
+    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipMemcpyAsync(s, b->d_chan + c, sizeof *s, hipMemcpyDeviceToHost, b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    return SDRX_OK;
+}
+
+int64_t sdrx_wfm_read(sdrx_wfm_t* b, int32_t c, int16_t* audio, int64_t cap)
+{
+    if (!b || c < 0 || c >= b->n_ch || cap < 0 || (cap > 0 && !audio)) { set_error("sdrx_wfm_read: bad argument"); return SDRX_EINVAL; }
+    WfmChan s;
+    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    const int64_t n = std::min<int64_t>(s.n_out, cap);
+    if (n == 0) return 0;
+    SDRX_HIP(hipMemcpy(audio, b->ch[(size_t)c].audio.p, (size_t)n * 2, hipMemcpyDeviceToHost));
+    return n;
+}
+
+int sdrx_wfm_last_dev(sdrx_wfm_t* b, int32_t c, const int16_t** d_audio, int64_t* n)
+{
+    if (!b || c < 0 || c >= b->n_ch || !d_audio || !n) { set_error("sdrx_wfm_last_dev: bad argument"); return SDRX_EINVAL; }
+    WfmChan s;
+    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    *d_audio = static_cast<const int16_t*>(b->ch[(size_t)c].audio.p);
+    *n = s.n_out;
+    return SDRX_OK;
+}
+
+int sdrx_wfm_squelch_open(sdrx_wfm_t* b, int32_t c)
+{
+    if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_wfm_squelch_open: bad argument"); return SDRX_EINVAL; }
+    WfmChan s;
+    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    return s.sq_open;
+}
+
+int sdrx_wfm_levels(sdrx_wfm_t* b, int32_t c, double* sum, double* peak, int64_t* count, int reset)
+{
+    if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_wfm_levels: bad argument"); return SDRX_EINVAL; }
+    WfmChan s;
+    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    if (sum) *sum = s.magsq_sum;
+    if (peak) *peak = s.magsq_peak;
+    if (count) *count = s.magsq_count;
+    if (reset) {                                          // getMagSqLevels: sum, peak and count back to 0
+        char* base = reinterpret_cast<char*>(b->d_chan + c);
+        SDRX_HIP(hipMemsetAsync(base + offsetof(WfmChan, magsq_sum), 0, sizeof(double), b->stream));
+        SDRX_HIP(hipMemsetAsync(base + offsetof(WfmChan, magsq_peak), 0, sizeof(double), b->stream));
+        SDRX_HIP(hipMemsetAsync(base + offsetof(WfmChan, magsq_count), 0, sizeof(long long), b->stream));
+        SDRX_HIP(hipStreamSynchronize(b->stream));
+    }
+    return SDRX_OK;
+}
+
+int sdrx_wfm_get_design(sdrx_wfm_t* b, int32_t c, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
+                        float* filter_iq, int32_t* nco_inc, float* squelch_level)
+{
+    if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_wfm_get_design: bad channel"); return SDRX_EINVAL; }
+    const int nt = b->ntaps[(size_t)c];
+    if (ntaps_per_phase) *ntaps_per_phase = nt;
+    if (taps && taps_cap > 0) std::memcpy(taps, &b->taps_all[(size_t)b->taps_off[(size_t)c]], (size_t)std::min(taps_cap, nt * 16) * 4);
+    if (filter_iq) std::memcpy(filter_iq, &b->filters_all[(size_t)c * WFM_FFT * 2], WFM_FFT * 8);
+    if (nco_inc) *nco_inc = b->h_chan[(size_t)c].nco_inc;
+    if (squelch_level) *squelch_level = b->h_chan[(size_t)c].squelch_level;
+    return SDRX_OK;
+}
+
+int sdrx_wfm_sync(sdrx_wfm_t* b)
+{
+    if (!b) return SDRX_EINVAL;
+    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    return SDRX_OK;
+}
+
+int sdrx_wfm_set_stream(sdrx_wfm_t* b, void* hip_stream)
+{
+    if (!b) return SDRX_EINVAL;
+    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    b->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : b->own_stream;
+    return SDRX_OK;
+}
+
+int sdrx_wfm_get_stream(sdrx_wfm_t* b, void** hip_stream)
+{
+    if (!b || !hip_stream) return SDRX_EINVAL;
+    *hip_stream = b->stream;
+    return SDRX_OK;
+}
+
+int sdrx_wfm_set_timing(sdrx_wfm_t* b, int enabled)
+{
+    if (!b) return SDRX_EINVAL;
+    b->timer.enabled = enabled != 0;
+    return SDRX_OK;
+}
+
+int sdrx_wfm_get_timing(sdrx_wfm_t* b, double* total_ms, int64_t* feeds, int reset)
+{
+    if (!b) return SDRX_EINVAL;
+    SDRX_HIP(hipSetDevice(b->device));
+    int rc = b->timer.collect(b->stream); if (rc) return rc;
+    if (total_ms) *total_ms = b->timer.total_ms;
+    if (feeds) *feeds = b->timer.count;
+    if (reset) { b->timer.total_ms = 0; b->timer.count = 0; }
+    return SDRX_OK;
+}
+
+int sdrx_wfm_last_launch(const sdrx_wfm_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes)
+{
+    if (!b) return SDRX_EINVAL;
+    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", b->last_name);
+    if (grid) *grid = b->last_grid;
+    if (block) *block = b->last_block;
+    if (lds_bytes) *lds_bytes = b->last_lds;
+    return SDRX_OK;
+}
+
+} // extern "C"
