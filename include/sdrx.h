@@ -248,6 +248,8 @@ int sdrx_backend_feed_bank(sdrx_backend_t* h, sdrx_chan_bank_t* bank);
 /* outputs of the last feed for channel ch: complex (re,im pairs) unless a discriminator is on;
  * returns the number of FLOATS written (<0: error) */
 int64_t sdrx_backend_read(sdrx_backend_t* h, int32_t ch, float* out, int64_t cap_floats);
+/* device-side view of the same (valid until the next feed): pointer and number of FLOATS */
+int sdrx_backend_last_dev(sdrx_backend_t* h, int32_t ch, const float** d_out, int64_t* n_floats);
 /* design products, for inspection: polyphase taps [16][ntaps], filter spectrum (2048 complex slots; 1024 used
  * unless filt_mode 4), NCO increment */
 int sdrx_backend_get_design(sdrx_backend_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
@@ -618,6 +620,69 @@ int sdrx_wfm_get_timing(sdrx_wfm_t* h, double* total_ms, int64_t* feeds, int res
 /* the filter-block kernel of the last feed (the feed's largest launch): wfm_fft_kernel, its grid, block and LDS bytes */
 int sdrx_wfm_last_launch(const sdrx_wfm_t* h, char* kernel_name, int name_cap,
                          int* grid, int* block, int* lds_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * AM demodulator bank: AMDemod::feed and AMDemod::processOneSample (plugins/channelrx/demodam/amdemod.cpp:101-276) in
+ * envelope mode (m_pll = false, the default), N channels per handle, each fed with int16 I/Q at the channelizer's output rate:
+ *     c = Complex(re, im) * m_nco.nextIQ();  m_interpolator.decimate(&dist, c, &ci)        as sdrx_backend_* (filt_mode 0)
+ *     per ci: magsq = re*re + im*im (re = ci.re / 32768.0f); m_movingAverage(magsq) (MovingAverageUtil<Real, double, 16>);
+ *             level sums; m_squelchDelayLine.write(magsq); squelch counter against m_magsq, cap rate / 10, open at rate / 20
+ *     open and not muted: demod = sqrt(readBack(rate / 20)); m_volumeAGC.feed(demod) (SimpleAGC, rate / 10 entries of 0.003f);
+ *             demod = (demod - agc) / agc; [m_bandpass.filter(demod) / 301.0f]; attack = (count - 0.05f * rate) / (0.05f * rate);
+ *             (qint16)(demod * smootherstep(attack) * (rate / 24) * volume);   closed or muted: 0
+ * The state of a fresh handle is the state after start(): distanceRemain = 0, so the first input already emits an output.
+ * Output: mono qint16 audio, the value the reference writes to .l and .r, bit-identical to the strict-IEEE scalar reference
+ * build.  Any feed length is valid (0 included); NCO phase, resampler window and distance, moving average, delay line,
+ * counter, AGC history, Bandpass ring and level accumulators carry across feeds.
+ *   - the delay line's contents start at 0.  DoubleBufferFIFO allocates with new T[] and does not clear, so a squelch that
+ *     is above its level from the very first output opens at audio index rate / 20 - 1 and reads one slot that was never
+ *     written; with 0 there the root is 0, the AGC is not fed and that sample is 0
+ *   - left out: m_pll / sync-AM, the interpolating branch (audio_rate > in_rate: SDRX_EINVAL), AudioFifo, and mid-stream
+ *     retune -- a channel is configured at creation
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_am sdrx_am_t;
+typedef struct sdrx_am_cfg {
+    int32_t in_rate;          /* channelizer output rate (m_inputSampleRate) */
+    int32_t nco_freq;         /* m_nco.setFreq(nco_freq, in_rate): the demod passes -frequencyOffset */
+    int32_t audio_rate;       /* m_audioSampleRate; 1000 <= audio_rate <= in_rate; distance = (Real) in_rate / (Real) audio_rate */
+    float   rf_bandwidth;     /* m_rfBandwidth: m_interpolator.create(16, in_rate, rfBW / 2.2f), m_bandpass.create(301, audio_rate, 300.0, rfBW / 2.0f) */
+    float   volume;           /* m_volume */
+    float   squelch_db;       /* m_squelch: m_squelchLevel = pow(10.0, squelch / 10.0) */
+    int32_t audio_mute;       /* m_audioMute */
+    int32_t bandpass_enable;  /* m_bandpassEnable */
+} sdrx_am_cfg;
+int sdrx_am_create(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg* cfg);
+int sdrx_am_destroy(sdrx_am_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_am_reset(sdrx_am_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to AMDemod::feed) */
+int sdrx_am_feed(sdrx_am_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_am_feed_dev(sdrx_am_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_am_feed_bank(sdrx_am_t* h, sdrx_chan_bank_t* bank);
+/* audio of the last feed for channel ch; returns the number of samples written (<0: error) */
+int64_t sdrx_am_read(sdrx_am_t* h, int32_t ch, int16_t* audio, int64_t cap);
+/* device-side view of the same (valid until the next feed) */
+int sdrx_am_last_dev(sdrx_am_t* h, int32_t ch, const int16_t** d_audio, int64_t* n);
+/* m_squelchOpen after the last feed: 1 / 0 (<0: error) */
+int sdrx_am_squelch_open(sdrx_am_t* h, int32_t ch);
+/* magsq: m_magsq, the 16-sample moving average after the last sample; sum / peak / count: m_magsqSum / m_magsqPeak /
+ * m_magsqCount of getMagSqLevels, zeroed by reset != 0 as getMagSqLevels does.  magsq, peak and count are exact; sum is a
+ * parallel double reduction (relative difference <= 2 * count * 2^-53) */
+int sdrx_am_levels(sdrx_am_t* h, int32_t ch, double* magsq, double* sum, double* peak, int64_t* count, int reset);
+/* design products, for inspection: polyphase taps [16][ntaps], the 151 folded Bandpass taps, NCO increment, m_squelchLevel */
+int sdrx_am_get_design(sdrx_am_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
+                       float* bandpass_taps, int32_t* nco_inc, float* squelch_level);
+int sdrx_am_sync(sdrx_am_t* h);
+int sdrx_am_set_stream(sdrx_am_t* h, void* hip_stream);
+int sdrx_am_get_stream(sdrx_am_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_am_set_timing(sdrx_am_t* h, int enabled);
+int sdrx_am_get_timing(sdrx_am_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the output kernel of the last feed (Bandpass, attack, conversion): am_out_kernel, its grid, block and LDS bytes */
+int sdrx_am_last_launch(const sdrx_am_t* h, char* kernel_name, int name_cap,
+                        int* grid, int* block, int* lds_bytes);
 
 #ifdef __cplusplus
 }

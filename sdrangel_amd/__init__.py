@@ -142,6 +142,7 @@ def lib() -> C.CDLL:
         "sdrx_fdecim_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
         "sdrx_fdecim_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_backend_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_backend_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
         "sdrx_backend_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32)]),
         "sdrx_backend_sync": (C.c_int, [vp]),
         "sdrx_audiotail_create": (C.c_int, [pp, C.c_int, i32, vp]),
@@ -201,6 +202,23 @@ def lib() -> C.CDLL:
         "sdrx_wfm_set_timing": (C.c_int, [vp, C.c_int]),
         "sdrx_wfm_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_wfm_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "sdrx_am_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_am_destroy": (C.c_int, [vp]),
+        "sdrx_am_reset": (C.c_int, [vp]),
+        "sdrx_am_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_am_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_am_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_am_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_am_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_am_squelch_open": (C.c_int, [vp, i32]),
+        "sdrx_am_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_am_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
+        "sdrx_am_sync": (C.c_int, [vp]),
+        "sdrx_am_set_stream": (C.c_int, [vp, vp]),
+        "sdrx_am_get_stream": (C.c_int, [vp, pp]),
+        "sdrx_am_set_timing": (C.c_int, [vp, C.c_int]),
+        "sdrx_am_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_am_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_fdecim_state_bytes": (i64, [vp]),
         "sdrx_fdecim_get_state": (C.c_int, [vp, vp]),
         "sdrx_fdecim_set_state": (C.c_int, [vp, vp]),
@@ -915,6 +933,12 @@ class BackendBank:
             raise SdrxError(f"sdrx_backend_read rc={n}: {lib().sdrx_last_error().decode()}")
         return out[:n].copy()
 
+    def last_dev(self, ch: int):
+        """(device pointer, number of floats) of the last feed's output of channel ch"""
+        p, n = C.c_void_p(), C.c_int64()
+        _check(lib().sdrx_backend_last_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_backend_last_dev")
+        return p.value or 0, n.value
+
     def sync(self):
         _check(lib().sdrx_backend_sync(self._h), "sdrx_backend_sync")
 
@@ -1034,6 +1058,111 @@ class WfmDemodBank:
         name = C.create_string_buffer(128)
         g, b, l = C.c_int(), C.c_int(), C.c_int()
         _check(lib().sdrx_wfm_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
+        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
+
+
+class AmCfg(C.Structure):
+    """sdrx_am_cfg: one AMDemod in envelope mode (in_rate, nco_freq = -frequencyOffset, audio_rate, AMDemodSettings)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
+                ("rf_bandwidth", C.c_float), ("volume", C.c_float), ("squelch_db", C.c_float),
+                ("audio_mute", C.c_int32), ("bandpass_enable", C.c_int32)]
+
+
+class AmDemodBank:
+    """N AM demodulators (AMDemod::feed, envelope mode): int16 I/Q at the channelizer's output rate in, mono qint16 audio out."""
+
+    def __init__(self, cfgs, device: int = 0):
+        self.n_ch = len(cfgs)
+        arr = (AmCfg * self.n_ch)(*cfgs)
+        self._h = C.c_void_p()
+        _check(lib().sdrx_am_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_am_create")
+        self.cfgs = list(cfgs)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().sdrx_am_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = _del
+
+    def reset(self):
+        _check(lib().sdrx_am_reset(self._h), "sdrx_am_reset")
+
+    def feed(self, per_channel_iq):
+        bufs = [_i16(x) for x in per_channel_iq]
+        ptrs = (C.c_void_p * self.n_ch)(*[b.ctypes.data for b in bufs])
+        ns = (C.c_int64 * self.n_ch)(*[b.size // 2 for b in bufs])
+        _check(lib().sdrx_am_feed(self._h, ptrs, ns), "sdrx_am_feed")
+
+    def feed_dev(self, ptrs, counts):
+        """device pointers (4-byte aligned) and complex sample counts per channel; asynchronous on the handle's stream"""
+        p = (C.c_void_p * self.n_ch)(*ptrs)
+        n = (C.c_int64 * self.n_ch)(*counts)
+        _check(lib().sdrx_am_feed_dev(self._h, p, n), "sdrx_am_feed_dev")
+
+    def feed_bank(self, bank: "ChannelizerBank"):
+        """channel c takes what the bank's last feed produced for its channel c; ordered on the device, no host sync"""
+        _check(lib().sdrx_am_feed_bank(self._h, bank._h), "sdrx_am_feed_bank")
+
+    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
+        if cap is None:
+            cap = self.last_dev(ch)[1]
+        out = np.empty(max(cap, 1), np.int16)
+        n = lib().sdrx_am_read(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_am_read rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def last_dev(self, ch: int):
+        """(device pointer, count) of the last feed's audio of channel ch"""
+        p, n = C.c_void_p(), C.c_int64()
+        _check(lib().sdrx_am_last_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_am_last_dev")
+        return p.value or 0, n.value
+
+    def squelch_open(self, ch: int) -> bool:
+        rc = lib().sdrx_am_squelch_open(self._h, ch)
+        if rc < 0:
+            raise SdrxError(f"sdrx_am_squelch_open rc={rc}: {lib().sdrx_last_error().decode()}")
+        return bool(rc)
+
+    def levels(self, ch: int, reset: bool = False):
+        """(m_magsq, m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
+        m, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        _check(lib().sdrx_am_levels(self._h, ch, C.byref(m), C.byref(s), C.byref(p), C.byref(n), int(reset)), "sdrx_am_levels")
+        return m.value, s.value, p.value, n.value
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], the 151 folded Bandpass taps, NCO increment, squelch level)"""
+        nt, inc, lvl = C.c_int32(), C.c_int32(), C.c_float()
+        taps = np.zeros(16 * 128, np.float32)
+        bp = np.zeros(151, np.float32)
+        _check(lib().sdrx_am_get_design(self._h, ch, C.byref(nt), taps.ctypes.data, taps.size, bp.ctypes.data, C.byref(inc), C.byref(lvl)),
+               "sdrx_am_get_design")
+        return nt.value, taps[: 16 * nt.value].copy(), bp, inc.value, lvl.value
+
+    def sync(self):
+        _check(lib().sdrx_am_sync(self._h), "sdrx_am_sync")
+
+    def set_stream(self, hip_stream: int | None):
+        _check(lib().sdrx_am_set_stream(self._h, hip_stream), "sdrx_am_set_stream")
+
+    def get_stream(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sdrx_am_get_stream(self._h, C.byref(p)), "sdrx_am_get_stream")
+        return p.value or 0
+
+    def set_timing(self, on: bool):
+        _check(lib().sdrx_am_set_timing(self._h, int(on)), "sdrx_am_set_timing")
+
+    def get_timing(self, reset: bool = True):
+        ms, n = C.c_double(), C.c_int64()
+        _check(lib().sdrx_am_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_am_get_timing")
+        return ms.value, n.value
+
+    def last_launch(self) -> dict:
+        name = C.create_string_buffer(128)
+        g, b, l = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().sdrx_am_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
         return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
 
 

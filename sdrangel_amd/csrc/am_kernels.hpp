@@ -1,0 +1,331 @@
+// AM demodulator bank kernels: the tail of AMDemod::feed, AMDemod::processOneSample in envelope mode
+// (plugins/channelrx/demodam/amdemod.cpp:152-276).  The front (NCO, Interpolator::decimate) is the channel back-end's
+// (backend_kernels.hpp); these kernels start from its complex resampler output `ci` at the audio rate.
+//     magsq = re*re + im*im;  m_movingAverage(magsq);  level sums;  m_squelchDelayLine.write(magsq);  squelch counter
+//     open: demod = sqrt(readBack(rate / 20)); m_volumeAGC.feed(demod); demod = (demod - agc) / agc;
+//           [m_bandpass.filter(demod) / 301.0f];  attack;  (qint16)(demod * smootherstep(attack) * (rate / 24) * volume)
+// Audio is bit-identical to the strict-IEEE scalar reference build: every float expression keeps the reference's operand
+// order and the file is compiled with -ffp-contract=off.  am_scan.hpp has the cut of the recurrences; DESIGN.md 4.10 the
+// kernel table.  The only loops that are serial along time are am_psum_kernel's: loads, one double add per sample, stores.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "am_scan.hpp"
+
+namespace sdrx {
+
+struct AmChan {                         // device resident: config + carried state of one channel
+    // --- config
+    int rate;                           // m_audioSampleRate
+    int D, H;                           // rate / 20: readBack delay and opening count; rate / 10: counter cap and AGC length
+    float level;                        // m_squelchLevel = (Real) pow(10.0, squelch / 10.0)
+    float volume;
+    float att;                          // 0.05f * rate
+    float gain;                         // (float)(rate / 24)
+    int mute, bandpass;
+    int bp_off;                         // float offset into the Bandpass tap table (151 per channel)
+    // --- state
+    int count, sq_open;                 // m_squelchCount, m_squelchOpen
+    double total;                       // MovingAverageUtil::m_total
+    double agc_sum;                     // MovingAverage<double>::m_sum of m_volumeAGC
+    double magsq;                       // m_magsq
+    double magsq_sum, magsq_peak;
+    long long magsq_count;
+    // --- per feed
+    int n, n_act, n_fed;                // audio samples; open and unmuted ones; AGC feeds
+    double total_next, agc_sum_next;    // written by am_psum_kernel, committed by am_carry_kernel
+};
+
+struct AmBufs {                         // per channel device pointers (per feed capacity ensured by the host)
+    const float2* ci;                   // the front's output of this feed
+    const int* n_ptr;                   // its count (device side)
+    const float* mhist; float* mhist_next;       // last 16 magsq
+    const float* rhist; float* rhist_next;       // last D roots
+    const double* vhist; double* vhist_next;     // last H fed values
+    const float* dhist; float* dhist_next;       // last 300 open demods
+    float* msq; float* root;            // per sample
+    double* dterm; double* tot;         // moving-average terms and totals
+    int* cnt; int* aidx; int* fcnt;     // counter after the sample; index in the open sequence (-1: closed); fed count through it
+    double* vnew; double* uterm; double* agc;    // per fed sample: value, AGC term, AGC sum after it
+    float* dem;                         // per open sample: (r - g) / g
+    int16_t* audio;
+    double* blk_sum; float* blk_peak;   // per 256 samples
+};
+
+// ---- 1. per sample: magsq, its root, the moving-average term; per 256 samples the level partials
+__global__ __launch_bounds__(256)
+void am_level_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
+{
+    __shared__ double sums[256];
+    __shared__ float peaks[256];
+    const int c = blockIdx.y, tid = threadIdx.x;
+    const AmBufs b = bufs[c];
+    const int n = *b.n_ptr;
+    if (blockIdx.x == 0 && tid == 0) ch[c].n = n;
+    const long i = (long)blockIdx.x * 256 + tid;
+    if ((long)blockIdx.x * 256 >= n) return;
+    auto power = [&](long j) -> float {
+        const float2 v = b.ci[j];
+        const float re = v.x / 32768.0f, im = v.y / 32768.0f;      // SDR_RX_SCALEF
+        return re * re + im * im;
+    };
+    float m = 0.0f;
+    if (i < n) {
+        m = power(i);
+        const float old = i >= AM_MA ? power(i - AM_MA) : b.mhist[i];
+        b.msq[i] = m;
+        b.root[i] = sqrtf(m);                           // the correctly rounded expansion (IEEE sqrt is the build default)
+        b.dterm[i] = am_ma_term(m, old);
+    }
+    sums[tid] = (double)m; peaks[tid] = m;
+    __syncthreads();
+    for (int st = 128; st; st >>= 1) {
+        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmaxf(peaks[tid], peaks[tid + st]); }
+        __syncthreads();
+    }
+    if (tid == 0) { b.blk_sum[blockIdx.x] = sums[0]; b.blk_peak[blockIdx.x] = peaks[0]; }
+}
+
+// ---- 2. rounded prefix sum along time: acc += term.  which = 0: moving-average total; 1: AGC sum over the fed samples.
+// One wave per 16 channels, 64 terms per channel and trip.  The wave loads each channel's 64 terms with one coalesced
+// 512-byte instruction into LDS (row pitch 65 doubles: the 16 chain lanes fall into 16 different bank pairs), lane c then
+// walks row c -- LDS read, one double add, LDS write of its result -- and the rows go back out coalesced.  (A lane reading
+// its own channel's terms straight from memory touches 64 different lines per instruction: measured 8.4 ms per launch for
+// 256 channels x 48 000 terms)
+constexpr int AM_PS_CH = 16, AM_PS_T = 64;
+__global__ __launch_bounds__(64)
+void am_psum_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs, int n_ch, int which)
+{
+    __shared__ double tile[AM_PS_CH][AM_PS_T + 1];
+    __shared__ const double* st[AM_PS_CH];
+    __shared__ double* so[AM_PS_CH];
+    __shared__ int sn[AM_PS_CH];
+    const int lane = threadIdx.x, c = blockIdx.x * AM_PS_CH + lane;
+    const bool chain = lane < AM_PS_CH && c < n_ch;
+    double acc = 0.0;
+    int n_mine = 0;
+    if (lane < AM_PS_CH) {
+        const int cc = min(c, n_ch - 1);                    // rows past the last channel: its pointers, no terms
+        const AmChan& s = ch[cc];
+        const AmBufs& b = bufs[cc];
+        st[lane] = which ? b.uterm : b.dterm;
+        so[lane] = which ? b.agc : b.tot;
+        if (chain) { n_mine = which ? s.n_fed : s.n; acc = which ? s.agc_sum : s.total; }
+        sn[lane] = n_mine;
+    }
+    __syncthreads();
+    int n_max = 0;
+    for (int q = 0; q < AM_PS_CH; q++) n_max = max(n_max, sn[q]);
+    for (int i = 0; i < n_max; i += AM_PS_T) {
+        // unconditional loads with the index clamped into the channel's terms, so that all sixteen are in flight together;
+        // what lies past a channel's end is never added and never stored
+        double v[AM_PS_CH];
+#pragma unroll
+        for (int q = 0; q < AM_PS_CH; q++) v[q] = st[q][min(i + lane, max(sn[q] - 1, 0))];
+#pragma unroll
+        for (int q = 0; q < AM_PS_CH; q++) tile[q][lane] = v[q];
+        __syncthreads();
+        if (chain) {
+            const int m = min(AM_PS_T, n_mine - i);
+            if (m == AM_PS_T) {
+#pragma unroll 16
+                for (int k = 0; k < AM_PS_T; k++) { acc += tile[lane][k]; tile[lane][k] = acc; }
+            } else {
+                for (int k = 0; k < m; k++) { acc += tile[lane][k]; tile[lane][k] = acc; }
+            }
+        }
+        __syncthreads();
+        for (int q = 0; q < AM_PS_CH; q++)
+            if (i + lane < sn[q]) so[q][i + lane] = tile[q][lane];
+        __syncthreads();
+    }
+    if (chain) { if (which) ch[c].agc_sum_next = acc; else ch[c].total_next = acc; }
+}
+
+__device__ __forceinline__ WfmClamp am_shfl_up(WfmClamp m, int o)
+{
+    WfmClamp r; r.a = __shfl_up(m.a, o, 64); r.lo = __shfl_up(m.lo, o, 64); r.hi = __shfl_up(m.hi, o, 64);
+    return r;
+}
+
+// ---- 3. one workgroup per channel, 1024 samples per trip: the squelch counter as a scan of clamp maps, open and fed
+// flags, their prefix counts (the compaction indices), the fed values, then the AGC terms; level accumulators
+__global__ __launch_bounds__(256)
+void am_gate_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
+{
+    __shared__ WfmClamp wmap[4];
+    __shared__ int wact[4], wfed[4];
+    __shared__ double sums[256];
+    __shared__ float peaks[256];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    AmChan& s = ch[c];
+    const AmBufs b = bufs[c];
+    const int n = s.n, cap = s.H, D = s.D, rate = s.rate;
+    const float level = s.level;
+    const bool mute = s.mute != 0;
+    int carry = s.count, nact = 0, nfed = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i0 = base + tid * 4;
+        bool up[4];
+        WfmClamp m = wfm_identity(cap);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            up[k] = false;
+            if (i0 + k < n) { up[k] = am_up(b.tot[i0 + k], level); m = wfm_compose(m, wfm_step(up[k], cap)); }
+        }
+        WfmClamp incl = m;
+        for (int o = 1; o < 64; o *= 2) {
+            const WfmClamp t = am_shfl_up(incl, o);
+            if (lane >= o) incl = wfm_compose(t, incl);
+        }
+        if (lane == 63) wmap[w] = incl;
+        __syncthreads();
+        WfmClamp pre = wfm_identity(cap);
+        for (int q = 0; q < w; q++) pre = wfm_compose(pre, wmap[q]);
+        WfmClamp ex = am_shfl_up(incl, 1);
+        if (lane == 0) ex = wfm_identity(cap);
+        int st = wfm_apply(wfm_compose(pre, ex), carry);
+        int stv[4]; bool act[4], fed[4]; float rr[4];
+        int a_loc = 0, f_loc = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            act[k] = fed[k] = false; stv[k] = st; rr[k] = 0.0f;
+            if (i0 + k < n) {
+                st = wfm_apply(wfm_step(up[k], cap), st);
+                stv[k] = st;
+                const bool open = am_open(st, rate);
+                act[k] = open && !mute;
+                rr[k] = am_stream_at(b.rhist, D, b.root, (long)(i0 + k) - D);
+                fed[k] = am_fed(open, mute, rr[k]);
+                a_loc += act[k]; f_loc += fed[k];
+            }
+        }
+        int a_inc = a_loc, f_inc = f_loc;
+        for (int o = 1; o < 64; o *= 2) {
+            const int ta = __shfl_up(a_inc, o, 64), tf = __shfl_up(f_inc, o, 64);
+            if (lane >= o) { a_inc += ta; f_inc += tf; }
+        }
+        if (lane == 63) { wact[w] = a_inc; wfed[w] = f_inc; }
+        __syncthreads();
+        int a_ex = nact + a_inc - a_loc, f_ex = nfed + f_inc - f_loc;
+        for (int q = 0; q < w; q++) { a_ex += wact[q]; f_ex += wfed[q]; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (i0 + k < n) {
+                b.cnt[i0 + k] = stv[k];
+                b.aidx[i0 + k] = act[k] ? a_ex++ : -1;
+                if (fed[k]) b.vnew[f_ex++] = (double)rr[k];
+                b.fcnt[i0 + k] = f_ex;
+            }
+        }
+        WfmClamp all = wmap[0];
+        for (int q = 1; q < 4; q++) all = wfm_compose(all, wmap[q]);
+        carry = wfm_apply(all, carry);
+        for (int q = 0; q < 4; q++) { nact += wact[q]; nfed += wfed[q]; }
+        __syncthreads();                                    // wmap / wact / wfed are rewritten by the next trip
+    }
+    // level accumulators: the 256-sample partials of am_level_kernel, in a fixed order
+    const int nblk = (n + 255) / 256;
+    double ps = 0.0; float pk = 0.0f;
+    for (int j = tid; j < nblk; j += 256) { ps += b.blk_sum[j]; pk = fmaxf(pk, b.blk_peak[j]); }
+    sums[tid] = ps; peaks[tid] = pk;
+    __syncthreads();                                        // also: every vnew of this feed is written
+    for (int st = 128; st; st >>= 1) {
+        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmaxf(peaks[tid], peaks[tid + st]); }
+        __syncthreads();
+    }
+    const int H = s.H;
+    for (int j = tid; j < nfed; j += 256) b.uterm[j] = am_agc_term(b.vnew[j], am_stream_at(b.vhist, H, (const double*)b.vnew, (long)j - H));
+    if (tid == 0) {
+        s.n_act = nact; s.n_fed = nfed;
+        if (n > 0) {
+            s.count = carry;
+            s.sq_open = am_open(carry, rate) ? 1 : 0;
+            s.magsq = b.tot[n - 1] / (double)AM_MA;
+            s.magsq_sum += sums[0];
+            if ((double)peaks[0] > s.magsq_peak) s.magsq_peak = (double)peaks[0];
+            s.magsq_count += n;
+        }
+    }
+}
+
+// ---- 4. per open sample: the AGC value at its fed count and the normalised envelope, into the compacted sequence
+__global__ __launch_bounds__(256)
+void am_demod_kernel(const AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
+{
+    const int c = blockIdx.y;
+    const AmChan& s = ch[c];
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= s.n) return;
+    const AmBufs& b = bufs[c];
+    const int a = b.aidx[i];
+    if (a < 0) return;
+    const float r = am_stream_at(b.rhist, s.D, (const float*)b.root, i - s.D);   // sqrt(readBack(rate / 20)) after the write
+    const int f = b.fcnt[i];
+    const double sum = f > 0 ? b.agc[f - 1] : s.agc_sum;
+    const float avg = (float)(sum / (double)s.H);                                // SimpleAGC::getValue, m_clip = 0
+    const float g = avg > 0.0f ? avg : 0.0f;
+    b.dem[a] = (r - g) / g;
+}
+
+__device__ __forceinline__ int am_to_q16(float v)
+{
+    // (qint16) of a float as x86-64 does it: cvttss2si (0x80000000 when out of range or NaN), then the low 16 bits
+    const int i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u;
+    return (int)(short)i;
+}
+__device__ __forceinline__ float am_smootherstep(float x)                   // util/stepfunctions.h:23-36
+{
+    if (x == 1.0f) return 1.0f; else if (x == 0.0f) return 0.0f;
+    const double x3 = x * x * x, x4 = x * x3, x5 = x * x4;
+    return (float)(6.0 * x5 - 15.0 * x4 + 10.0 * x3);
+}
+
+// ---- 5. per sample: the Bandpass over the compacted sequence (one lane per open sample, taps from LDS), attack,
+// conversion; closed or muted samples are 0
+__global__ __launch_bounds__(256)
+void am_out_kernel(const AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs, const float* __restrict__ bp_taps)
+{
+    __shared__ float taps[AM_BP_H + 1];
+    const int c = blockIdx.y;
+    const AmChan& s = ch[c];
+    if ((long)blockIdx.x * 256 >= s.n) return;
+    if (s.bandpass) {
+        for (int k = threadIdx.x; k <= AM_BP_H; k += 256) taps[k] = bp_taps[s.bp_off + k];
+        __syncthreads();
+    }
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= s.n) return;
+    const AmBufs& b = bufs[c];
+    const int a = b.aidx[i];
+    int q = 0;
+    if (a >= 0) {
+        float demod = b.dem[a];
+        if (s.bandpass) {
+            const float* __restrict__ hist = b.dhist;
+            const float* __restrict__ cur = b.dem;
+            demod = am_bandpass(taps, [&](int k) { return am_stream_at(hist, AM_BP_HIST, cur, (long)a - k); });
+            demod /= 301.0f;
+        }
+        const float attack = ((float)b.cnt[i] - s.att) / s.att;
+        q = am_to_q16(demod * am_smootherstep(attack) * s.gain * s.volume);
+    }
+    b.audio[i] = (int16_t)q;
+}
+
+// ---- 6. carry: the histories of the next feed (double-buffered: this feed's are still being read), the two sums
+__global__ __launch_bounds__(256)
+void am_carry_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
+{
+    const int c = blockIdx.x, tid = threadIdx.x;
+    AmChan& s = ch[c];
+    const AmBufs b = bufs[c];
+    const int n = s.n;
+    if (tid < AM_MA) b.mhist_next[tid] = am_hist_next(b.mhist, AM_MA, (const float*)b.msq, n, tid);
+    for (int i = tid; i < s.D; i += 256) b.rhist_next[i] = am_hist_next(b.rhist, s.D, (const float*)b.root, n, i);
+    for (int i = tid; i < s.H; i += 256) b.vhist_next[i] = am_hist_next(b.vhist, s.H, (const double*)b.vnew, s.n_fed, i);
+    for (int i = tid; i < AM_BP_HIST; i += 256) b.dhist_next[i] = am_hist_next(b.dhist, AM_BP_HIST, (const float*)b.dem, s.n_act, i);
+    if (tid == 0) { s.total = s.total_next; s.agc_sum = s.agc_sum_next; }
+}
+
+} // namespace sdrx

@@ -1,0 +1,16 @@
+// What another handle of libsdrx.so needs to run behind a channel back-end it owns (sdrx_am.hip): the device-side view of a
+// channel's last outputs without a host round trip, and the stream the back-end launches on.
+#pragma once
+#include "sdrx_common.hpp"
+
+namespace sdrx {
+
+struct BackendView {
+    const void* out;        // float2 (no discriminator) or float samples of the last feed; may move when a feed grows the buffers
+    const int* n_out;       // their count, written on the device by the feed's last kernel
+};
+int backend_view(sdrx_backend_t* b, int32_t ch, BackendView* v);
+// hip_stream == nullptr: back to the back-end's own stream.  Waits for the work queued so far.
+int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream);
+
+} // namespace sdrx

@@ -6,6 +6,8 @@
 #include "sdrx_common.hpp"
 #include "backend_kernels.hpp"
 #include "backend_design.hpp"
+#include "backend_view.hpp"
+#include <cstddef>
 #include <vector>
 #include <cmath>
 #include <cstring>
@@ -395,6 +397,19 @@ int64_t sdrx_backend_read(sdrx_backend_t* b, int32_t c, float* out, int64_t cap_
     return n_floats;
 }
 
+int sdrx_backend_last_dev(sdrx_backend_t* b, int32_t c, const float** d_out, int64_t* n_floats)
+{
+    if (!b || c < 0 || c >= b->n_ch || !d_out || !n_floats) { set_error("sdrx_backend_last_dev: bad argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->device));
+    BeChan s;
+    SDRX_HIP(hipMemcpyAsync(&s, b->d_chan + c, sizeof s, hipMemcpyDeviceToHost, b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    const bool real = s.discri != 0;
+    *d_out = static_cast<const float*>(real ? b->ch[(size_t)c].real_out.p : b->ch[(size_t)c].cplx_out.p);
+    *n_floats = (int64_t)s.n_out * (real ? 1 : 2);
+    return SDRX_OK;
+}
+
 int sdrx_backend_get_design(sdrx_backend_t* b, int32_t c, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
                             float* filter_iq, int32_t* nco_inc)
 {
@@ -416,3 +431,25 @@ int sdrx_backend_sync(sdrx_backend_t* b)
 }
 
 } // extern "C"
+
+namespace sdrx {
+
+int backend_view(sdrx_backend_t* b, int32_t c, BackendView* v)
+{
+    if (!b || c < 0 || c >= b->n_ch || !v) { set_error("backend_view: bad argument"); return SDRX_EINVAL; }
+    const ChanHost& h = b->ch[(size_t)c];
+    v->out = h.cfg.discri ? h.real_out.p : h.cplx_out.p;
+    v->n_out = reinterpret_cast<const int*>(reinterpret_cast<const char*>(b->d_chan + c) + offsetof(BeChan, n_out));
+    return SDRX_OK;
+}
+
+int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream)
+{
+    if (!b) return SDRX_EINVAL;
+    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipStreamSynchronize(b->stream));
+    b->stream = hip_stream ? hip_stream : b->own_stream;
+    return SDRX_OK;
+}
+
+} // namespace sdrx
