@@ -48,6 +48,24 @@ std::string lower_job(const TkMJob& j, int PI, int PO, TkLJob& r)
     return {};
 }
 
+// the root arms: which kinds there are, and that they sit where the kernel's root fill and root history copy will look for them
+std::string lower_root(const TkSubtree& st, TkLRoot& r)
+{
+    const int P = mx_pitch(0) / 4;                          // the tables count dwords
+    r.base = 4 * st.rootE_I;
+    r.kinds = (st.rootO_I >= 0 ? MX_ROOT_O : 0) | (st.rootA_I >= 0 ? MX_ROOT_A : 0);
+    // the kernel takes every array length from mx_pitch(), a constant of the level, not from the tables
+    if (st.root_len != P) return "lower: root arrays of another length";
+    if (!r.kinds) return "lower: root without odd arms";       // a root is an inner node: alloc_arms gives it O, A or both
+    if (st.rootE_I < 0 || st.rootE_I != st.root_off || st.rootE_Q != st.rootE_I + P) return "lower: root even arms not at the window's start";
+    if ((st.rootO_I >= 0) != (st.rootO_Q >= 0) || (st.rootA_I >= 0) != (st.rootA_Q >= 0)) return "lower: half a root odd arm";
+    int at = st.rootE_I + 2 * P;
+    if (r.kinds & MX_ROOT_O) { if (st.rootO_I != at || st.rootO_Q != at + P) return "lower: root odd arms not at 2 pitches"; at += 2 * P; }
+    if (r.kinds & MX_ROOT_A) { if (st.rootA_I != at || st.rootA_Q != at + P) return "lower: root alternating arms not behind the others"; }
+    if (st.root_arr_cnt != mx_root_arrays(r.kinds)) return "lower: unexpected root array count";
+    return {};
+}
+
 // one subtree's levels into out.jobs / out.src (their index range, sorted by class inside each level)
 std::string lower_subtree(const BankPlan& plan, const TkSubtree& st, LoweredBank& out)
 {
@@ -85,10 +103,14 @@ std::string lower_bank(const BankPlan& plan, LoweredBank& out)
     // tree_kernel<true> for its pass: the first such layout is reported, the bank is planned all the same
     std::string first_err;
     std::vector<uint8_t> sub_mx(plan.subtrees.size(), 0);
+    out.roots.assign(plan.subtrees.size(), TkLRoot{ 0, -1 });
     for (size_t s = 0; s < plan.subtrees.size(); s++) {
         const TkSubtree& st = plan.subtrees[s];
         if (!plan.mfma || !subtree_all_mx(st)) continue;
-        const std::string err = lower_subtree(plan, st, out);
+        TkLRoot root;
+        std::string err = lower_root(st, root);
+        if (err.empty()) err = lower_subtree(plan, st, out);
+        if (err.empty()) out.roots[s] = root;
         if (err.empty()) sub_mx[s] = 1;
         else if (first_err.empty()) first_err = err;
     }

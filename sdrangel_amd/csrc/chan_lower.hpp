@@ -47,6 +47,17 @@ struct TkLJob {
 };
 static_assert(sizeof(TkLJob) == 32, "one s_load_dwordx8 per job");
 
+// A subtree's root arms.  alloc_arms() lays them out like a child's: E_I E_Q [O_I O_Q] [A_I A_Q], back to back, each
+// mx_pitch(0) bytes.  So the root fill stores at one per-lane address plus immediates, and the kernel pins two numbers in scalar
+// registers where the six arm offsets, their count and the window of TkSubtree took nine.
+enum : int { MX_ROOT_O = 1, MX_ROOT_A = 2 };
+struct TkLRoot {
+    int base;           // byte address of the window of E_I, the first root array (TkSubtree::root_off)
+    int kinds;          // MX_ROOT_O: plain odd arms at 2, 3 pitches; MX_ROOT_A: alternating odd arms after them (at 2, 3 without O);
+                        // at least one of the two: a root is an inner node
+};
+constexpr int mx_root_arrays(int kinds) { return 2 + 2 * (kinds & 1) + (kinds & 2); }
+
 inline int mx_class(int meta) { return meta & 15; }
 inline int mx_flags(int meta, int k) { return (meta >> (4 + 4 * k)) & 15; }
 
@@ -54,6 +65,7 @@ struct LoweredBank {
     std::vector<TkLJob> jobs;        // parallel to BankPlan::mjobs: a level's jobs keep their index range (TkLevel::mjob_base, n_mjobs),
                                      // sorted by class inside it
     std::vector<int> src;            // jobs[i] was lowered from mjobs[src[i]]
+    std::vector<TkLRoot> roots;      // parallel to BankPlan::subtrees (kinds -1: a subtree the lowering did not take)
     std::vector<uint8_t> pass_mx;    // per pass: 1 = every subtree of the pass runs on tree_mx_kernel
 };
 

@@ -43,9 +43,10 @@ struct Group {
     BankPlan plan;
     LoweredBank low;              // the plan's matrix-core jobs for tree_mx_kernel, and which passes run it
     std::vector<StreamBuf> bufs;  // one per plan stream
-    void* d_static = nullptr;     // subtrees | nodes | arrays | mjobs | lowered jobs
+    void* d_static = nullptr;     // subtrees | nodes | arrays | mjobs | lowered jobs | lowered roots
     TkSubtree* d_subtrees = nullptr; TkNode* d_nodes = nullptr; TkArray* d_arrays = nullptr; TkMJob* d_mjobs = nullptr;
     TkLJob* d_ljobs = nullptr;
+    TkLRoot* d_lroots = nullptr;
 };
 
 } // namespace
@@ -92,19 +93,22 @@ static int upload_group(sdrx_chan_bank* b, Group* g)
     }
     const size_t b0 = p.subtrees.size() * sizeof(TkSubtree), b1 = p.nodes.size() * sizeof(TkNode), b2 = p.arrays.size() * sizeof(TkArray);
     const size_t b3 = p.mjobs.size() * sizeof(TkMJob), b4 = g->low.jobs.size() * sizeof(TkLJob);
+    const size_t b5 = g->low.roots.size() * sizeof(TkLRoot);
     if (b0 + b1 + b2 == 0) return SDRX_OK;
-    SDRX_HIP(hipMalloc(&g->d_static, b0 + b1 + b2 + b3 + b4 + 64));
+    SDRX_HIP(hipMalloc(&g->d_static, b0 + b1 + b2 + b3 + b4 + b5 + 64));
     char* d = static_cast<char*>(g->d_static);
     g->d_subtrees = reinterpret_cast<TkSubtree*>(d);
     g->d_nodes = reinterpret_cast<TkNode*>(d + b0);
     g->d_arrays = reinterpret_cast<TkArray*>(d + b0 + b1);
     g->d_mjobs = reinterpret_cast<TkMJob*>(d + b0 + b1 + b2);
     g->d_ljobs = reinterpret_cast<TkLJob*>(d + b0 + b1 + b2 + b3);
+    g->d_lroots = reinterpret_cast<TkLRoot*>(d + b0 + b1 + b2 + b3 + b4);
     if (b0) SDRX_HIP(hipMemcpy(g->d_subtrees, p.subtrees.data(), b0, hipMemcpyHostToDevice));
     if (b1) SDRX_HIP(hipMemcpy(g->d_nodes, p.nodes.data(), b1, hipMemcpyHostToDevice));
     if (b2) SDRX_HIP(hipMemcpy(g->d_arrays, p.arrays.data(), b2, hipMemcpyHostToDevice));
     if (b3) SDRX_HIP(hipMemcpy(g->d_mjobs, p.mjobs.data(), b3, hipMemcpyHostToDevice));
     if (b4) SDRX_HIP(hipMemcpy(g->d_ljobs, g->low.jobs.data(), b4, hipMemcpyHostToDevice));
+    if (b5) SDRX_HIP(hipMemcpy(g->d_lroots, g->low.roots.data(), b5, hipMemcpyHostToDevice));
     return SDRX_OK;
 }
 
@@ -285,7 +289,7 @@ static int feed_group(sdrx_chan_bank* b, Group* g, const uint32_t* d_in, int64_t
         // have dot2 levels and keep tree_kernel<true>.  Both are the matrix-core engine: last_launch() names it tree_kernel<mfma>.
         if (g->low.pass_mx[p])
             hipLaunchKernelGGL(tree_mx_kernel, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->stream,
-                               g->d_subtrees, g->d_arrays, d_streams + s0, d_sinks, g->d_ljobs);
+                               g->d_subtrees, g->d_arrays, d_streams + s0, d_sinks, g->d_ljobs, g->d_lroots);
         else if (plan.mfma)
             hipLaunchKernelGGL(tree_kernel<true>, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->stream,
                                g->d_subtrees, g->d_nodes, g->d_arrays, d_streams + s0, d_sinks, g->d_mjobs);

@@ -4,6 +4,9 @@
 // one 8-dword descriptor per job, every LDS address a base plus a compile-time multiple of the level's pitch, so the lane adds its
 // share once per base and the ds_read / ds_write immediate offsets do the rest.  The level index is a template parameter (it
 // fixes the pitches), and so is the job's epilogue class: a wave's job pair runs a body with no branch it does not need.
+// What is the same for every lane of a chunk is decided on the scalar side or at compile time: the array lengths of the history
+// walks are constants of the level, the root arms hang off one lowered base (TkLRoot), and a job whose 256 outputs lie inside the
+// feed's range stores them without a per-lane compare.
 // Bit for bit what tree_kernel<true> computes: the biased odd arms and their zero history, the wrap-negated alternating copies,
 // the int16 stores, the sink ranges of ragged feeds are all the same code.
 #pragma once
@@ -19,9 +22,20 @@ __device__ __forceinline__ int mx_div_pow2_trunc(int v, int n)
     return (v + ((v >> 31) & ((1 << n) - 1))) >> n;     // s.m_real /= (1 << n) (downchannelizer.cpp:80)
 }
 
+// q rows of the arrays `REL` levels below the root, in dwords.  The length is a constant of the level here (chan_lower.cpp refuses
+// a pass whose plan says otherwise), and the row index q is an array index inside one pass: below lds_dwords / LEN, a few hundred
+// at most with 160 KB of LDS, far inside the 24 bits __mul24 takes.  One full-rate 24-bit multiply (or a multiply-add with the
+// base) in place of the quarter-rate 32-bit multiplies that a length read from the level record costs.
+template<int REL> __device__ __forceinline__ int mx_rows(int q)
+{
+    constexpr int LEN = mx_pitch(REL) / 4;
+    static_assert(LEN > 0 && LEN < (1 << 16) && (160 * 1024 / 4) / LEN < (1 << 16), "24-bit multiply: length and row index both fit 16 bits");
+    return __mul24(q, LEN);
+}
+
 __global__ __launch_bounds__(TK_THREADS, 4)
 void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __restrict__ arrays, const TkStream* __restrict__ streams,
-                    const TkSink* __restrict__ sinks, const TkLJob* __restrict__ ljobs)
+                    const TkSink* __restrict__ sinks, const TkLJob* __restrict__ ljobs, const TkLRoot* __restrict__ lroots)
 {
     constexpr int C = TK_CHUNK, NT = TK_THREADS, LPT = C / 4 / NT;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -47,10 +61,8 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
     taps.init(lane);
     const uint32_t root_xm = st.root_xm;
     // pinned in registers, as in tree_kernel.hpp (the compiler re-loads them from the descriptor inside the loops otherwise)
-    int n_levels = st.n_levels, store_base = st.store_base, root_off = st.root_off, root_len = st.root_len;
-    asm volatile("" : "+s"(n_levels), "+s"(store_base), "+s"(root_off), "+s"(root_len));
-    int rE_I = st.rootE_I, rE_Q = st.rootE_Q, rO_I = st.rootO_I, rO_Q = st.rootO_Q, rA_I = st.rootA_I, rA_Q = st.rootA_Q, root_cnt16 = st.root_arr_cnt * 16;
-    asm volatile("" : "+s"(rE_I), "+s"(rE_Q), "+s"(rO_I), "+s"(rO_Q), "+s"(rA_I), "+s"(rA_Q), "+s"(root_cnt16));
+    int n_levels = st.n_levels, store_base = st.store_base, root_base = lroots[sp.subtree].base, root_kinds = lroots[sp.subtree].kinds;
+    asm volatile("" : "+s"(n_levels), "+s"(store_base), "+s"(root_base), "+s"(root_kinds));
 
     uint4 pre[LPT];
     auto fetch = [&](long chunk, const int tid) {
@@ -100,20 +112,41 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
         // the history walks and the boundary fetch out of the loop, and spill them
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
-        // ---- stream samples -> root arms
+        // ---- stream samples -> root arms (TkLRoot: E_I E_Q [O_I O_Q] [A_I A_Q], one pitch apart): one address per lane and
+        // chunk, every store an immediate offset from it; one body per set of kinds.  A root is an inner node, so it has at least
+        // one odd kind (chan_lower.cpp refuses a root with none): E+O, E+A or E+O+A.
+        {
+            char* p = ldsw + root_base + 4 * (HIST / 2 + tid);
+            auto fill = [&](auto Kc) {
+                constexpr int K = decltype(Kc)::value, P0 = mx_pitch(0), AT = (K & MX_ROOT_O) ? 4 * P0 : 2 * P0;
+                static_assert(AT + P0 + 4 * (LPT - 1) * NT < 65536, "ds_write immediate offset");
 #pragma unroll
-        for (int j = 0; j < LPT; j++) {
-            const int q = HIST / 2 + j * NT + tid;
-            const uint4 v = pre[j];
-            const uint32_t oI = __builtin_amdgcn_perm(v.w, v.y, 0x05040100u);
-            const uint32_t oQ = __builtin_amdgcn_perm(v.w, v.y, 0x07060302u);
-            lds[rE_I + q] = __builtin_amdgcn_perm(v.z, v.x, 0x05040100u);
-            lds[rE_Q + q] = __builtin_amdgcn_perm(v.z, v.x, 0x07060302u);
-            if (rO_I >= 0) { lds[rO_I + q] = oI ^ root_xm; lds[rO_Q + q] = oQ ^ root_xm; }
-            if (rA_I >= 0) { lds[rA_I + q] = pmul(oI, ALT) ^ root_xm; lds[rA_Q + q] = pmul(oQ, ALT) ^ root_xm; }
+                for (int j = 0; j < LPT; j++) {
+                    const uint4 v = pre[j];
+                    const uint32_t oI = __builtin_amdgcn_perm(v.w, v.y, 0x05040100u);
+                    const uint32_t oQ = __builtin_amdgcn_perm(v.w, v.y, 0x07060302u);
+                    char* pj = p + 4 * j * NT;
+                    *reinterpret_cast<uint32_t*>(pj) = __builtin_amdgcn_perm(v.z, v.x, 0x05040100u);
+                    *reinterpret_cast<uint32_t*>(pj + P0) = __builtin_amdgcn_perm(v.z, v.x, 0x07060302u);
+                    if constexpr (K & MX_ROOT_O) {
+                        *reinterpret_cast<uint32_t*>(pj + 2 * P0) = oI ^ root_xm; *reinterpret_cast<uint32_t*>(pj + 3 * P0) = oQ ^ root_xm;
+                    }
+                    if constexpr (K & MX_ROOT_A) {
+                        *reinterpret_cast<uint32_t*>(pj + AT) = pmul(oI, ALT) ^ root_xm; *reinterpret_cast<uint32_t*>(pj + AT + P0) = pmul(oQ, ALT) ^ root_xm;
+                    }
+                }
+            };
+            if (root_kinds == (MX_ROOT_O | MX_ROOT_A)) fill(std::integral_constant<int, MX_ROOT_O | MX_ROOT_A>{});
+            else if (root_kinds == MX_ROOT_O) fill(std::integral_constant<int, MX_ROOT_O>{});
+            else fill(std::integral_constant<int, MX_ROOT_A>{});
         }
-        for (int i = tid; i < root_cnt16; i += NT)
-            lds[root_off + (i >> 4) * root_len + (i & 15)] = lds[store_base + i];
+        {
+            const uint32_t* slots = lds + store_base;
+            uint32_t* win = reinterpret_cast<uint32_t*>(ldsw + root_base);
+            const int root_cnt16 = 16 * mx_root_arrays(root_kinds);
+            for (int i = tid; i < root_cnt16; i += NT)
+                win[mx_rows<0>(i >> 4) + (i & 15)] = slots[i];
+        }
         if (chunk < last) fetch(chunk + 1, tid);
         __syncthreads();
 
@@ -127,18 +160,17 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
             constexpr int L = decltype(Lc)::value;
             constexpr int PI = mx_pitch(L), PO = mx_pitch(L + 1);
             const s16i rec = *(const s16i __attribute__((address_space(4)))*)reinterpret_cast<const int*>(&st.lv[L + lv0]);
-            const int nout = rec[3], arr_base = rec[4], arr_cnt = rec[5], in_len = rec[7], mjob_base = rec[9], n_mjobs = rec[10];
+            const int nout = rec[3], arr_base = rec[4], arr_cnt = rec[5], mjob_base = rec[9], n_mjobs = rec[10];
             const uint32_t xm = (uint32_t)rec[11];
-            const int prev_off = rec[12], prev_arr_cnt = rec[13], arr_off = rec[14], arr_len = rec[15];
-            {   // history walk (tree_kernel.hpp)
-                const int n_restore = arr_cnt * 16, n_all = n_restore + prev_arr_cnt * 16;
+            const int prev_off = rec[12], prev_arr_cnt = rec[13], arr_off = rec[14];
+            {   // history walk (tree_kernel.hpp), its two ranges as two loops: restore the history in front of the arrays this level
+                // produces, save the tails of the arrays it reads.  The lengths are PO / 4 and PI / 4 (mx_rows).
+                const int n_restore = arr_cnt * 16, n_save = prev_arr_cnt * 16;
                 const int slot0 = store_base + 16 * arr_base;
-                for (int i = tid; i < n_all; i += NT) {
-                    const int k = i - n_restore;
-                    const int src = k < 0 ? slot0 + i : prev_off + (k >> 4) * in_len + in_len - 16 + (k & 15);
-                    const int dst = k < 0 ? arr_off + (i >> 4) * arr_len + (i & 15) : slot0 - prev_arr_cnt * 16 + k;
-                    lds[dst] = lds[src];
-                }
+                for (int i = tid; i < n_restore; i += NT)
+                    lds[arr_off + mx_rows<L + 1>(i >> 4) + (i & 15)] = lds[slot0 + i];
+                for (int k = tid; k < n_save; k += NT)
+                    lds[slot0 - n_save + k] = lds[prev_off + PI / 4 - 16 + mx_rows<L>(k >> 4) + (k & 15)];
             }
             struct JobIn { v4i bI0, bI1, bQ0, bQ1; uint2 cI01, cQ01; uint32_t cI2, cQ2; };
             // the job's operands: two bases, everything else immediate offsets (the centre taps of a lower/upper parent come from
@@ -161,7 +193,7 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
             auto st32 = [&](char* p, int off, uint32_t v) { *reinterpret_cast<uint32_t*>(p + off) = v; };
             // a child's outputs: arms (flags f, see TkMOut) at its base, then its sink list (MX_SINK only)
             auto child = [&](auto Sk, const uint32_t eI, const uint32_t oI, const uint32_t eQ, const uint32_t oQ, const int base, const int f,
-                             const int sink, const long abs0) {
+                             const int sink, const long job0) {
                 constexpr bool SINK = decltype(Sk)::value;
                 if (f) {
                     char* p = ldsw + base + pl;
@@ -189,14 +221,27 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
                                 w[2] = __builtin_amdgcn_perm(eQ, eI, 0x07060302u); w[3] = __builtin_amdgcn_perm(oQ, oI, 0x07060302u);
                             }
                             typedef uint32_t __attribute__((address_space(1))) gu32;
-                            gu32* dst = (gu32*)(reinterpret_cast<uint32_t*>(ptr0) + abs0);
-                            const long rel = abs0 - lo, span = hi - lo;
-                            if (rel >= 0 && rel + 4 <= span) {
-                                typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));
-                                *(u4a __attribute__((address_space(1)))*)dst = u4a{ w[0], w[1], w[2], w[3] };
-                            } else if (rel > -4 && rel < span) {
+                            typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));
+                            // The job's 256 outputs [job0, job0 + 256) against [lo, hi), on the scalar side: every job but those of
+                            // a feed's first and last chunk lies wholly inside, and stores 16 bytes per lane at one scalar base
+                            // plus the lane's 32-bit offset, no compare.  (The sign of both differences in one 32-bit register:
+                            // there is no scalar 64-bit signed compare.)
+                            int inside = (int)((uint64_t)((job0 - lo) | (hi - 256 - job0)) >> 32);
+                            asm("" : "+s"(inside));
+                            if (inside >= 0) {
+                                typedef char __attribute__((address_space(1))) gchar;
+                                gchar* row = (gchar*)(reinterpret_cast<uint32_t*>(ptr0) + job0);
+                                *(u4a __attribute__((address_space(1)))*)(row + (uint32_t)(4 * pl)) = u4a{ w[0], w[1], w[2], w[3] };
+                            } else {
+                                const long abs0 = job0 + pl;
+                                gu32* dst = (gu32*)(reinterpret_cast<uint32_t*>(ptr0) + abs0);
+                                const long rel = abs0 - lo, span = hi - lo;
+                                if (rel >= 0 && rel + 4 <= span) {
+                                    *(u4a __attribute__((address_space(1)))*)dst = u4a{ w[0], w[1], w[2], w[3] };
+                                } else if (rel > -4 && rel < span) {
 #pragma unroll
-                                for (int i = 0; i < 4; i++) if (rel + i >= 0 && rel + i < span) dst[i] = w[i];
+                                    for (int i = 0; i < 4; i++) if (rel + i >= 0 && rel + i < span) dst[i] = w[i];
+                                }
                             }
                             si = sr[7];
                         }
@@ -206,9 +251,14 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
             // the epilogue of class CLS (chan_lower.hpp)
             auto finish = [&](auto Cc, const JobIn& r, const v4i SI, const v4i SQ, const s8i d) {
                 constexpr int CLS = decltype(Cc)::value;
+                // the low 16 bits of (a >> 11) and of (b >> 11) in one dword: the second shift is an SDWA write to WORD_1 that preserves
+                // the rest (dst_unused:UNUSED_PRESERVE).  On gfx950 a VALU consumer of an SDWA dst_sel write needs one wait state, and the
+                // compiler's hazard recognizer does not see inside inline asm: the s_nop 0 in the string carries it, whatever the
+                // schedule.  The pack in plain C++ (two shifts and a v_bfi_b32, hazards owned by the compiler) needs one more live
+                // register per pack and spilled 24 VGPRs to scratch here (experiments/README.md), so it was not kept.
                 auto shpack = [](int a, int b) {
                     uint32_t v = (uint32_t)(a >> (HB_SHIFT - 1));
-                    asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(v) : "s"(HB_SHIFT - 1), "v"(b));
+                    asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\ts_nop 0" : "+v"(v) : "s"(HB_SHIFT - 1), "v"(b));
                     return v;
                 };
                 const uint32_t sI02 = shpack(SI[0], SI[2]), sI13 = shpack(SI[1], SI[3]);
@@ -227,16 +277,16 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
                     st4(d[3], psub(sI02, cI02), padd(sQ02, cQ02), padd(sI13, cI13), psub(sQ13, cQ13), mb);
                 } else {
                     const std::integral_constant<bool, CLS == MX_SINK> Sk;
-                    const long abs0 = CLS == MX_SINK ? chunk * nout + d[6] + 16 * n16 + 4 * g4 : 0;
+                    const long job0 = CLS == MX_SINK ? chunk * nout + d[6] : 0;       // first output of the job: wave-uniform
                     // child 0: the centre stage (every centre tap added), or the lower half: k even -> (+im, -re), k odd -> (-im, +re);
                     // child 1: the upper half, the negation (inthalfbandfiltereo.h:158-206, 357-405).  The sign that differs between
                     // centre and lower is one packed multiply.
                     const uint32_t sg = (meta & MX_LU_BIT) ? 0xffffffffu : PLAIN;
                     if (f0 | (d[4] >= 0)) {
                         const uint32_t nI13 = pmul(cI13, sg), nQ02 = pmul(cQ02, sg);
-                        child(Sk, padd(sI02, cI02), padd(sI13, nI13), padd(sQ02, nQ02), padd(sQ13, cQ13), d[2], f0, d[4], abs0);
+                        child(Sk, padd(sI02, cI02), padd(sI13, nI13), padd(sQ02, nQ02), padd(sQ13, cQ13), d[2], f0, d[4], job0);
                     }
-                    if (f1 | (d[5] >= 0)) child(Sk, psub(sI02, cI02), padd(sI13, cI13), padd(sQ02, cQ02), psub(sQ13, cQ13), d[3], f1, d[5], abs0);
+                    if (f1 | (d[5] >= 0)) child(Sk, psub(sI02, cI02), padd(sI13, cI13), padd(sQ02, cQ02), psub(sQ13, cQ13), d[3], f1, d[5], job0);
                 }
             };
             // two jobs of one class: both jobs' loads, then the MFMAs, then the epilogues (tree_kernel.hpp); or one job
