@@ -42,14 +42,6 @@ def _share_hip_runtime_with_torch() -> None:
         C.CDLL(p, mode=C.RTLD_GLOBAL)
 
 
-def _del(self):
-    """Finaliser shared by the handle classes: close(), quietly -- at interpreter shutdown the module's globals may already be gone."""
-    try:
-        self.close()
-    except Exception:
-        pass
-
-
 def lib() -> C.CDLL:
     """Load libsdrx.so (built in-tree by `make -C sdrangel_amd/csrc` / __graft_entry__.build())."""
     global _lib
@@ -74,20 +66,15 @@ def lib() -> C.CDLL:
         "sdrx_decim_process": (C.c_int, [vp, vp, i32, vp, C.POINTER(i32)]),
         "sdrx_decim_process_dev": (C.c_int, [vp, vp, i64, vp, C.POINTER(i64)]),
         "sdrx_decim_process_dev_batch": (C.c_int, [vp, i32, vp, vp, vp, vp]),
-        "sdrx_decim_sync": (C.c_int, [vp]),
         "sdrx_decim_ring_create": (C.c_int, [vp, i32, i32, i32]),
         "sdrx_decim_ring_destroy": (C.c_int, [vp]),
         "sdrx_decim_ring_acquire": (vp, [vp]),
         "sdrx_decim_ring_submit": (C.c_int, [vp, i32]),
         "sdrx_decim_ring_retire": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i32)]),
-        "sdrx_decim_set_stream": (C.c_int, [vp, vp]),
         "sdrx_decim_group_int16": (C.c_int, [C.c_int, C.c_int]),
         "sdrx_decim_state_bytes": (i64, [vp]),
         "sdrx_decim_get_state": (C.c_int, [vp, vp]),
         "sdrx_decim_set_state": (C.c_int, [vp, vp]),
-        "sdrx_decim_set_timing": (C.c_int, [vp, C.c_int]),
-        "sdrx_decim_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
-        "sdrx_decim_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_decim_last_fallback": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), vp, i64]),
         "sdrx_chan_bank_create": (C.c_int, [pp, C.c_int, i32, i32, vp, vp]),
         "sdrx_chan_bank_destroy": (C.c_int, [vp]),
@@ -104,12 +91,6 @@ def lib() -> C.CDLL:
         "sdrx_chan_bank_read": (i64, [vp, i32, vp, i64]),
         "sdrx_chan_bank_skip": (i64, [vp, i32, i64]),
         "sdrx_chan_bank_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
-        "sdrx_chan_bank_sync": (C.c_int, [vp]),
-        "sdrx_chan_bank_set_stream": (C.c_int, [vp, vp]),
-        "sdrx_chan_bank_get_stream": (C.c_int, [vp, C.POINTER(vp)]),
-        "sdrx_chan_bank_set_timing": (C.c_int, [vp, C.c_int]),
-        "sdrx_chan_bank_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
-        "sdrx_chan_bank_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_backend_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_backend_destroy": (C.c_int, [vp]),
         "sdrx_backend_feed": (C.c_int, [vp, vp, vp]),
@@ -121,36 +102,25 @@ def lib() -> C.CDLL:
         "sdrx_dccorr_reset": (C.c_int, [vp]),
         "sdrx_dccorr_process": (C.c_int, [vp, vp, C.c_int64]),
         "sdrx_dccorr_process_dev": (C.c_int, [vp, vp, vp, C.c_int64]),
-        "sdrx_dccorr_sync": (C.c_int, [vp]),
-        "sdrx_dccorr_set_stream": (C.c_int, [vp, vp]),
         "sdrx_iqimb_create": (C.c_int, [C.POINTER(vp), C.c_int, i32]),
         "sdrx_iqimb_destroy": (C.c_int, [vp]),
         "sdrx_iqimb_reset": (C.c_int, [vp]),
         "sdrx_iqimb_process": (C.c_int, [vp, vp, vp]),
         "sdrx_iqimb_process_dev": (C.c_int, [vp, vp, vp, vp]),
-        "sdrx_iqimb_sync": (C.c_int, [vp]),
-        "sdrx_iqimb_set_stream": (C.c_int, [vp, vp]),
         "sdrx_fdecim_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "sdrx_fdecim_destroy": (C.c_int, [vp]),
         "sdrx_fdecim_reset": (C.c_int, [vp]),
         "sdrx_fdecim_process": (C.c_int, [vp, vp, C.c_int32, vp, C.POINTER(C.c_int32)]),
         "sdrx_fdecim_process_dev": (C.c_int, [vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]),
-        "sdrx_fdecim_sync": (C.c_int, [vp]),
-        "sdrx_fdecim_set_stream": (C.c_int, [vp, vp]),
         "sdrx_fdecim_group": (C.c_int32, [C.c_int, C.c_int]),
-        "sdrx_fdecim_set_timing": (C.c_int, [vp, C.c_int]),
-        "sdrx_fdecim_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
-        "sdrx_fdecim_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_backend_read": (i64, [vp, i32, vp, i64]),
         "sdrx_backend_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
         "sdrx_backend_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32)]),
-        "sdrx_backend_sync": (C.c_int, [vp]),
         "sdrx_audiotail_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_audiotail_destroy": (C.c_int, [vp]),
         "sdrx_audiotail_reset": (C.c_int, [vp]),
         "sdrx_audiotail_feed": (C.c_int, [vp, vp, vp, vp]),
         "sdrx_audiotail_feed_dev": (C.c_int, [vp, vp, vp, vp]),
-        "sdrx_audiotail_sync": (C.c_int, [vp]),
         "sdrx_iir_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_iir_destroy": (C.c_int, [vp]),
         "sdrx_iir_reset": (C.c_int, [vp]),
@@ -179,12 +149,6 @@ def lib() -> C.CDLL:
         "sdrx_spectrum_read": (i64, [vp, vp, i64]),
         "sdrx_spectrum_skip": (i64, [vp, i64]),
         "sdrx_spectrum_window": (C.c_int, [vp, vp, i32]),
-        "sdrx_spectrum_sync": (C.c_int, [vp]),
-        "sdrx_spectrum_set_stream": (C.c_int, [vp, vp]),
-        "sdrx_spectrum_get_stream": (C.c_int, [vp, pp]),
-        "sdrx_spectrum_set_timing": (C.c_int, [vp, C.c_int]),
-        "sdrx_spectrum_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
-        "sdrx_spectrum_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_wfm_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_wfm_destroy": (C.c_int, [vp]),
         "sdrx_wfm_reset": (C.c_int, [vp]),
@@ -196,12 +160,6 @@ def lib() -> C.CDLL:
         "sdrx_wfm_squelch_open": (C.c_int, [vp, i32]),
         "sdrx_wfm_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_wfm_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
-        "sdrx_wfm_sync": (C.c_int, [vp]),
-        "sdrx_wfm_set_stream": (C.c_int, [vp, vp]),
-        "sdrx_wfm_get_stream": (C.c_int, [vp, pp]),
-        "sdrx_wfm_set_timing": (C.c_int, [vp, C.c_int]),
-        "sdrx_wfm_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
-        "sdrx_wfm_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_am_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_am_destroy": (C.c_int, [vp]),
         "sdrx_am_reset": (C.c_int, [vp]),
@@ -213,12 +171,6 @@ def lib() -> C.CDLL:
         "sdrx_am_squelch_open": (C.c_int, [vp, i32]),
         "sdrx_am_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_am_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
-        "sdrx_am_sync": (C.c_int, [vp]),
-        "sdrx_am_set_stream": (C.c_int, [vp, vp]),
-        "sdrx_am_get_stream": (C.c_int, [vp, pp]),
-        "sdrx_am_set_timing": (C.c_int, [vp, C.c_int]),
-        "sdrx_am_get_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
-        "sdrx_am_last_launch": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "sdrx_fdecim_state_bytes": (i64, [vp]),
         "sdrx_fdecim_get_state": (C.c_int, [vp, vp]),
         "sdrx_fdecim_set_state": (C.c_int, [vp, vp]),
@@ -230,10 +182,8 @@ def lib() -> C.CDLL:
         "sdrx_fdecim_save_stages": (C.c_int, [vp, vp]),
         "sdrx_fdecim_load_stages": (C.c_int, [vp, vp]),
         "sdrx_decim24_process_dev": (C.c_int, [vp, vp, i64, vp, C.POINTER(i64)]),
-        "sdrx_decim24_sync": (C.c_int, [vp]),
         "sdrx_chan24_bank_feed_dev": (C.c_int, [vp, vp, i64]),
         "sdrx_chan24_bank_out_dev": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(i64)]),
-        "sdrx_chan24_bank_sync": (C.c_int, [vp]),
         "sdrx_chan24_bank_create": (C.c_int, [pp, C.c_int, i32, i32, vp, vp]),
         "sdrx_chan24_bank_destroy": (C.c_int, [vp]),
         "sdrx_chan24_bank_reset": (C.c_int, [vp]),
@@ -258,6 +208,22 @@ def lib() -> C.CDLL:
         "sdrx_fifo_read_commit": (u32, [vp, u32]),
         "sdrx_fifo_dropped": (C.c_uint64, [vp]),
     }
+    # the stream / timing / launch-record accessors: one row per kind, stamped per handle family that exports it
+    acc = {
+        "sync": [vp],
+        "set_stream": [vp, vp],
+        "get_stream": [vp, pp],
+        "set_timing": [vp, C.c_int],
+        "get_timing": [vp, C.POINTER(C.c_double), C.POINTER(i64), C.c_int],
+        "last_launch": [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    }
+    five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
+    families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
+                "wfm": five + ("get_stream",), "am": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
+    for prefix, names in families.items():
+        for name in names:
+            sig[f"sdrx_{prefix}_{name}"] = (C.c_int, acc[name])
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == the header and the library disagree
         fn.restype = res
@@ -287,53 +253,106 @@ def _i16(a) -> np.ndarray:
     return a
 
 
-class Decimators:
-    """Decimators<qint32, qint16, 16, input_bits> used with one (log2, fcpos)
-    (sdrbase/dsp/decimators.h:279-341).  `decimate(buf)` == decimateK_{inf,sup,cen}(&it, buf, len)."""
+class _Handle:
+    """Owner of one C handle; `_prefix` names its entry points (sdrx_<prefix>_*)."""
 
-    def __init__(self, log2_decim: int, fcpos: int = FC_CEN, input_bits: int = 12, device: int = 0):
+    _prefix = ""
+
+    def _fn(self, name: str):
+        return getattr(lib(), f"sdrx_{self._prefix}_{name}")
+
+    def _open(self, *args, create: str = "create"):
         self._h = C.c_void_p()
-        _check(lib().sdrx_decim_create(C.byref(self._h), device, log2_decim, fcpos, input_bits), "sdrx_decim_create")
-        self.log2, self.fcpos, self.input_bits = log2_decim, fcpos, input_bits
+        _check(self._fn(create)(C.byref(self._h), *args), f"sdrx_{self._prefix}_{create}")
+
+    def _call(self, name: str, *args, what: str | None = None):
+        _check(self._fn(name)(self._h, *args), what or f"sdrx_{self._prefix}_{name}")
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_decim_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
-    __del__ = _del
+    def __del__(self):
+        try:                               # quietly: at interpreter shutdown the module's globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+# The accessors every stream-owning handle family shares, written once; a class lists the mixins whose entry points its
+# family exports (lib() binds the same rows per prefix).
+class _Sync:
+    def sync(self):
+        self._call("sync")
+
+
+class _SetStream:
+    def set_stream(self, hip_stream: int | None):
+        self._call("set_stream", hip_stream)
+
+
+class _GetStream:
+    def get_stream(self) -> int:
+        p = C.c_void_p()
+        self._call("get_stream", C.byref(p))
+        return p.value or 0
+
+
+class _Timed:
+    def set_timing(self, on: bool):
+        self._call("set_timing", int(on))
+
+    def get_timing(self, reset: bool = True):
+        """(total kernel ms, launches) measured with HIP events on the launch stream"""
+        ms, n = C.c_double(), C.c_int64()
+        self._call("get_timing", C.byref(ms), C.byref(n), int(reset))
+        return ms.value, n.value
+
+    def last_launch(self) -> dict:
+        name = C.create_string_buffer(128)
+        g, b, l = C.c_int(), C.c_int(), C.c_int()
+        self._call("last_launch", name, 128, C.byref(g), C.byref(b), C.byref(l), what="last_launch")
+        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
+
+
+class Decimators(_Handle, _Sync, _SetStream, _Timed):
+    """Decimators<qint32, qint16, 16, input_bits> used with one (log2, fcpos)
+    (sdrbase/dsp/decimators.h:279-341).  `decimate(buf)` == decimateK_{inf,sup,cen}(&it, buf, len)."""
+    _prefix = "decim"
+
+    def __init__(self, log2_decim: int, fcpos: int = FC_CEN, input_bits: int = 12, device: int = 0):
+        self._open(device, log2_decim, fcpos, input_bits)
+        self.log2, self.fcpos, self.input_bits = log2_decim, fcpos, input_bits
 
     def reset(self):
-        _check(lib().sdrx_decim_reset(self._h), "sdrx_decim_reset")
+        self._call("reset")
 
     def decimate(self, buf) -> np.ndarray:
         """buf: int16 interleaved I,Q (len = reference `len`).  Returns int16 array of 2*n_out."""
         buf = _i16(buf)
         out = np.empty(max(2 * ((buf.size // 2) >> self.log2), 2), np.int16)
         n = C.c_int32()
-        _check(lib().sdrx_decim_process(self._h, buf.ctypes.data, buf.size, out.ctypes.data, C.byref(n)), "sdrx_decim_process")
+        self._call("process", buf.ctypes.data, buf.size, out.ctypes.data, C.byref(n))
         return out[: 2 * n.value]
 
     def decimate_dev(self, d_in_ptr: int, n_int16: int, d_out_ptr: int) -> int:
         """device pointers; asynchronous on the handle's stream; returns #complex outputs"""
         n = C.c_int64()
-        _check(lib().sdrx_decim_process_dev(self._h, d_in_ptr, n_int16, d_out_ptr, C.byref(n)), "sdrx_decim_process_dev")
+        self._call("process_dev", d_in_ptr, n_int16, d_out_ptr, C.byref(n))
         return n.value
-
-    def sync(self):
-        _check(lib().sdrx_decim_sync(self._h), "sdrx_decim_sync")
 
     def save_stages(self, stages: "DecimStages"):
         """stages 1..log2 of `stages` := what this variant's filters hold now"""
-        _check(lib().sdrx_decim_save_stages(self._h, stages._h), "sdrx_decim_save_stages")
+        self._call("save_stages", stages._h)
 
     def load_stages(self, stages: "DecimStages"):
         """continue from the shared filter set of one reference Decimators object (decimators.h:326-333)"""
-        _check(lib().sdrx_decim_load_stages(self._h, stages._h), "sdrx_decim_load_stages")
+        self._call("load_stages", stages._h)
 
     # ---- pinned double-buffered host path: the receive buffer IS a slot of the handle's pinned ring
     def ring_create(self, slot_elems: int, n_slots: int, flush_slots: int = 1):
-        _check(lib().sdrx_decim_ring_create(self._h, slot_elems, n_slots, flush_slots), "sdrx_decim_ring_create")
+        self._call("ring_create", slot_elems, n_slots, flush_slots)
         self._slot_elems = slot_elems
 
     def ring_acquire(self) -> np.ndarray:
@@ -345,44 +364,26 @@ class Decimators:
         return np.ctypeslib.as_array((ct * self._slot_elems).from_address(p))
 
     def ring_submit(self, n_elems: int):
-        _check(lib().sdrx_decim_ring_submit(self._h, n_elems), "sdrx_decim_ring_submit")
+        self._call("ring_submit", n_elems)
 
     def ring_retire(self) -> np.ndarray:
         """outputs of the oldest submitted block (a view of the pinned output slot: copy it before that slot is reused)"""
         out, n = C.c_void_p(), C.c_int32()
-        _check(lib().sdrx_decim_ring_retire(self._h, C.byref(out), C.byref(n)), "sdrx_decim_ring_retire")
+        self._call("ring_retire", C.byref(out), C.byref(n))
         if n.value == 0:
             return np.empty(0, np.int16)
         return np.ctypeslib.as_array((C.c_int16 * (2 * n.value)).from_address(out.value))
 
-    def set_stream(self, hip_stream: int | None):
-        _check(lib().sdrx_decim_set_stream(self._h, hip_stream), "sdrx_decim_set_stream")
-
-    def set_timing(self, on: bool):
-        _check(lib().sdrx_decim_set_timing(self._h, int(on)), "sdrx_decim_set_timing")
-
-    def get_timing(self, reset: bool = True):
-        """(total kernel ms, launches) measured with HIP events on the launch stream"""
-        ms, n = C.c_double(), C.c_int64()
-        _check(lib().sdrx_decim_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_decim_get_timing")
-        return ms.value, n.value
-
     def get_state(self) -> bytes:
         nb = lib().sdrx_decim_state_bytes(self._h)
         buf = C.create_string_buffer(nb)
-        _check(lib().sdrx_decim_get_state(self._h, buf), "sdrx_decim_get_state")
+        self._call("get_state", buf)
         return buf.raw
 
     def set_state(self, state: bytes):
         if len(state) != lib().sdrx_decim_state_bytes(self._h):
             raise ValueError("state size")
-        _check(lib().sdrx_decim_set_state(self._h, state), "sdrx_decim_set_state")
-
-    def last_launch(self) -> dict:
-        name = C.create_string_buffer(128)
-        g, b, l = C.c_int(), C.c_int(), C.c_int()
-        _check(lib().sdrx_decim_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
-        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
+        self._call("set_state", state)
 
     def last_fallback(self) -> dict:
         """chunks (4096 input samples) of the most recent call that the FAST kernel flagged for the EXACT recompute;
@@ -410,19 +411,12 @@ def decimate_dev_batch(handles, d_in_ptrs, n_elems, d_out_ptrs) -> list:
     return list(no)
 
 
-class DecimStages:
+class DecimStages(_Handle):
     """The six IntHalfbandFilterEO states that all decimateK_x of ONE reference Decimators object share."""
+    _prefix = "decim_stages"
 
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        _check(lib().sdrx_decim_stages_create(C.byref(self._h), device), "sdrx_decim_stages_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_decim_stages_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device)
 
 
 class DecimatorsObject:
@@ -456,8 +450,7 @@ class DecimatorsU(Decimators):
     """DecimatorsU<qint32, quint8, 16, 8, shift> (sdrbase/dsp/decimatorsu.h): unsigned 8-bit I/Q (RTL-SDR)."""
 
     def __init__(self, log2_decim: int, fcpos: int = FC_CEN, shift: int = 127, device: int = 0):
-        self._h = C.c_void_p()
-        _check(lib().sdrx_decim_create_u8(C.byref(self._h), device, log2_decim, fcpos, shift), "sdrx_decim_create_u8")
+        self._open(device, log2_decim, fcpos, shift, create="create_u8")
         self.log2, self.fcpos, self.input_bits = log2_decim, fcpos, 8
 
     def decimate(self, buf) -> np.ndarray:
@@ -470,45 +463,31 @@ class DecimatorsU(Decimators):
         return out[: 2 * n.value]
 
 
-class Fanout:
+class Fanout(_Handle):
     """One staged source stream copied to several GPUs point-to-point (sdrx_fanout_*; xGMI peer copies on a multi-GPU node)."""
+    _prefix = "fanout"
 
     def __init__(self, src_device: int, dst_devices, max_bytes: int):
         d = np.ascontiguousarray(dst_devices, dtype=np.int32)
         self.n = d.size
-        self._h = C.c_void_p()
-        _check(lib().sdrx_fanout_create(C.byref(self._h), src_device, self.n, d.ctypes.data, max_bytes), "sdrx_fanout_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_fanout_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(src_device, self.n, d.ctypes.data, max_bytes)
 
     def send(self, d_src: int, n_bytes: int, producer_stream: int | None = None):
-        _check(lib().sdrx_fanout_send(self._h, d_src, n_bytes, producer_stream), "sdrx_fanout_send")
+        self._call("send", d_src, n_bytes, producer_stream)
 
     def buffer(self, i: int) -> int:
         return lib().sdrx_fanout_buffer(self._h, i) or 0
 
     def wait(self, i: int):
-        _check(lib().sdrx_fanout_wait(self._h, i), "sdrx_fanout_wait")
+        self._call("wait", i)
 
 
-class FloatDecimStages:
+class FloatDecimStages(_Handle):
     """The six IntHalfbandFilterEOF states that all decimateK_x of ONE DecimatorsFI / FF / IF object share."""
+    _prefix = "fdecim_stages"
 
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        _check(lib().sdrx_fdecim_stages_create(C.byref(self._h), device), "sdrx_fdecim_stages_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_fdecim_stages_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device)
 
 
 class FloatDecimatorsObject:
@@ -538,93 +517,53 @@ class FloatDecimatorsObject:
         self._stages.close()
 
 
-class FloatDecimators:
+class FloatDecimators(_Handle, _Sync, _SetStream, _Timed):
     """The float half-band decimators over IntHalfbandFilterEOF<64>, one (log2, fcpos) per object:
     kind "fi" = DecimatorsFI (float I/Q -> int16 Sample; AirspyHF), "ff" = DecimatorsFF (float -> float),
     "if" = DecimatorsIF<qint16, input_bits> (int16 -> float).  `decimate(buf)` == decimateK_{inf,sup,cen}(&it, buf, nbIAndQ)."""
+    _prefix = "fdecim"
 
     KINDS = {"fi": (0, 0), "ff": (0, 1), "if": (1, 1)}
 
     def __init__(self, kind: str, log2_decim: int, fcpos: int = FC_CEN, input_bits: int = 16, device: int = 0):
         self.in_kind, self.out_kind = self.KINDS[kind]
-        self._h = C.c_void_p()
-        _check(lib().sdrx_fdecim_create(C.byref(self._h), device, log2_decim, fcpos, self.in_kind, self.out_kind, input_bits), "sdrx_fdecim_create")
+        self._open(device, log2_decim, fcpos, self.in_kind, self.out_kind, input_bits)
         self.kind, self.log2, self.fcpos = kind, log2_decim, fcpos
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_fdecim_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
-
     def reset(self):
-        _check(lib().sdrx_fdecim_reset(self._h), "sdrx_fdecim_reset")
+        self._call("reset")
 
     def decimate(self, buf) -> np.ndarray:
         buf = np.ascontiguousarray(buf, dtype=np.float32 if self.in_kind == 0 else np.int16)
         out = np.empty(buf.size + 8, np.int16 if self.out_kind == 0 else np.float32)
         n = C.c_int32()
-        _check(lib().sdrx_fdecim_process(self._h, buf.ctypes.data, buf.size, out.ctypes.data, C.byref(n)), "sdrx_fdecim_process")
+        self._call("process", buf.ctypes.data, buf.size, out.ctypes.data, C.byref(n))
         return out[: 2 * n.value]
 
     def decimate_dev(self, d_in_ptr: int, n_elems: int, d_out_ptr: int) -> int:
         n = C.c_int64()
-        _check(lib().sdrx_fdecim_process_dev(self._h, d_in_ptr, n_elems, d_out_ptr, C.byref(n)), "sdrx_fdecim_process_dev")
+        self._call("process_dev", d_in_ptr, n_elems, d_out_ptr, C.byref(n))
         return n.value
 
-    def sync(self):
-        _check(lib().sdrx_fdecim_sync(self._h), "sdrx_fdecim_sync")
 
-    def set_stream(self, hip_stream: int | None):
-        _check(lib().sdrx_fdecim_set_stream(self._h, hip_stream), "sdrx_fdecim_set_stream")
-
-    def set_timing(self, on: bool):
-        _check(lib().sdrx_fdecim_set_timing(self._h, int(on)), "sdrx_fdecim_set_timing")
-
-    def get_timing(self, reset: bool = True):
-        ms, n = C.c_double(), C.c_int64()
-        _check(lib().sdrx_fdecim_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_fdecim_get_timing")
-        return ms.value, n.value
-
-    def last_launch(self) -> dict:
-        name = C.create_string_buffer(128)
-        g, b, l = C.c_int(), C.c_int(), C.c_int()
-        _check(lib().sdrx_fdecim_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
-        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
-
-
-class DcCorrection:
+class DcCorrection(_Handle, _Sync, _SetStream):
     """DSPDeviceSourceEngine::iqCorrections(begin, end, false): the DC offset correction of the device stream"""
+    _prefix = "dccorr"
 
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        _check(lib().sdrx_dccorr_create(C.byref(self._h), device), "sdrx_dccorr_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_dccorr_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device)
 
     def reset(self):
-        _check(lib().sdrx_dccorr_reset(self._h), "sdrx_dccorr_reset")
+        self._call("reset")
 
     def process(self, iq) -> np.ndarray:
         """returns the corrected copy of an int16 I/Q span (the C call works in place)"""
         buf = np.array(iq, dtype=np.int16, copy=True)
-        _check(lib().sdrx_dccorr_process(self._h, buf.ctypes.data, buf.size // 2), "sdrx_dccorr_process")
+        self._call("process", buf.ctypes.data, buf.size // 2)
         return buf
 
     def process_dev(self, d_in_ptr: int, d_out_ptr: int, n_cplx: int):
-        _check(lib().sdrx_dccorr_process_dev(self._h, d_in_ptr, d_out_ptr, n_cplx), "sdrx_dccorr_process_dev")
-
-    def sync(self):
-        _check(lib().sdrx_dccorr_sync(self._h), "sdrx_dccorr_sync")
-
-    def set_stream(self, hip_stream: int | None):
-        _check(lib().sdrx_dccorr_set_stream(self._h, hip_stream), "sdrx_dccorr_set_stream")
+        self._call("process_dev", d_in_ptr, d_out_ptr, n_cplx)
 
 
 # FFTWindow::Function and SpectrumVis::AveragingMode (include/sdrx.h SDRX_SPECTRUM_*)
@@ -637,27 +576,20 @@ class SpectrumCfg(C.Structure):
                 ("window", C.c_int32), ("linear", C.c_int32), ("scalef", C.c_float)]
 
 
-class SpectrumVis:
+class SpectrumVis(_Handle, _Sync, _SetStream, _GetStream, _Timed):
     """SpectrumVis (sdrgui/dsp/spectrumvis.{h,cpp}) on the GPU: every frame the reference hands to
     GLSpectrum::newSpectrum is queued on the device until read() -> (frames, N) float32."""
+    _prefix = "spectrum"
 
     def __init__(self, fft_size: int = 1024, overlap_percent: int = 0, avg_nb: int = 0, avg_mode: int = AVG_NONE,
                  window: int = WIN_BLACKMAN_HARRIS, linear: bool = False, scalef: float = 32768.0, device: int = 0):
-        self._h = C.c_void_p()
         cfg = self._cfg(fft_size, overlap_percent, avg_nb, avg_mode, window, linear, scalef)
-        _check(lib().sdrx_spectrum_create(C.byref(self._h), device, C.byref(cfg)), "sdrx_spectrum_create")
+        self._open(device, C.byref(cfg))
         self.scalef = scalef
 
     @staticmethod
     def _cfg(fft_size, overlap_percent, avg_nb, avg_mode, window, linear, scalef) -> SpectrumCfg:
         return SpectrumCfg(int(fft_size), int(overlap_percent), int(avg_nb), int(avg_mode), int(window), int(bool(linear)), float(scalef))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_spectrum_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
 
     @property
     def fft_size(self) -> int:
@@ -666,21 +598,21 @@ class SpectrumVis:
     def configure(self, fft_size: int, overlap_percent: int, avg_nb: int, avg_mode: int, window: int, linear: bool):
         """handleConfigure: keeps the 4096-entry buffer, zeroes the averages"""
         cfg = self._cfg(fft_size, overlap_percent, avg_nb, avg_mode, window, linear, self.scalef)
-        _check(lib().sdrx_spectrum_configure(self._h, C.byref(cfg)), "sdrx_spectrum_configure")
+        self._call("configure", C.byref(cfg))
 
     def reset(self):
-        _check(lib().sdrx_spectrum_reset(self._h), "sdrx_spectrum_reset")
+        self._call("reset")
 
     def feed(self, iq, positive_only: bool = False):
         iq = _i16(iq)
-        _check(lib().sdrx_spectrum_feed(self._h, iq.ctypes.data, iq.size // 2, int(positive_only)), "sdrx_spectrum_feed")
+        self._call("feed", iq.ctypes.data, iq.size // 2, int(positive_only))
 
     def feed_dev(self, t, positive_only: bool = False):
         """t: a contiguous int16 torch tensor of interleaved I/Q on the handle's device, ordered against the handle's
         stream by the caller (synchronise, or hand the torch stream over with set_stream)"""
         if not t.is_contiguous() or str(t.dtype) != "torch.int16":
             raise TypeError("expected a contiguous int16 tensor")
-        _check(lib().sdrx_spectrum_feed_dev(self._h, t.data_ptr(), t.numel() // 2, int(positive_only)), "sdrx_spectrum_feed_dev")
+        self._call("feed_dev", t.data_ptr(), t.numel() // 2, int(positive_only))
 
     def available(self) -> int:
         return lib().sdrx_spectrum_available(self._h)
@@ -703,31 +635,6 @@ class SpectrumVis:
         lib().sdrx_spectrum_window(self._h, out.ctypes.data, n)
         return out
 
-    def sync(self):
-        _check(lib().sdrx_spectrum_sync(self._h), "sdrx_spectrum_sync")
-
-    def set_stream(self, hip_stream: int | None):
-        _check(lib().sdrx_spectrum_set_stream(self._h, hip_stream), "sdrx_spectrum_set_stream")
-
-    def get_stream(self) -> int:
-        p = C.c_void_p()
-        _check(lib().sdrx_spectrum_get_stream(self._h, C.byref(p)), "sdrx_spectrum_get_stream")
-        return p.value or 0
-
-    def set_timing(self, on: bool):
-        _check(lib().sdrx_spectrum_set_timing(self._h, int(on)), "sdrx_spectrum_set_timing")
-
-    def get_timing(self, reset: bool = True):
-        ms, n = C.c_double(), C.c_int64()
-        _check(lib().sdrx_spectrum_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_spectrum_get_timing")
-        return ms.value, n.value
-
-    def last_launch(self) -> dict:
-        name = C.create_string_buffer(128)
-        g, b, l = C.c_int(), C.c_int(), C.c_int()
-        _check(lib().sdrx_spectrum_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
-        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
-
 
 def chan_plan(in_rate: int, req_rate: int, req_fc: int):
     """DownChannelizer::applyConfiguration's float bisection -> (modes, out_rate, residual_ofs)."""
@@ -739,56 +646,48 @@ def chan_plan(in_rate: int, req_rate: int, req_fc: int):
     return modes[:n].copy(), r.value, f.value
 
 
-class ChannelizerBank:
+class ChannelizerBank(_Handle, _Sync, _SetStream, _Timed):
     """N x DownChannelizer fed from one device stream (sdrbase/dsp/downchannelizer.{h,cpp})."""
+    _prefix = "chan_bank"
 
     def __init__(self, in_rate: int, req_rates, req_fcs, device: int = 0):
         rr = np.ascontiguousarray(req_rates, dtype=np.int32)
         fc = np.ascontiguousarray(req_fcs, dtype=np.int32)
         assert rr.size == fc.size
         self.n_ch = int(rr.size)
-        self._h = C.c_void_p()
-        _check(lib().sdrx_chan_bank_create(C.byref(self._h), device, in_rate, self.n_ch, rr.ctypes.data, fc.ctypes.data),
-               "sdrx_chan_bank_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_chan_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device, in_rate, self.n_ch, rr.ctypes.data, fc.ctypes.data)
 
     def info(self, ch: int):
         n, r, f = C.c_int32(), C.c_int32(), C.c_int32()
         modes = np.zeros(32, np.uint8)
-        _check(lib().sdrx_chan_bank_info(self._h, ch, C.byref(n), modes.ctypes.data, C.byref(r), C.byref(f)), "sdrx_chan_bank_info")
+        self._call("info", ch, C.byref(n), modes.ctypes.data, C.byref(r), C.byref(f))
         return modes[: n.value].copy(), r.value, f.value
 
     def add_channel(self, req_rate: int, req_fc: int) -> int:
         c = C.c_int32(-1)
-        _check(lib().sdrx_chan_bank_add_channel(self._h, req_rate, req_fc, C.byref(c)), "sdrx_chan_bank_add_channel")
+        self._call("add_channel", req_rate, req_fc, C.byref(c))
         self.n_ch = max(getattr(self, "n_ch", 0), c.value + 1)
         return c.value
 
     def remove_channel(self, ch: int):
-        _check(lib().sdrx_chan_bank_remove_channel(self._h, ch), "sdrx_chan_bank_remove_channel")
+        self._call("remove_channel", ch)
 
     @property
     def group_count(self) -> int:
         return lib().sdrx_chan_bank_group_count(self._h)
 
     def reconfigure(self, ch: int, req_rate: int, req_fc: int):
-        _check(lib().sdrx_chan_bank_reconfigure(self._h, ch, req_rate, req_fc), "sdrx_chan_bank_reconfigure")
+        self._call("reconfigure", ch, req_rate, req_fc)
 
     def reset(self):
-        _check(lib().sdrx_chan_bank_reset(self._h), "sdrx_chan_bank_reset")
+        self._call("reset")
 
     def feed(self, iq):
         iq = _i16(iq)
-        _check(lib().sdrx_chan_bank_feed(self._h, iq.ctypes.data, iq.size // 2), "sdrx_chan_bank_feed")
+        self._call("feed", iq.ctypes.data, iq.size // 2)
 
     def feed_dev(self, d_ptr: int, n_cplx: int):
-        _check(lib().sdrx_chan_bank_feed_dev(self._h, d_ptr, n_cplx), "sdrx_chan_bank_feed_dev")
+        self._call("feed_dev", d_ptr, n_cplx)
 
     def available(self, ch: int) -> int:
         return lib().sdrx_chan_bank_available(self._h, ch)
@@ -804,31 +703,11 @@ class ChannelizerBank:
     def last_dev(self, ch: int):
         """(device pointer, n_cplx) of what the last feed produced for channel ch"""
         p, n = C.c_void_p(), C.c_int64()
-        _check(lib().sdrx_chan_bank_last_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_chan_bank_last_dev")
+        self._call("last_dev", ch, C.byref(p), C.byref(n))
         return p.value or 0, n.value
 
     def skip(self, ch: int, n: int = -1) -> int:
         return lib().sdrx_chan_bank_skip(self._h, ch, n)
-
-    def sync(self):
-        _check(lib().sdrx_chan_bank_sync(self._h), "sdrx_chan_bank_sync")
-
-    def set_stream(self, hip_stream: int | None):
-        _check(lib().sdrx_chan_bank_set_stream(self._h, hip_stream), "sdrx_chan_bank_set_stream")
-
-    def set_timing(self, on: bool):
-        _check(lib().sdrx_chan_bank_set_timing(self._h, int(on)), "sdrx_chan_bank_set_timing")
-
-    def get_timing(self, reset: bool = True):
-        ms, n = C.c_double(), C.c_int64()
-        _check(lib().sdrx_chan_bank_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_chan_bank_get_timing")
-        return ms.value, n.value
-
-    def last_launch(self) -> dict:
-        name = C.create_string_buffer(128)
-        g, b, l = C.c_int(), C.c_int(), C.c_int()
-        _check(lib().sdrx_chan_bank_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
-        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
 
 
 class FirCfg(C.Structure):
@@ -836,21 +715,14 @@ class FirCfg(C.Structure):
     _fields_ = [("kind", C.c_int32), ("ntaps", C.c_int32), ("sample_rate", C.c_float), ("f1", C.c_float), ("f2", C.c_float)]
 
 
-class FirBank:
+class FirBank(_Handle):
     """Lowpass<Real> / Bandpass<Real> (sdrbase/dsp/lowpass.h, bandpass.h) for N channels."""
+    _prefix = "firbank"
 
     def __init__(self, cfgs, device: int = 0):
         self.n_ch = len(cfgs)
         arr = (FirCfg * self.n_ch)(*cfgs)
-        self._h = C.c_void_p()
-        _check(lib().sdrx_firbank_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_firbank_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_firbank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device, self.n_ch, arr)
 
     def taps(self, ch: int) -> np.ndarray:
         t = np.zeros(4096, np.float32)
@@ -863,7 +735,7 @@ class FirBank:
         pi = (C.c_void_p * self.n_ch)(*[x.ctypes.data for x in ins])
         po = (C.c_void_p * self.n_ch)(*[x.ctypes.data for x in outs])
         ns = (C.c_int64 * self.n_ch)(*[x.size for x in ins])
-        _check(lib().sdrx_firbank_feed(self._h, pi, ns, po), "sdrx_firbank_feed")
+        self._call("feed", pi, ns, po)
         return [o[: x.size] for o, x in zip(outs, ins)]
 
 
@@ -894,37 +766,30 @@ class BackendCfg(C.Structure):
                 ("f1", C.c_float), ("f2", C.c_float), ("discri", C.c_int32), ("fm_scaling", C.c_float)]
 
 
-class BackendBank:
+class BackendBank(_Handle, _Sync):
     """NCO -> Interpolator -> fftfilt -> discriminator for N channels (front of the channelrx demods)."""
+    _prefix = "backend"
 
     def __init__(self, cfgs, device: int = 0):
         self.n_ch = len(cfgs)
         arr = (BackendCfg * self.n_ch)(*cfgs)
-        self._h = C.c_void_p()
-        _check(lib().sdrx_backend_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_backend_create")
+        self._open(device, self.n_ch, arr)
         self.cfgs = list(cfgs)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_backend_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
 
     def feed(self, per_channel_iq):
         bufs = [_i16(x) for x in per_channel_iq]
         ptrs = (C.c_void_p * self.n_ch)(*[b.ctypes.data for b in bufs])
         ns = (C.c_int64 * self.n_ch)(*[b.size // 2 for b in bufs])
-        _check(lib().sdrx_backend_feed(self._h, ptrs, ns), "sdrx_backend_feed")
+        self._call("feed", ptrs, ns)
 
     def feed_bank(self, bank: "ChannelizerBank"):
         """channel c takes what the bank's last feed produced for its channel c; ordered on the device, no host sync"""
-        _check(lib().sdrx_backend_feed_bank(self._h, bank._h), "sdrx_backend_feed_bank")
+        self._call("feed_bank", bank._h)
 
     def feed_dev(self, ptrs, counts):
         p = (C.c_void_p * self.n_ch)(*ptrs)
         n = (C.c_int64 * self.n_ch)(*counts)
-        _check(lib().sdrx_backend_feed_dev(self._h, p, n), "sdrx_backend_feed_dev")
+        self._call("feed_dev", p, n)
 
     def read(self, ch: int, cap_floats: int = 1 << 24) -> np.ndarray:
         out = np.empty(cap_floats, np.float32)
@@ -936,18 +801,14 @@ class BackendBank:
     def last_dev(self, ch: int):
         """(device pointer, number of floats) of the last feed's output of channel ch"""
         p, n = C.c_void_p(), C.c_int64()
-        _check(lib().sdrx_backend_last_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_backend_last_dev")
+        self._call("last_dev", ch, C.byref(p), C.byref(n))
         return p.value or 0, n.value
-
-    def sync(self):
-        _check(lib().sdrx_backend_sync(self._h), "sdrx_backend_sync")
 
     def design(self, ch: int):
         nt, inc = C.c_int32(), C.c_int32()
         taps = np.zeros(16 * 256, np.float32)
         filt = np.zeros(4096, np.float32)
-        _check(lib().sdrx_backend_get_design(self._h, ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc)),
-               "sdrx_backend_get_design")
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc))
         return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value
 
 
@@ -958,109 +819,6 @@ class WfmCfg(C.Structure):
                 ("audio_mute", C.c_int32)]
 
 
-def wfm_required_bw(rf_bw: int) -> int:
-    """WFMDemod::requiredBW: the rate the demodulator asks its channelizer for"""
-    return 48000 if rf_bw <= 48000 else (3 * rf_bw) // 2
-
-
-class WfmDemodBank:
-    """N wideband-FM demodulators (WFMDemod::feed): int16 I/Q at the channelizer's output rate in, mono qint16 audio out."""
-
-    def __init__(self, cfgs, device: int = 0):
-        self.n_ch = len(cfgs)
-        arr = (WfmCfg * self.n_ch)(*cfgs)
-        self._h = C.c_void_p()
-        _check(lib().sdrx_wfm_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_wfm_create")
-        self.cfgs = list(cfgs)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_wfm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
-
-    def reset(self):
-        _check(lib().sdrx_wfm_reset(self._h), "sdrx_wfm_reset")
-
-    def feed(self, per_channel_iq):
-        bufs = [_i16(x) for x in per_channel_iq]
-        ptrs = (C.c_void_p * self.n_ch)(*[b.ctypes.data for b in bufs])
-        ns = (C.c_int64 * self.n_ch)(*[b.size // 2 for b in bufs])
-        _check(lib().sdrx_wfm_feed(self._h, ptrs, ns), "sdrx_wfm_feed")
-
-    def feed_dev(self, ptrs, counts):
-        """device pointers (4-byte aligned) and complex sample counts per channel; asynchronous on the handle's stream"""
-        p = (C.c_void_p * self.n_ch)(*ptrs)
-        n = (C.c_int64 * self.n_ch)(*counts)
-        _check(lib().sdrx_wfm_feed_dev(self._h, p, n), "sdrx_wfm_feed_dev")
-
-    def feed_bank(self, bank: "ChannelizerBank"):
-        """channel c takes what the bank's last feed produced for its channel c; ordered on the device, no host sync"""
-        _check(lib().sdrx_wfm_feed_bank(self._h, bank._h), "sdrx_wfm_feed_bank")
-
-    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
-        if cap is None:
-            cap = self.last_dev(ch)[1]
-        out = np.empty(max(cap, 1), np.int16)
-        n = lib().sdrx_wfm_read(self._h, ch, out.ctypes.data, cap)
-        if n < 0:
-            raise SdrxError(f"sdrx_wfm_read rc={n}: {lib().sdrx_last_error().decode()}")
-        return out[:n].copy()
-
-    def last_dev(self, ch: int):
-        """(device pointer, count) of the last feed's audio of channel ch"""
-        p, n = C.c_void_p(), C.c_int64()
-        _check(lib().sdrx_wfm_last_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_wfm_last_dev")
-        return p.value or 0, n.value
-
-    def squelch_open(self, ch: int) -> bool:
-        rc = lib().sdrx_wfm_squelch_open(self._h, ch)
-        if rc < 0:
-            raise SdrxError(f"sdrx_wfm_squelch_open rc={rc}: {lib().sdrx_last_error().decode()}")
-        return bool(rc)
-
-    def levels(self, ch: int, reset: bool = False):
-        """(m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
-        s, p, n = C.c_double(), C.c_double(), C.c_int64()
-        _check(lib().sdrx_wfm_levels(self._h, ch, C.byref(s), C.byref(p), C.byref(n), int(reset)), "sdrx_wfm_levels")
-        return s.value, p.value, n.value
-
-    def design(self, ch: int):
-        """(taps per phase, taps [16 * ntaps], filter spectrum as 2048 floats, NCO increment, squelch level)"""
-        nt, inc, lvl = C.c_int32(), C.c_int32(), C.c_float()
-        taps = np.zeros(16 * 128, np.float32)
-        filt = np.zeros(2048, np.float32)
-        _check(lib().sdrx_wfm_get_design(self._h, ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc), C.byref(lvl)),
-               "sdrx_wfm_get_design")
-        return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value, lvl.value
-
-    def sync(self):
-        _check(lib().sdrx_wfm_sync(self._h), "sdrx_wfm_sync")
-
-    def set_stream(self, hip_stream: int | None):
-        _check(lib().sdrx_wfm_set_stream(self._h, hip_stream), "sdrx_wfm_set_stream")
-
-    def get_stream(self) -> int:
-        p = C.c_void_p()
-        _check(lib().sdrx_wfm_get_stream(self._h, C.byref(p)), "sdrx_wfm_get_stream")
-        return p.value or 0
-
-    def set_timing(self, on: bool):
-        _check(lib().sdrx_wfm_set_timing(self._h, int(on)), "sdrx_wfm_set_timing")
-
-    def get_timing(self, reset: bool = True):
-        ms, n = C.c_double(), C.c_int64()
-        _check(lib().sdrx_wfm_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_wfm_get_timing")
-        return ms.value, n.value
-
-    def last_launch(self) -> dict:
-        name = C.create_string_buffer(128)
-        g, b, l = C.c_int(), C.c_int(), C.c_int()
-        _check(lib().sdrx_wfm_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
-        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
-
-
 class AmCfg(C.Structure):
     """sdrx_am_cfg: one AMDemod in envelope mode (in_rate, nco_freq = -frequencyOffset, audio_rate, AMDemodSettings)"""
     _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
@@ -1068,102 +826,98 @@ class AmCfg(C.Structure):
                 ("audio_mute", C.c_int32), ("bandpass_enable", C.c_int32)]
 
 
-class AmDemodBank:
-    """N AM demodulators (AMDemod::feed, envelope mode): int16 I/Q at the channelizer's output rate in, mono qint16 audio out."""
+def wfm_required_bw(rf_bw: int) -> int:
+    """WFMDemod::requiredBW: the rate the demodulator asks its channelizer for"""
+    return 48000 if rf_bw <= 48000 else (3 * rf_bw) // 2
+
+
+class _DemodBank(_Handle, _Sync, _SetStream, _GetStream, _Timed):
+    """N demodulators of one kind: int16 I/Q at the channelizer's output rate in, mono qint16 audio out.  A subclass
+    names its entry points (`_prefix`) and its cfg struct (`_cfg`) and adds what differs per kind: levels() and design()."""
+
+    _cfg = None
 
     def __init__(self, cfgs, device: int = 0):
         self.n_ch = len(cfgs)
-        arr = (AmCfg * self.n_ch)(*cfgs)
-        self._h = C.c_void_p()
-        _check(lib().sdrx_am_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_am_create")
+        arr = (self._cfg * self.n_ch)(*cfgs)
+        self._open(device, self.n_ch, arr)
         self.cfgs = list(cfgs)
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_am_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
-
     def reset(self):
-        _check(lib().sdrx_am_reset(self._h), "sdrx_am_reset")
+        self._call("reset")
 
     def feed(self, per_channel_iq):
         bufs = [_i16(x) for x in per_channel_iq]
         ptrs = (C.c_void_p * self.n_ch)(*[b.ctypes.data for b in bufs])
         ns = (C.c_int64 * self.n_ch)(*[b.size // 2 for b in bufs])
-        _check(lib().sdrx_am_feed(self._h, ptrs, ns), "sdrx_am_feed")
+        self._call("feed", ptrs, ns)
 
     def feed_dev(self, ptrs, counts):
         """device pointers (4-byte aligned) and complex sample counts per channel; asynchronous on the handle's stream"""
         p = (C.c_void_p * self.n_ch)(*ptrs)
         n = (C.c_int64 * self.n_ch)(*counts)
-        _check(lib().sdrx_am_feed_dev(self._h, p, n), "sdrx_am_feed_dev")
+        self._call("feed_dev", p, n)
 
     def feed_bank(self, bank: "ChannelizerBank"):
         """channel c takes what the bank's last feed produced for its channel c; ordered on the device, no host sync"""
-        _check(lib().sdrx_am_feed_bank(self._h, bank._h), "sdrx_am_feed_bank")
+        self._call("feed_bank", bank._h)
 
     def read(self, ch: int, cap: int | None = None) -> np.ndarray:
         if cap is None:
             cap = self.last_dev(ch)[1]
         out = np.empty(max(cap, 1), np.int16)
-        n = lib().sdrx_am_read(self._h, ch, out.ctypes.data, cap)
+        n = self._fn("read")(self._h, ch, out.ctypes.data, cap)
         if n < 0:
-            raise SdrxError(f"sdrx_am_read rc={n}: {lib().sdrx_last_error().decode()}")
+            raise SdrxError(f"sdrx_{self._prefix}_read rc={n}: {lib().sdrx_last_error().decode()}")
         return out[:n].copy()
 
     def last_dev(self, ch: int):
         """(device pointer, count) of the last feed's audio of channel ch"""
         p, n = C.c_void_p(), C.c_int64()
-        _check(lib().sdrx_am_last_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_am_last_dev")
+        self._call("last_dev", ch, C.byref(p), C.byref(n))
         return p.value or 0, n.value
 
     def squelch_open(self, ch: int) -> bool:
-        rc = lib().sdrx_am_squelch_open(self._h, ch)
+        rc = self._fn("squelch_open")(self._h, ch)
         if rc < 0:
-            raise SdrxError(f"sdrx_am_squelch_open rc={rc}: {lib().sdrx_last_error().decode()}")
+            raise SdrxError(f"sdrx_{self._prefix}_squelch_open rc={rc}: {lib().sdrx_last_error().decode()}")
         return bool(rc)
+
+    def _design(self, ch: int, third: np.ndarray):
+        nt, inc, lvl = C.c_int32(), C.c_int32(), C.c_float()
+        taps = np.zeros(16 * 128, np.float32)
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, third.ctypes.data, C.byref(inc), C.byref(lvl))
+        return nt.value, taps[: 16 * nt.value].copy(), third, inc.value, lvl.value
+
+
+class WfmDemodBank(_DemodBank):
+    """N wideband-FM demodulators (WFMDemod::feed): int16 I/Q at the channelizer's output rate in, mono qint16 audio out."""
+    _prefix, _cfg = "wfm", WfmCfg
+
+    def levels(self, ch: int, reset: bool = False):
+        """(m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
+        s, p, n = C.c_double(), C.c_double(), C.c_int64()
+        self._call("levels", ch, C.byref(s), C.byref(p), C.byref(n), int(reset))
+        return s.value, p.value, n.value
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], filter spectrum as 2048 floats, NCO increment, squelch level)"""
+        return self._design(ch, np.zeros(2048, np.float32))
+
+
+class AmDemodBank(_DemodBank):
+    """N AM demodulators (AMDemod::feed, envelope mode): int16 I/Q at the channelizer's output rate in, mono qint16 audio out."""
+    _prefix, _cfg = "am", AmCfg
 
     def levels(self, ch: int, reset: bool = False):
         """(m_magsq, m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
         m, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
-        _check(lib().sdrx_am_levels(self._h, ch, C.byref(m), C.byref(s), C.byref(p), C.byref(n), int(reset)), "sdrx_am_levels")
+        self._call("levels", ch, C.byref(m), C.byref(s), C.byref(p), C.byref(n), int(reset))
         return m.value, s.value, p.value, n.value
 
     def design(self, ch: int):
         """(taps per phase, taps [16 * ntaps], the 151 folded Bandpass taps, NCO increment, squelch level)"""
-        nt, inc, lvl = C.c_int32(), C.c_int32(), C.c_float()
-        taps = np.zeros(16 * 128, np.float32)
-        bp = np.zeros(151, np.float32)
-        _check(lib().sdrx_am_get_design(self._h, ch, C.byref(nt), taps.ctypes.data, taps.size, bp.ctypes.data, C.byref(inc), C.byref(lvl)),
-               "sdrx_am_get_design")
-        return nt.value, taps[: 16 * nt.value].copy(), bp, inc.value, lvl.value
-
-    def sync(self):
-        _check(lib().sdrx_am_sync(self._h), "sdrx_am_sync")
-
-    def set_stream(self, hip_stream: int | None):
-        _check(lib().sdrx_am_set_stream(self._h, hip_stream), "sdrx_am_set_stream")
-
-    def get_stream(self) -> int:
-        p = C.c_void_p()
-        _check(lib().sdrx_am_get_stream(self._h, C.byref(p)), "sdrx_am_get_stream")
-        return p.value or 0
-
-    def set_timing(self, on: bool):
-        _check(lib().sdrx_am_set_timing(self._h, int(on)), "sdrx_am_set_timing")
-
-    def get_timing(self, reset: bool = True):
-        ms, n = C.c_double(), C.c_int64()
-        _check(lib().sdrx_am_get_timing(self._h, C.byref(ms), C.byref(n), int(reset)), "sdrx_am_get_timing")
-        return ms.value, n.value
-
-    def last_launch(self) -> dict:
-        name = C.create_string_buffer(128)
-        g, b, l = C.c_int(), C.c_int(), C.c_int()
-        _check(lib().sdrx_am_last_launch(self._h, name, 128, C.byref(g), C.byref(b), C.byref(l)), "last_launch")
-        return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
+        return self._design(ch, np.zeros(151, np.float32))
 
 
 class AudioTailCfg(C.Structure):
@@ -1174,24 +928,17 @@ class AudioTailCfg(C.Structure):
                 ("agc_clamping", C.c_int32), ("agc_threshold", C.c_double)]
 
 
-class AudioTail:
+class AudioTail(_Handle):
     """audio-rate tail of the NFM / SSB demods (squelch / MagAGC / delay line / Bandpass -> qint16) for N channels"""
+    _prefix = "audiotail"
 
     def __init__(self, cfgs, device: int = 0):
         self.n_ch = len(cfgs)
         arr = (AudioTailCfg * self.n_ch)(*cfgs)
-        self._h = C.c_void_p()
-        _check(lib().sdrx_audiotail_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_audiotail_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_audiotail_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device, self.n_ch, arr)
 
     def reset(self):
-        _check(lib().sdrx_audiotail_reset(self._h), "sdrx_audiotail_reset")
+        self._call("reset")
 
     def feed(self, per_channel_cplx):
         ins = [np.ascontiguousarray(x, dtype=np.float32) for x in per_channel_cplx]
@@ -1199,7 +946,7 @@ class AudioTail:
         pi = (C.c_void_p * self.n_ch)(*[x.ctypes.data for x in ins])
         po = (C.c_void_p * self.n_ch)(*[x.ctypes.data for x in outs])
         ns = (C.c_int64 * self.n_ch)(*[x.size // 2 for x in ins])
-        _check(lib().sdrx_audiotail_feed(self._h, pi, ns, po), "sdrx_audiotail_feed")
+        self._call("feed", pi, ns, po)
         return [o[: x.size // 2] for o, x in zip(outs, ins)]
 
 
@@ -1207,8 +954,9 @@ class IirCfg(C.Structure):
     _fields_ = [("order", C.c_int32), ("a", C.c_float * 9), ("b", C.c_float * 9)]
 
 
-class IirBank:
+class IirBank(_Handle):
     """IIRFilter<float, Order> (sdrbase/dsp/iirfilter.h), one filter per channel"""
+    _prefix = "iir"
 
     def __init__(self, specs, device: int = 0):
         """specs: list of (order, a, b)"""
@@ -1218,18 +966,10 @@ class IirBank:
             arr[i].order = o
             for j in range(o + 1):
                 arr[i].a[j] = a[j]; arr[i].b[j] = b[j]
-        self._h = C.c_void_p()
-        _check(lib().sdrx_iir_create(C.byref(self._h), device, self.n_ch, arr), "sdrx_iir_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_iir_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device, self.n_ch, arr)
 
     def reset(self):
-        _check(lib().sdrx_iir_reset(self._h), "sdrx_iir_reset")
+        self._call("reset")
 
     def feed(self, per_channel):
         ins = [np.ascontiguousarray(x, dtype=np.float32) for x in per_channel]
@@ -1237,87 +977,67 @@ class IirBank:
         pi = (C.c_void_p * self.n_ch)(*[x.ctypes.data for x in ins])
         po = (C.c_void_p * self.n_ch)(*[x.ctypes.data for x in outs])
         ns = (C.c_int64 * self.n_ch)(*[x.size for x in ins])
-        _check(lib().sdrx_iir_feed(self._h, pi, ns, po), "sdrx_iir_feed")
+        self._call("feed", pi, ns, po)
         return [o[: x.size] for o, x in zip(outs, ins)]
 
 
-class Decimators24:
+class Decimators24(_Handle, _Sync):
     """Decimators<qint32, qint16, 24, InputBits> of the reference's 24-bit sample build (decimators.h, SDR_RX_SAMPLE_24BIT):
     int16 I/Q in, {int32, int32} samples out; same call contract as Decimators.decimate()."""
+    _prefix = "decim24"
 
     def __init__(self, log2_decim: int, fcpos: int = FC_CEN, input_bits: int = 12, device: int = 0):
-        self._h = C.c_void_p()
-        _check(lib().sdrx_decim24_create(C.byref(self._h), device, log2_decim, fcpos, input_bits), "sdrx_decim24_create")
+        self._open(device, log2_decim, fcpos, input_bits)
         self.log2 = log2_decim
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_decim24_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
-
     def reset(self):
-        _check(lib().sdrx_decim24_reset(self._h), "sdrx_decim24_reset")
+        self._call("reset")
 
     def decimate(self, buf) -> np.ndarray:
         buf = np.ascontiguousarray(buf, dtype=np.int16)
         out = np.empty(2 * ((buf.size // 2) >> self.log2) + 2, np.int32)
         n = C.c_int32()
-        _check(lib().sdrx_decim24_process(self._h, buf.ctypes.data, buf.size, out.ctypes.data, C.byref(n)), "sdrx_decim24_process")
+        self._call("process", buf.ctypes.data, buf.size, out.ctypes.data, C.byref(n))
         return out[: 2 * n.value]
 
 
     def decimate_dev(self, d_iq: int, n_cplx: int, d_out: int) -> int:
         """device pointers (e.g. torch tensor .data_ptr()); asynchronous, sync() waits; returns the samples produced"""
         n = C.c_int64()
-        _check(lib().sdrx_decim24_process_dev(self._h, d_iq, n_cplx, d_out, C.byref(n)), "sdrx_decim24_process_dev")
+        self._call("process_dev", d_iq, n_cplx, d_out, C.byref(n))
         return n.value
 
-    def sync(self):
-        _check(lib().sdrx_decim24_sync(self._h), "sdrx_decim24_sync")
 
-
-class ChannelizerBank24:
+class ChannelizerBank24(_Handle, _Sync):
     """N DownChannelizers (downchannelizer.cpp) of the 24-bit sample build on one {int32, int32} stream."""
+    _prefix = "chan24_bank"
 
     def __init__(self, in_rate: int, req_rates, req_fcs, device: int = 0):
         rr = np.ascontiguousarray(req_rates, dtype=np.int32); rf = np.ascontiguousarray(req_fcs, dtype=np.int32)
         self.n_ch = rr.size
-        self._h = C.c_void_p()
-        _check(lib().sdrx_chan24_bank_create(C.byref(self._h), device, in_rate, self.n_ch, rr.ctypes.data, rf.ctypes.data), "sdrx_chan24_bank_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_chan24_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device, in_rate, self.n_ch, rr.ctypes.data, rf.ctypes.data)
 
     def reset(self):
-        _check(lib().sdrx_chan24_bank_reset(self._h), "sdrx_chan24_bank_reset")
+        self._call("reset")
 
     def info(self, ch: int):
         n, r, f = C.c_int32(), C.c_int32(), C.c_int32()
         modes = np.zeros(40, np.uint8)
-        _check(lib().sdrx_chan24_bank_info(self._h, ch, C.byref(n), modes.ctypes.data, C.byref(r), C.byref(f)), "sdrx_chan24_bank_info")
+        self._call("info", ch, C.byref(n), modes.ctypes.data, C.byref(r), C.byref(f))
         return modes[: n.value].copy(), r.value, f.value
 
     def feed_dev(self, d_iq: int, n_cplx: int):
-        _check(lib().sdrx_chan24_bank_feed_dev(self._h, d_iq, n_cplx), "sdrx_chan24_bank_feed_dev")
+        self._call("feed_dev", d_iq, n_cplx)
 
     def out_dev(self, ch: int):
         p, n = C.c_void_p(), C.c_int64()
-        _check(lib().sdrx_chan24_bank_out_dev(self._h, ch, C.byref(p), C.byref(n)), "sdrx_chan24_bank_out_dev")
+        self._call("out_dev", ch, C.byref(p), C.byref(n))
         return p.value, n.value
-
-    def sync(self):
-        _check(lib().sdrx_chan24_bank_sync(self._h), "sdrx_chan24_bank_sync")
 
     def feed(self, iq):
         """iq: interleaved int32 I/Q; returns the per-channel outputs of this feed"""
         iq = np.ascontiguousarray(iq, dtype=np.int32)
-        _check(lib().sdrx_chan24_bank_feed(self._h, iq.ctypes.data, iq.size // 2), "sdrx_chan24_bank_feed")
+        self._call("feed", iq.ctypes.data, iq.size // 2)
         outs = []
         for c in range(self.n_ch):
             out = np.empty(iq.size + 2, np.int32)
@@ -1328,49 +1048,35 @@ class ChannelizerBank24:
         return outs
 
 
-class IqImbalance:
+class IqImbalance(_Handle):
     """DSPDeviceSourceEngine::iqCorrections(begin, end, true) (DC + I/Q imbalance, float flavour) for N device streams."""
+    _prefix = "iqimb"
 
     def __init__(self, n_streams: int, device: int = 0):
         self.n = n_streams
-        self._h = C.c_void_p()
-        _check(lib().sdrx_iqimb_create(C.byref(self._h), device, n_streams), "sdrx_iqimb_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_iqimb_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(device, n_streams)
 
     def reset(self):
-        _check(lib().sdrx_iqimb_reset(self._h), "sdrx_iqimb_reset")
+        self._call("reset")
 
     def process(self, per_stream_iq):
         """in place on copies: returns the corrected int16 I/Q per stream"""
         bufs = [_i16(x).copy() for x in per_stream_iq]
         ptrs = (C.c_void_p * self.n)(*[b.ctypes.data for b in bufs])
         ns = (C.c_int64 * self.n)(*[b.size // 2 for b in bufs])
-        _check(lib().sdrx_iqimb_process(self._h, ptrs, ns), "sdrx_iqimb_process")
+        self._call("process", ptrs, ns)
         return bufs
 
 
-class SampleSinkFifo:
+class SampleSinkFifo(_Handle):
     """sdrbase/dsp/samplesinkfifo.{h,cpp}: write / read / readBegin / readCommit."""
+    _prefix = "fifo"
 
     def __init__(self, size: int):
-        self._h = C.c_void_p()
-        _check(lib().sdrx_fifo_create(C.byref(self._h), size), "sdrx_fifo_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sdrx_fifo_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = _del
+        self._open(size)
 
     def set_size(self, size: int):
-        _check(lib().sdrx_fifo_set_size(self._h, size), "sdrx_fifo_set_size")
+        self._call("set_size", size)
 
     size = property(lambda self: lib().sdrx_fifo_size(self._h))
     fill = property(lambda self: lib().sdrx_fifo_fill(self._h))

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "am_scan.hpp"
+#include "dsp_device.hpp"
 
 namespace sdrx {
 
@@ -142,12 +143,6 @@ void am_psum_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs, in
     if (chain) { if (which) ch[c].agc_sum_next = acc; else ch[c].total_next = acc; }
 }
 
-__device__ __forceinline__ WfmClamp am_shfl_up(WfmClamp m, int o)
-{
-    WfmClamp r; r.a = __shfl_up(m.a, o, 64); r.lo = __shfl_up(m.lo, o, 64); r.hi = __shfl_up(m.hi, o, 64);
-    return r;
-}
-
 // ---- 3. one workgroup per channel, 1024 samples per trip: the squelch counter as a scan of clamp maps, open and fed
 // flags, their prefix counts (the compaction indices), the fed values, then the AGC terms; level accumulators
 __global__ __launch_bounds__(256)
@@ -173,16 +168,16 @@ void am_gate_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
             up[k] = false;
             if (i0 + k < n) { up[k] = am_up(b.tot[i0 + k], level); m = wfm_compose(m, wfm_step(up[k], cap)); }
         }
-        WfmClamp incl = m;
+        WfmClamp incl = m;                                  // wfm_wave_scan, written out: the call compiles to other code here
         for (int o = 1; o < 64; o *= 2) {
-            const WfmClamp t = am_shfl_up(incl, o);
+            const WfmClamp t = wfm_shfl_up(incl, o);
             if (lane >= o) incl = wfm_compose(t, incl);
         }
         if (lane == 63) wmap[w] = incl;
         __syncthreads();
         WfmClamp pre = wfm_identity(cap);
         for (int q = 0; q < w; q++) pre = wfm_compose(pre, wmap[q]);
-        WfmClamp ex = am_shfl_up(incl, 1);
+        WfmClamp ex = wfm_shfl_up(incl, 1);
         if (lane == 0) ex = wfm_identity(cap);
         int st = wfm_apply(wfm_compose(pre, ex), carry);
         int stv[4]; bool act[4], fed[4]; float rr[4];
@@ -268,12 +263,6 @@ void am_demod_kernel(const AmChan* __restrict__ ch, const AmBufs* __restrict__ b
     b.dem[a] = (r - g) / g;
 }
 
-__device__ __forceinline__ int am_to_q16(float v)
-{
-    // (qint16) of a float as x86-64 does it: cvttss2si (0x80000000 when out of range or NaN), then the low 16 bits
-    const int i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u;
-    return (int)(short)i;
-}
 __device__ __forceinline__ float am_smootherstep(float x)                   // util/stepfunctions.h:23-36
 {
     if (x == 1.0f) return 1.0f; else if (x == 0.0f) return 0.0f;
@@ -308,7 +297,7 @@ void am_out_kernel(const AmChan* __restrict__ ch, const AmBufs* __restrict__ buf
             demod /= 301.0f;
         }
         const float attack = ((float)b.cnt[i] - s.att) / s.att;
-        q = am_to_q16(demod * am_smootherstep(attack) * s.gain * s.volume);
+        q = sdrx_to_q16(demod * am_smootherstep(attack) * s.gain * s.volume);
     }
     b.audio[i] = (int16_t)q;
 }

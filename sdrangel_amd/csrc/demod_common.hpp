@@ -1,0 +1,86 @@
+// host code the demodulator banks share (sdrx_wfm.hip, sdrx_am.hip): input staging and checks, the hand-over from a
+// channelizer bank, one channel's device state, the per-feed pointer table.  `who` is the entry point named in the error text.
+#pragma once
+#include "sdrx_common.hpp"
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace sdrx {
+
+inline int demod_check_lengths(int n_ch, const int64_t* n_per_ch, const char* who)
+{
+    for (int c = 0; c < n_ch; c++)
+        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff) { set_error(std::string(who) + ": bad length"); return SDRX_EINVAL; }
+    return SDRX_OK;
+}
+
+inline int demod_check_dev_pointers(int n_ch, const int16_t* const* d_iq, const int64_t* n_per_ch, const char* who)
+{
+    for (int c = 0; c < n_ch; c++)
+        if (n_per_ch[c] > 0 && (!d_iq[c] || (reinterpret_cast<uintptr_t>(d_iq[c]) & 3u))) {
+            set_error(std::string(who) + ": null or misaligned channel pointer"); return SDRX_EINVAL;
+        }
+    return SDRX_OK;
+}
+
+// host-pointer feed: once the stream is idle, channel c's samples go to ch[c].stage_in on it; d[c] is that device copy
+template <class Host>
+int demod_stage_inputs(std::vector<Host>& ch, hipStream_t stream, const int16_t* const* iq, const int64_t* n_per_ch, const char* who,
+                       std::vector<const int16_t*>& d)
+{
+    SDRX_HIP(hipStreamSynchronize(stream));
+    d.resize(ch.size());
+    for (size_t c = 0; c < ch.size(); c++) {
+        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff || (n_per_ch[c] > 0 && !iq[c])) { set_error(std::string(who) + ": bad length or null channel pointer"); return SDRX_EINVAL; }
+        DevBuf& st = ch[c].stage_in;
+        int rc = st.reserve((size_t)std::max<int64_t>(n_per_ch[c], 1) * 4); if (rc) return rc;
+        if (n_per_ch[c] > 0) SDRX_HIP(hipMemcpyAsync(st.p, iq[c], (size_t)n_per_ch[c] * 4, hipMemcpyHostToDevice, stream));
+        d[c] = static_cast<const int16_t*>(st.p);
+    }
+    return SDRX_OK;
+}
+
+// what the bank's last feed produced for its channels 0 .. n_ch-1
+inline int demod_gather_bank(sdrx_chan_bank_t* bank, int n_ch, const char* who, std::vector<const int16_t*>& d, std::vector<int64_t>& n)
+{
+    d.resize((size_t)n_ch); n.resize((size_t)n_ch);
+    for (int c = 0; c < n_ch; c++) {
+        int rc = sdrx_chan_bank_last_dev(bank, c, &d[(size_t)c], &n[(size_t)c]);
+        if (rc) { set_error(std::string(who) + ": the bank has fewer channels than the demodulator bank"); return rc; }
+    }
+    return SDRX_OK;
+}
+
+template <class Chan>
+int demod_fetch_state(const HandleCore& core, const Chan* d_chan, int32_t c, Chan* s)
+{
+    SDRX_HIP(hipSetDevice(core.device));
+    SDRX_HIP(hipMemcpyAsync(s, d_chan + c, sizeof *s, hipMemcpyDeviceToHost, core.stream));
+    SDRX_HIP(hipStreamSynchronize(core.stream));
+    return SDRX_OK;
+}
+
+// getMagSqLevels' reset: the sum and the peak (doubles) and the count (long long) of one channel's state back to 0
+template <class Chan>
+int demod_zero_levels(const HandleCore& core, Chan* chan, size_t sum_off, size_t peak_off, size_t count_off)
+{
+    char* base = reinterpret_cast<char*>(chan);
+    SDRX_HIP(hipMemsetAsync(base + sum_off, 0, sizeof(double), core.stream));
+    SDRX_HIP(hipMemsetAsync(base + peak_off, 0, sizeof(double), core.stream));
+    SDRX_HIP(hipMemsetAsync(base + count_off, 0, sizeof(long long), core.stream));
+    SDRX_HIP(hipStreamSynchronize(core.stream));
+    return SDRX_OK;
+}
+
+// the pinned per-feed table goes to the device in one async copy; `ev` behind it is what the next feed waits for
+// (hipEventSynchronize) before it rewrites the table
+template <class Bufs>
+int demod_upload_bufs(Bufs* d_bufs, const Bufs* h_bufs, int n_ch, hipEvent_t ev, hipStream_t stream)
+{
+    SDRX_HIP(hipMemcpyAsync(d_bufs, h_bufs, (size_t)n_ch * sizeof(Bufs), hipMemcpyHostToDevice, stream));
+    SDRX_HIP(hipEventRecord(ev, stream));
+    return SDRX_OK;
+}
+
+} // namespace sdrx

@@ -6,6 +6,7 @@
 #include "sdrx_common.hpp"
 #include "am_kernels.hpp"
 #include "backend_view.hpp"
+#include "demod_common.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -59,8 +60,7 @@ void bandpass_design(double rate, double f1, double f2, float* t)
 } // namespace
 
 struct sdrx_am {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
     int n_ch = 0;
     std::vector<sdrx_am_cfg> cfg;
     std::vector<sdrx_backend_cfg> be_cfg;
@@ -73,9 +73,6 @@ struct sdrx_am {
     hipEvent_t bufs_ev = nullptr;
     float* d_bp = nullptr;
     std::vector<float> bp_all;
-    EventTimer timer;
-    char last_name[64] = "";
-    int last_grid = 0, last_block = 0, last_lds = 0;
 };
 
 static int validate(int32_t n_ch, const sdrx_am_cfg* cfg)
@@ -106,7 +103,7 @@ static int ensure_capacity(sdrx_am* b, int c, int64_t n_in)
     // every audio sample consumes at least one input (step >= 1): at most `cap` samples per feed; nothing here carries state
     const size_t n = (size_t)cap + 16, nblk = n / 256 + 1;
     const size_t bytes = 4 * al(n * 4) + al(n * 4) + 5 * al(n * 8) + al(n * 4) + al(n * 2) + al(nblk * 8) + al(nblk * 4);
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     int rc = h.work.reserve(bytes); if (rc) return rc;
     h.cap_in = cap;
     return SDRX_OK;
@@ -114,7 +111,7 @@ static int ensure_capacity(sdrx_am* b, int c, int64_t n_in)
 
 static int upload_fresh_state(sdrx_am* b)
 {
-    SDRX_HIP(hipMemcpyAsync(b->d_chan, b->h_chan.data(), (size_t)b->n_ch * sizeof(AmChan), hipMemcpyHostToDevice, b->stream));
+    SDRX_HIP(hipMemcpyAsync(b->d_chan, b->h_chan.data(), (size_t)b->n_ch * sizeof(AmChan), hipMemcpyHostToDevice, b->core.stream));
     std::vector<char> img;
     for (int c = 0; c < b->n_ch; c++) {
         AmHost& h = b->ch[(size_t)c];
@@ -124,8 +121,8 @@ static int upload_fresh_state(sdrx_am* b)
         // DoubleBufferFIFO does not clear its array, see sdrx.h)
         double* v = reinterpret_cast<double*>(img.data() + al(AM_MA * 4) + al((size_t)s.D * 4));
         for (int i = 0; i < s.H; i++) v[i] = am_agc_initial();
-        SDRX_HIP(hipMemcpyAsync(h.hist, img.data(), h.hist_set, hipMemcpyHostToDevice, b->stream));
-        SDRX_HIP(hipStreamSynchronize(b->stream));        // img is reused
+        SDRX_HIP(hipMemcpyAsync(h.hist, img.data(), h.hist_set, hipMemcpyHostToDevice, b->core.stream));
+        SDRX_HIP(hipStreamSynchronize(b->core.stream));        // img is reused
         h.cur = 0;
     }
     return SDRX_OK;
@@ -133,8 +130,8 @@ static int upload_fresh_state(sdrx_am* b)
 
 static int make_front(sdrx_am* b)
 {
-    int rc = sdrx_backend_create(&b->front, b->device, b->n_ch, b->be_cfg.data()); if (rc) return rc;
-    return backend_set_stream(b->front, b->stream);
+    int rc = sdrx_backend_create(&b->front, b->core.device, b->n_ch, b->be_cfg.data()); if (rc) return rc;
+    return backend_set_stream(b->front, b->core.stream);
 }
 
 extern "C" {
@@ -142,8 +139,8 @@ extern "C" {
 int sdrx_am_destroy(sdrx_am_t* b)
 {
     if (!b) return SDRX_OK;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    (void)hipSetDevice(b->core.device);
+    if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
     if (b->front) (void)sdrx_backend_destroy(b->front);
     for (auto& h : b->ch) {
         h.work.release(); h.stage_in.release();
@@ -154,8 +151,7 @@ int sdrx_am_destroy(sdrx_am_t* b)
     if (b->h_bufs) (void)hipHostFree(b->h_bufs);
     if (b->bufs_ev) (void)hipEventDestroy(b->bufs_ev);
     if (b->d_bp) (void)hipFree(b->d_bp);
-    b->timer.release();
-    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+    b->core.close();
     delete b;
     return SDRX_OK;
 }
@@ -165,19 +161,15 @@ int sdrx_am_create(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg*
     if (!out) { set_error("sdrx_am_create: null out"); return SDRX_EINVAL; }
     *out = nullptr;
     int rc = validate(n_ch, cfg); if (rc) return rc;
-    rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_am* b = new (std::nothrow) sdrx_am;
     if (!b) return SDRX_ENOMEM;
-    b->device = device; b->n_ch = n_ch;
-    hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete b; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-    b->stream = b->own_stream;
+    rc = b->core.open(device);
+    if (rc) { delete b; return rc; }
+    b->n_ch = n_ch;
     b->cfg.assign(cfg, cfg + n_ch);
     b->ch.resize((size_t)n_ch); b->h_chan.resize((size_t)n_ch); b->be_cfg.resize((size_t)n_ch);
     b->bp_all.assign((size_t)n_ch * (AM_BP_H + 1), 0.0f);
 
-#define AM_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = hip_fail(e_, #call, __FILE__, __LINE__); sdrx_am_destroy(b); return r_; } } while (0)
     for (int c = 0; c < n_ch; c++) {
         const sdrx_am_cfg& k = cfg[c];
         sdrx_backend_cfg& f = b->be_cfg[(size_t)c];
@@ -199,16 +191,15 @@ int sdrx_am_create(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg*
         bandpass_design((double)k.audio_rate, 300.0, (double)(k.rf_bandwidth / 2.0f), &b->bp_all[(size_t)s.bp_off]);
         AmHost& h = b->ch[(size_t)c];
         h.hist_set = al(AM_MA * 4) + al((size_t)s.D * 4) + al((size_t)s.H * 8) + al(AM_BP_HIST * 4);
-        AM_TRY(hipMalloc(reinterpret_cast<void**>(&h.hist), 2 * h.hist_set));
+        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.hist), 2 * h.hist_set), sdrx_am_destroy(b));
     }
-    AM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_bp), b->bp_all.size() * 4));
-    AM_TRY(hipMemcpy(b->d_bp, b->bp_all.data(), b->bp_all.size() * 4, hipMemcpyHostToDevice));
-    AM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(AmChan)));
-    AM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(AmBufs)));
-    AM_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(AmBufs), hipHostMallocDefault));
-    AM_TRY(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming));
-    AM_TRY(hipEventRecord(b->bufs_ev, b->stream));
-#undef AM_TRY
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bp), b->bp_all.size() * 4), sdrx_am_destroy(b));
+    SDRX_HIP_ELSE(hipMemcpy(b->d_bp, b->bp_all.data(), b->bp_all.size() * 4, hipMemcpyHostToDevice), sdrx_am_destroy(b));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(AmChan)), sdrx_am_destroy(b));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(AmBufs)), sdrx_am_destroy(b));
+    SDRX_HIP_ELSE(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(AmBufs), hipHostMallocDefault), sdrx_am_destroy(b));
+    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming), sdrx_am_destroy(b));
+    SDRX_HIP_ELSE(hipEventRecord(b->bufs_ev, b->core.stream), sdrx_am_destroy(b));
     rc = make_front(b);
     if (!rc) rc = upload_fresh_state(b);
     if (rc) { sdrx_am_destroy(b); return rc; }
@@ -219,8 +210,8 @@ int sdrx_am_create(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg*
 int sdrx_am_reset(sdrx_am_t* b)
 {
     if (!b) { set_error("sdrx_am_reset: null handle"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     // the front has no reset of its own: a fresh one with the same design
     if (b->front) { (void)sdrx_backend_destroy(b->front); b->front = nullptr; }
     int rc = make_front(b); if (rc) return rc;
@@ -262,90 +253,62 @@ static int tail_common(sdrx_am* b, const int64_t* n_per_ch)
         u.audio = reinterpret_cast<int16_t*>(take(n * 2));
         u.blk_sum = reinterpret_cast<double*>(take(nblk * 8)); u.blk_peak = reinterpret_cast<float*>(take(nblk * 4));
     }
-    SDRX_HIP(hipMemcpyAsync(b->d_bufs, b->h_bufs, (size_t)b->n_ch * sizeof(AmBufs), hipMemcpyHostToDevice, b->stream));
-    SDRX_HIP(hipEventRecord(b->bufs_ev, b->stream));
+    int rc = demod_upload_bufs(b->d_bufs, b->h_bufs, b->n_ch, b->bufs_ev, b->core.stream); if (rc) return rc;
     const unsigned nc = (unsigned)b->n_ch, gp = (nc + AM_PS_CH - 1) / AM_PS_CH, gx = (unsigned)std::max<int64_t>(1, (bound + 255) / 256);
-    hipLaunchKernelGGL(am_level_kernel, dim3(gx, nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+    hipLaunchKernelGGL(am_level_kernel, dim3(gx, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->n_ch, 0);
+    hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch, 0);
     SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_gate_kernel, dim3(nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+    hipLaunchKernelGGL(am_gate_kernel, dim3(nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->n_ch, 1);
+    hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch, 1);
     SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_demod_kernel, dim3(gx, nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+    hipLaunchKernelGGL(am_demod_kernel, dim3(gx, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_out_kernel, dim3(gx, nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs, b->d_bp);
+    hipLaunchKernelGGL(am_out_kernel, dim3(gx, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_bp);
     SDRX_HIP(hipGetLastError());
-    snprintf(b->last_name, sizeof(b->last_name), "%s", "am_out_kernel");
-    b->last_grid = (int)(gx * nc); b->last_block = 256; b->last_lds = (int)((AM_BP_H + 1) * sizeof(float));
-    hipLaunchKernelGGL(am_carry_kernel, dim3(nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+    b->core.note_launch("am_out_kernel", (int)(gx * nc), 256, (int)((AM_BP_H + 1) * sizeof(float)));
+    hipLaunchKernelGGL(am_carry_kernel, dim3(nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
     for (auto& h : b->ch) h.cur ^= 1;
-    return SDRX_OK;
-}
-
-static int check_lengths(const sdrx_am* b, const int64_t* n_per_ch, const char* who)
-{
-    for (int c = 0; c < b->n_ch; c++)
-        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff) { set_error(std::string(who) + ": bad length"); return SDRX_EINVAL; }
     return SDRX_OK;
 }
 
 int sdrx_am_feed_dev(sdrx_am_t* b, const int16_t* const* d_iq, const int64_t* n_per_ch)
 {
     if (!b || !d_iq || !n_per_ch) { set_error("sdrx_am_feed_dev: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
-    int rc = check_lengths(b, n_per_ch, "sdrx_am_feed_dev"); if (rc) return rc;
-    for (int c = 0; c < b->n_ch; c++)
-        if (n_per_ch[c] > 0 && (!d_iq[c] || (reinterpret_cast<uintptr_t>(d_iq[c]) & 3u))) { set_error("sdrx_am_feed_dev: null or misaligned channel pointer"); return SDRX_EINVAL; }
-    rc = b->timer.begin(b->stream); if (rc) return rc;
+    SDRX_HIP(hipSetDevice(b->core.device));
+    int rc = demod_check_lengths(b->n_ch, n_per_ch, "sdrx_am_feed_dev"); if (rc) return rc;
+    rc = demod_check_dev_pointers(b->n_ch, d_iq, n_per_ch, "sdrx_am_feed_dev"); if (rc) return rc;
+    rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
     rc = sdrx_backend_feed_dev(b->front, d_iq, n_per_ch); if (rc) return rc;
     rc = tail_common(b, n_per_ch); if (rc) return rc;
-    return b->timer.end(b->stream);
+    return b->core.timer.end(b->core.stream);
 }
 
 int sdrx_am_feed_bank(sdrx_am_t* b, sdrx_chan_bank_t* bank)
 {
     if (!b || !bank) { set_error("sdrx_am_feed_bank: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
-    std::vector<int64_t> n((size_t)b->n_ch);
-    for (int c = 0; c < b->n_ch; c++) {
-        const int16_t* d = nullptr;
-        int rc = sdrx_chan_bank_last_dev(bank, c, &d, &n[(size_t)c]);
-        if (rc) { set_error("sdrx_am_feed_bank: the bank has fewer channels than the demodulator bank"); return rc; }
-    }
-    int rc = check_lengths(b, n.data(), "sdrx_am_feed_bank"); if (rc) return rc;
-    rc = b->timer.begin(b->stream); if (rc) return rc;
+    SDRX_HIP(hipSetDevice(b->core.device));
+    std::vector<const int16_t*> d;                          // the front takes them from the bank itself
+    std::vector<int64_t> n;
+    int rc = demod_gather_bank(bank, b->n_ch, "sdrx_am_feed_bank", d, n); if (rc) return rc;
+    rc = demod_check_lengths(b->n_ch, n.data(), "sdrx_am_feed_bank"); if (rc) return rc;
+    rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
     // the front orders its readers against the bank's stream (sdrx_backend_feed_bank); the tail reads the front's output only
     rc = sdrx_backend_feed_bank(b->front, bank); if (rc) return rc;
     rc = tail_common(b, n.data()); if (rc) return rc;
-    return b->timer.end(b->stream);
+    return b->core.timer.end(b->core.stream);
 }
 
 int sdrx_am_feed(sdrx_am_t* b, const int16_t* const* iq, const int64_t* n_per_ch)
 {
     if (!b || !iq || !n_per_ch) { set_error("sdrx_am_feed: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    std::vector<const int16_t*> d((size_t)b->n_ch);
-    for (int c = 0; c < b->n_ch; c++) {
-        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff || (n_per_ch[c] > 0 && !iq[c])) { set_error("sdrx_am_feed: bad length or null channel pointer"); return SDRX_EINVAL; }
-        AmHost& h = b->ch[(size_t)c];
-        int rc = h.stage_in.reserve((size_t)std::max<int64_t>(n_per_ch[c], 1) * 4); if (rc) return rc;
-        if (n_per_ch[c] > 0) SDRX_HIP(hipMemcpyAsync(h.stage_in.p, iq[c], (size_t)n_per_ch[c] * 4, hipMemcpyHostToDevice, b->stream));
-        d[(size_t)c] = static_cast<const int16_t*>(h.stage_in.p);
-    }
-    int rc = sdrx_am_feed_dev(b, d.data(), n_per_ch); if (rc) return rc;
-    SDRX_HIP(hipStreamSynchronize(b->stream));            // the caller's buffers are free again on return
-    return SDRX_OK;
-}
-
-static int fetch_state(sdrx_am* b, int32_t c, AmChan* s)
-{
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipMemcpyAsync(s, b->d_chan + c, sizeof *s, hipMemcpyDeviceToHost, b->stream));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipSetDevice(b->core.device));
+    std::vector<const int16_t*> d;
+    int rc = demod_stage_inputs(b->ch, b->core.stream, iq, n_per_ch, "sdrx_am_feed", d); if (rc) return rc;
+    rc = sdrx_am_feed_dev(b, d.data(), n_per_ch); if (rc) return rc;
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));            // the caller's buffers are free again on return
     return SDRX_OK;
 }
 
@@ -353,7 +316,7 @@ int64_t sdrx_am_read(sdrx_am_t* b, int32_t c, int16_t* audio, int64_t cap)
 {
     if (!b || c < 0 || c >= b->n_ch || cap < 0 || (cap > 0 && !audio)) { set_error("sdrx_am_read: bad argument"); return SDRX_EINVAL; }
     AmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     const int64_t n = std::min<int64_t>(s.n, cap);
     if (n == 0) return 0;
     SDRX_HIP(hipMemcpy(audio, b->h_bufs[c].audio, (size_t)n * 2, hipMemcpyDeviceToHost));
@@ -364,7 +327,7 @@ int sdrx_am_last_dev(sdrx_am_t* b, int32_t c, const int16_t** d_audio, int64_t* 
 {
     if (!b || c < 0 || c >= b->n_ch || !d_audio || !n) { set_error("sdrx_am_last_dev: bad argument"); return SDRX_EINVAL; }
     AmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     *d_audio = s.n > 0 ? b->h_bufs[c].audio : static_cast<const int16_t*>(b->ch[(size_t)c].work.p);
     *n = s.n;
     return SDRX_OK;
@@ -374,7 +337,7 @@ int sdrx_am_squelch_open(sdrx_am_t* b, int32_t c)
 {
     if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_am_squelch_open: bad argument"); return SDRX_EINVAL; }
     AmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     return s.sq_open;
 }
 
@@ -382,19 +345,13 @@ int sdrx_am_levels(sdrx_am_t* b, int32_t c, double* magsq, double* sum, double* 
 {
     if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_am_levels: bad argument"); return SDRX_EINVAL; }
     AmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     if (magsq) *magsq = s.magsq;
     if (sum) *sum = s.magsq_sum;
     if (peak) *peak = s.magsq_peak;
     if (count) *count = s.magsq_count;
-    if (reset) {                                          // getMagSqLevels: sum, peak and count back to 0; m_magsq stays
-        char* base = reinterpret_cast<char*>(b->d_chan + c);
-        SDRX_HIP(hipMemsetAsync(base + offsetof(AmChan, magsq_sum), 0, sizeof(double), b->stream));
-        SDRX_HIP(hipMemsetAsync(base + offsetof(AmChan, magsq_peak), 0, sizeof(double), b->stream));
-        SDRX_HIP(hipMemsetAsync(base + offsetof(AmChan, magsq_count), 0, sizeof(long long), b->stream));
-        SDRX_HIP(hipStreamSynchronize(b->stream));
-    }
-    return SDRX_OK;
+    if (!reset) return SDRX_OK;                           // getMagSqLevels: sum, peak and count back to 0; m_magsq stays
+    return demod_zero_levels(b->core, b->d_chan + c, offsetof(AmChan, magsq_sum), offsetof(AmChan, magsq_peak), offsetof(AmChan, magsq_count));
 }
 
 int sdrx_am_get_design(sdrx_am_t* b, int32_t c, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
@@ -407,56 +364,21 @@ int sdrx_am_get_design(sdrx_am_t* b, int32_t c, int32_t* ntaps_per_phase, float*
     return SDRX_OK;
 }
 
-int sdrx_am_sync(sdrx_am_t* b)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    return SDRX_OK;
-}
+int sdrx_am_sync(sdrx_am_t* b) { return b ? b->core.sync() : SDRX_EINVAL; }
 
 int sdrx_am_set_stream(sdrx_am_t* b, void* hip_stream)
 {
     if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    b->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : b->own_stream;
-    return backend_set_stream(b->front, b->stream);
+    int rc = b->core.set_stream(hip_stream); if (rc) return rc;
+    return backend_set_stream(b->front, b->core.stream);      // the front launches on the same stream
 }
 
-int sdrx_am_get_stream(sdrx_am_t* b, void** hip_stream)
-{
-    if (!b || !hip_stream) return SDRX_EINVAL;
-    *hip_stream = b->stream;
-    return SDRX_OK;
-}
+int sdrx_am_get_stream(sdrx_am_t* b, void** hip_stream) { return b ? b->core.get_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_am_set_timing(sdrx_am_t* b, int enabled)
-{
-    if (!b) return SDRX_EINVAL;
-    b->timer.enabled = enabled != 0;
-    return SDRX_OK;
-}
+int sdrx_am_set_timing(sdrx_am_t* b, int enabled) { return b ? b->core.set_timing(enabled) : SDRX_EINVAL; }
 
-int sdrx_am_get_timing(sdrx_am_t* b, double* total_ms, int64_t* feeds, int reset)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    int rc = b->timer.collect(b->stream); if (rc) return rc;
-    if (total_ms) *total_ms = b->timer.total_ms;
-    if (feeds) *feeds = b->timer.count;
-    if (reset) { b->timer.total_ms = 0; b->timer.count = 0; }
-    return SDRX_OK;
-}
+int sdrx_am_get_timing(sdrx_am_t* b, double* total_ms, int64_t* feeds, int reset) { return b ? b->core.get_timing(total_ms, feeds, reset) : SDRX_EINVAL; }
 
-int sdrx_am_last_launch(const sdrx_am_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes)
-{
-    if (!b) return SDRX_EINVAL;
-    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", b->last_name);
-    if (grid) *grid = b->last_grid;
-    if (block) *block = b->last_block;
-    if (lds_bytes) *lds_bytes = b->last_lds;
-    return SDRX_OK;
-}
+int sdrx_am_last_launch(const sdrx_am_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes) { return b ? b->core.last_launch(kernel_name, name_cap, grid, block, lds_bytes) : SDRX_EINVAL; }
 
 } // extern "C"

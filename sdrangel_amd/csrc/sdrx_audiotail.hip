@@ -10,6 +10,7 @@
 // (the FIR ring and taps of the NFM flavour sit in LDS, lane-interleaved).  256 channels x 1 s of 48 kS/s audio is ~12 M
 // lane-steps: milliseconds, which is why "stays on the host" (round 1) was a choice, not a constraint.
 #include "sdrx_common.hpp"
+#include "dsp_device.hpp"
 #include <new>
 #include <vector>
 #include <cmath>
@@ -41,13 +42,6 @@ struct AtChan {                              // everything a channel carries bet
 };
 
 struct AtJob { const float* in; int16_t* out; long n; };
-
-__device__ __forceinline__ int to_q16(float v)
-{
-    // (qint16) of a float as x86-64 does it: cvttss2si (0x80000000 when out of range or NaN), then the low 16 bits
-    const int i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u;
-    return (int)(short)i;
-}
 
 __device__ __forceinline__ float at_atan2_approx2(float y, float x)      // phasediscri.h:172-197
 {
@@ -120,7 +114,7 @@ void audiotail_kernel(AtChan* __restrict__ chans, const AtJob* __restrict__ jobs
                     b = b > 0 ? b - 1 : AT_TAPS - 1;
                 }
                 acc += s_ring[a * AT_LANES + lane] * s_taps[AT_H * AT_LANES + lane];
-                y16 = to_q16(acc * vol);
+                y16 = sdrx_to_q16(acc * vol);
             }
             jb.out[k] = (int16_t)y16;
         }
@@ -166,7 +160,7 @@ void audiotail_kernel(AtChan* __restrict__ chans, const AtJob* __restrict__ jobs
             const float sv = cnt < sdd ? at_smootherstep((float)(step_up * sd)) : at_smootherstep((float)(step_down * sd));   // getStepValue
             const float zr = dr * sv, zi = di * sv;
             const float demod = (float)((double)(zr + zi) * 0.7);
-            jb.out[k] = (int16_t)to_q16(demod * vol);
+            jb.out[k] = (int16_t)sdrx_to_q16(demod * vol);
         }
         s.u0 = u0; s.sum = sum; s.hist_idx = hi; s.step_up = step_up; s.step_down = step_down; s.gate_counter = gc; s.acount = cnt;
         s.dl_w = dl_w; s.dl_cur = dl_cur;
@@ -201,8 +195,8 @@ void bandpass_taps(double rate, double f1, double f2, float* t)
 } // namespace
 
 struct sdrx_audiotail {
-    int device = 0, n_ch = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
+    int n_ch = 0;
     std::vector<sdrx_audiotail_cfg> cfg;
     AtChan* d_chan = nullptr;
     std::vector<void*> bufs;                 // per-channel delay lines / histories
@@ -226,7 +220,7 @@ static int audiotail_init_state(sdrx_audiotail* h)
             bandpass_taps((double)k.audio_rate, 300.0, (double)k.af_bandwidth, s.taps); // m_bandpass.create(301, rate, 300.0, bw) (:428-429)
             s.ring_p = 0;
             s.dl = static_cast<float*>(h->bufs[bi++]);
-            SDRX_HIP(hipMemsetAsync(s.dl, 0, sizeof(float) * 2 * NFM_DL, h->stream));
+            SDRX_HIP(hipMemsetAsync(s.dl, 0, sizeof(float) * 2 * NFM_DL, h->core.stream));
         } else {
             const float Rf = (float)3276.8;                                            // MagAGC::resize(n, n / 2, Real agcTarget)
             s.R = (double)Rf; s.u0 = 1.0;
@@ -236,12 +230,12 @@ static int audiotail_init_state(sdrx_audiotail* h)
             s.clamping = k.agc_clamping; s.clamp_max = 32768.0 / 100.0; s.agc_active = k.agc_active;
             s.dl = static_cast<float*>(h->bufs[bi++]);
             s.hist = static_cast<double*>(h->bufs[bi++]);
-            SDRX_HIP(hipMemsetAsync(s.dl, 0, sizeof(float) * 4 * SSB_DL, h->stream));
-            SDRX_HIP(hipMemsetAsync(s.hist, 0, sizeof(double) * (size_t)k.agc_nb_samples, h->stream));
+            SDRX_HIP(hipMemsetAsync(s.dl, 0, sizeof(float) * 4 * SSB_DL, h->core.stream));
+            SDRX_HIP(hipMemsetAsync(s.hist, 0, sizeof(double) * (size_t)k.agc_nb_samples, h->core.stream));
         }
     }
-    SDRX_HIP(hipMemcpyAsync(h->d_chan, hc.data(), sizeof(AtChan) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_chan, hc.data(), sizeof(AtChan) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
@@ -258,14 +252,13 @@ int sdrx_audiotail_create(sdrx_audiotail_t** out, int device, int32_t n_ch, cons
             set_error("sdrx_audiotail_create: bad channel configuration"); return SDRX_EINVAL;
         }
     }
-    int rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_audiotail* h = new (std::nothrow) sdrx_audiotail;
     if (!h) return SDRX_ENOMEM;
-    h->device = device; h->n_ch = n_ch; h->cfg.assign(cfg, cfg + n_ch);
+    int rc = h->core.open(device);
+    if (rc) { delete h; return rc; }
+    h->n_ch = n_ch; h->cfg.assign(cfg, cfg + n_ch);
     h->d_in.resize((size_t)n_ch); h->d_out.resize((size_t)n_ch); h->last_n.assign((size_t)n_ch, 0);
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) { h->stream = h->own_stream; e = hipMalloc(reinterpret_cast<void**>(&h->d_chan), sizeof(AtChan) * (size_t)n_ch); }
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_chan), sizeof(AtChan) * (size_t)n_ch);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_jobs), sizeof(AtJob) * (size_t)n_ch);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_jobs), sizeof(AtJob) * (size_t)n_ch, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->jobs_ev, hipEventDisableTiming);
@@ -287,8 +280,8 @@ int sdrx_audiotail_create(sdrx_audiotail_t** out, int device, int32_t n_ch, cons
 int sdrx_audiotail_destroy(sdrx_audiotail_t* h)
 {
     if (!h) return SDRX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)hipSetDevice(h->core.device);
+    if (h->core.stream) (void)hipStreamSynchronize(h->core.stream);
     for (void* p : h->bufs) (void)hipFree(p);
     if (h->d_chan) (void)hipFree(h->d_chan);
     if (h->d_jobs) (void)hipFree(h->d_jobs);
@@ -296,7 +289,7 @@ int sdrx_audiotail_destroy(sdrx_audiotail_t* h)
     if (h->jobs_ev) (void)hipEventDestroy(h->jobs_ev);
     for (auto& b : h->d_in) b.release();
     for (auto& b : h->d_out) b.release();
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->core.close();
     delete h;
     return SDRX_OK;
 }
@@ -304,23 +297,23 @@ int sdrx_audiotail_destroy(sdrx_audiotail_t* h)
 int sdrx_audiotail_reset(sdrx_audiotail_t* h)
 {
     if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return audiotail_init_state(h);
 }
 
 int sdrx_audiotail_feed_dev(sdrx_audiotail_t* h, const float* const* d_in, const int64_t* n, int16_t* const* d_audio)
 {
     if (!h || !d_in || !n || !d_audio) { set_error("sdrx_audiotail_feed_dev: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     SDRX_HIP(hipEventSynchronize(h->jobs_ev));
     for (int c = 0; c < h->n_ch; c++) {
         if (n[c] < 0 || (n[c] > 0 && (!d_in[c] || !d_audio[c]))) { set_error("sdrx_audiotail_feed_dev: bad channel argument"); return SDRX_EINVAL; }
         h->h_jobs[c] = AtJob{ d_in[c], d_audio[c], (long)n[c] };
     }
-    SDRX_HIP(hipMemcpyAsync(h->d_jobs, h->h_jobs, sizeof(AtJob) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->stream));
-    SDRX_HIP(hipEventRecord(h->jobs_ev, h->stream));
-    hipLaunchKernelGGL(audiotail_kernel, dim3((unsigned)((h->n_ch + AT_LANES - 1) / AT_LANES)), dim3(AT_LANES), 0, h->stream, h->d_chan, h->d_jobs, h->n_ch);
+    SDRX_HIP(hipMemcpyAsync(h->d_jobs, h->h_jobs, sizeof(AtJob) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->core.stream));
+    SDRX_HIP(hipEventRecord(h->jobs_ev, h->core.stream));
+    hipLaunchKernelGGL(audiotail_kernel, dim3((unsigned)((h->n_ch + AT_LANES - 1) / AT_LANES)), dim3(AT_LANES), 0, h->core.stream, h->d_chan, h->d_jobs, h->n_ch);
     SDRX_HIP(hipGetLastError());
     return SDRX_OK;
 }
@@ -328,29 +321,23 @@ int sdrx_audiotail_feed_dev(sdrx_audiotail_t* h, const float* const* d_in, const
 int sdrx_audiotail_feed(sdrx_audiotail_t* h, const float* const* in, const int64_t* n, int16_t* const* audio)
 {
     if (!h || !in || !n || !audio) { set_error("sdrx_audiotail_feed: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     std::vector<const float*> di((size_t)h->n_ch); std::vector<int16_t*> dout((size_t)h->n_ch);
     for (int c = 0; c < h->n_ch; c++) {
         if (n[c] < 0 || (n[c] > 0 && (!in[c] || !audio[c]))) { set_error("sdrx_audiotail_feed: bad channel argument"); return SDRX_EINVAL; }
         int rc = h->d_in[(size_t)c].reserve((size_t)(n[c] > 0 ? n[c] : 1) * 8); if (rc) return rc;
         rc = h->d_out[(size_t)c].reserve((size_t)(n[c] > 0 ? n[c] : 1) * 2); if (rc) return rc;
-        if (n[c]) SDRX_HIP(hipMemcpyAsync(h->d_in[(size_t)c].p, in[c], (size_t)n[c] * 8, hipMemcpyHostToDevice, h->stream));
+        if (n[c]) SDRX_HIP(hipMemcpyAsync(h->d_in[(size_t)c].p, in[c], (size_t)n[c] * 8, hipMemcpyHostToDevice, h->core.stream));
         di[(size_t)c] = static_cast<const float*>(h->d_in[(size_t)c].p); dout[(size_t)c] = static_cast<int16_t*>(h->d_out[(size_t)c].p);
     }
     int rc = sdrx_audiotail_feed_dev(h, di.data(), n, dout.data()); if (rc) return rc;
     for (int c = 0; c < h->n_ch; c++)
-        if (n[c]) SDRX_HIP(hipMemcpyAsync(audio[c], h->d_out[(size_t)c].p, (size_t)n[c] * 2, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+        if (n[c]) SDRX_HIP(hipMemcpyAsync(audio[c], h->d_out[(size_t)c].p, (size_t)n[c] * 2, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
-int sdrx_audiotail_sync(sdrx_audiotail_t* h)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    return SDRX_OK;
-}
+int sdrx_audiotail_sync(sdrx_audiotail_t* h) { return h ? h->core.sync() : SDRX_EINVAL; }
 
 } // extern "C"
 
@@ -396,8 +383,8 @@ void iir_kernel(IirChan* __restrict__ chans, const IirJob* __restrict__ jobs, in
 } // namespace
 
 struct sdrx_iir {
-    int device = 0, n_ch = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
+    int n_ch = 0;
     std::vector<IirChan> init;
     IirChan* d_chan = nullptr; IirJob* d_jobs = nullptr; IirJob* h_jobs = nullptr; hipEvent_t jobs_ev = nullptr;
     std::vector<DevBuf> d_in, d_out;
@@ -410,11 +397,11 @@ int sdrx_iir_create(sdrx_iir_t** out, int device, int32_t n_ch, const sdrx_iir_c
     if (!out || n_ch <= 0 || !cfg) { set_error("sdrx_iir_create: bad argument"); return SDRX_EINVAL; }
     *out = nullptr;
     for (int c = 0; c < n_ch; c++) if (cfg[c].order < 2 || cfg[c].order > 8) { set_error("sdrx_iir_create: order 2..8"); return SDRX_EINVAL; }
-    int rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_iir* h = new (std::nothrow) sdrx_iir;
     if (!h) return SDRX_ENOMEM;
-    h->device = device; h->n_ch = n_ch; h->init.resize((size_t)n_ch); h->d_in.resize((size_t)n_ch); h->d_out.resize((size_t)n_ch);
+    int rc = h->core.open(device);
+    if (rc) { delete h; return rc; }
+    h->n_ch = n_ch; h->init.resize((size_t)n_ch); h->d_in.resize((size_t)n_ch); h->d_out.resize((size_t)n_ch);
     for (int c = 0; c < n_ch; c++) {
         IirChan& s = h->init[(size_t)c];
         std::memset(&s, 0, sizeof s);
@@ -424,8 +411,7 @@ int sdrx_iir_create(sdrx_iir_t** out, int device, int32_t n_ch, const sdrx_iir_c
             else { s.ma[i] = cfg[c].b[i]; s.mb[i] = cfg[c].a[i]; }              // iirfilter.h:78-81 (sic)
         }
     }
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) { h->stream = h->own_stream; e = hipMalloc(reinterpret_cast<void**>(&h->d_chan), sizeof(IirChan) * (size_t)n_ch); }
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_chan), sizeof(IirChan) * (size_t)n_ch);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_jobs), sizeof(IirJob) * (size_t)n_ch);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_jobs), sizeof(IirJob) * (size_t)n_ch, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->jobs_ev, hipEventDisableTiming);
@@ -437,15 +423,15 @@ int sdrx_iir_create(sdrx_iir_t** out, int device, int32_t n_ch, const sdrx_iir_c
 int sdrx_iir_destroy(sdrx_iir_t* h)
 {
     if (!h) return SDRX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)hipSetDevice(h->core.device);
+    if (h->core.stream) (void)hipStreamSynchronize(h->core.stream);
     if (h->d_chan) (void)hipFree(h->d_chan);
     if (h->d_jobs) (void)hipFree(h->d_jobs);
     if (h->h_jobs) (void)hipHostFree(h->h_jobs);
     if (h->jobs_ev) (void)hipEventDestroy(h->jobs_ev);
     for (auto& b : h->d_in) b.release();
     for (auto& b : h->d_out) b.release();
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->core.close();
     delete h;
     return SDRX_OK;
 }
@@ -453,31 +439,31 @@ int sdrx_iir_destroy(sdrx_iir_t* h)
 int sdrx_iir_reset(sdrx_iir_t* h)
 {
     if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipMemcpyAsync(h->d_chan, h->init.data(), sizeof(IirChan) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipMemcpyAsync(h->d_chan, h->init.data(), sizeof(IirChan) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
 int sdrx_iir_feed(sdrx_iir_t* h, const float* const* in, const int64_t* n, float* const* out)
 {
     if (!h || !in || !n || !out) { set_error("sdrx_iir_feed: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     SDRX_HIP(hipEventSynchronize(h->jobs_ev));
     for (int c = 0; c < h->n_ch; c++) {
         if (n[c] < 0 || (n[c] > 0 && (!in[c] || !out[c]))) { set_error("sdrx_iir_feed: bad channel argument"); return SDRX_EINVAL; }
         int rc = h->d_in[(size_t)c].reserve((size_t)(n[c] > 0 ? n[c] : 1) * 4); if (rc) return rc;
         rc = h->d_out[(size_t)c].reserve((size_t)(n[c] > 0 ? n[c] : 1) * 4); if (rc) return rc;
-        if (n[c]) SDRX_HIP(hipMemcpyAsync(h->d_in[(size_t)c].p, in[c], (size_t)n[c] * 4, hipMemcpyHostToDevice, h->stream));
+        if (n[c]) SDRX_HIP(hipMemcpyAsync(h->d_in[(size_t)c].p, in[c], (size_t)n[c] * 4, hipMemcpyHostToDevice, h->core.stream));
         h->h_jobs[c] = IirJob{ static_cast<const float*>(h->d_in[(size_t)c].p), static_cast<float*>(h->d_out[(size_t)c].p), (long)n[c] };
     }
-    SDRX_HIP(hipMemcpyAsync(h->d_jobs, h->h_jobs, sizeof(IirJob) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->stream));
-    SDRX_HIP(hipEventRecord(h->jobs_ev, h->stream));
-    hipLaunchKernelGGL(iir_kernel, dim3((unsigned)((h->n_ch + 63) / 64)), dim3(64), 0, h->stream, h->d_chan, h->d_jobs, h->n_ch);
+    SDRX_HIP(hipMemcpyAsync(h->d_jobs, h->h_jobs, sizeof(IirJob) * (size_t)h->n_ch, hipMemcpyHostToDevice, h->core.stream));
+    SDRX_HIP(hipEventRecord(h->jobs_ev, h->core.stream));
+    hipLaunchKernelGGL(iir_kernel, dim3((unsigned)((h->n_ch + 63) / 64)), dim3(64), 0, h->core.stream, h->d_chan, h->d_jobs, h->n_ch);
     SDRX_HIP(hipGetLastError());
     for (int c = 0; c < h->n_ch; c++)
-        if (n[c]) SDRX_HIP(hipMemcpyAsync(out[c], h->d_out[(size_t)c].p, (size_t)n[c] * 4, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+        if (n[c]) SDRX_HIP(hipMemcpyAsync(out[c], h->d_out[(size_t)c].p, (size_t)n[c] * 4, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 

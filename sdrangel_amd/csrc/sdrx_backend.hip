@@ -30,8 +30,7 @@ struct ChanHost {
 } // namespace
 
 struct sdrx_backend {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
     int n_ch = 0;
     std::vector<ChanHost> ch;
     std::vector<BeChan> h_chan;   // host mirror of the config part (state lives on the device)
@@ -68,9 +67,9 @@ static int ensure_capacity(sdrx_backend* b, int c, int64_t n_in)
         if (bytes <= buf.cap) return SDRX_OK;
         void* np = nullptr;
         SDRX_HIP(hipMalloc(&np, bytes));
-        SDRX_HIP(hipMemsetAsync(np, 0, bytes, b->stream));
-        if (buf.p && keep) SDRX_HIP(hipMemcpyAsync(np, buf.p, keep, hipMemcpyDeviceToDevice, b->stream));
-        SDRX_HIP(hipStreamSynchronize(b->stream));
+        SDRX_HIP(hipMemsetAsync(np, 0, bytes, b->core.stream));
+        if (buf.p && keep) SDRX_HIP(hipMemcpyAsync(np, buf.p, keep, hipMemcpyDeviceToDevice, b->core.stream));
+        SDRX_HIP(hipStreamSynchronize(b->core.stream));
         if (buf.p) (void)hipFree(buf.p);
         buf.p = np; buf.cap = bytes;
         return SDRX_OK;
@@ -91,8 +90,8 @@ extern "C" {
 int sdrx_backend_destroy(sdrx_backend_t* b)
 {
     if (!b) return SDRX_OK;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    (void)hipSetDevice(b->core.device);
+    if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
     for (auto& h : b->ch) {
         h.mixed.release(); h.res.release(); h.head.release(); h.tail.release();
         h.cplx_out.release(); h.real_out.release(); h.stage_in.release();
@@ -111,7 +110,7 @@ int sdrx_backend_destroy(sdrx_backend_t* b)
     if (b->d_filters) (void)hipFree(b->d_filters);
     if (b->d_utbl) (void)hipFree(b->d_utbl);
     if (b->d_utbl2) (void)hipFree(b->d_utbl2);
-    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+    b->core.close();
     delete b;
     return SDRX_OK;
 }
@@ -129,35 +128,31 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
             return SDRX_EINVAL;
         }
     }
-    int rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_backend* b = new (std::nothrow) sdrx_backend;
     if (!b) return SDRX_ENOMEM;
-    b->device = device; b->n_ch = n_ch;
-    hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete b; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-    b->stream = b->own_stream;
+    int rc = b->core.open(device);
+    if (rc) { delete b; return rc; }
+    b->n_ch = n_ch;
     b->ch.resize((size_t)n_ch); b->h_chan.resize((size_t)n_ch);
     b->taps_off.resize((size_t)n_ch); b->filt_off.resize((size_t)n_ch); b->ntaps.resize((size_t)n_ch);
 
-#define BE_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = hip_fail(e_, #call, __FILE__, __LINE__); sdrx_backend_destroy(b); return r_; } } while (0)
     // NCO table (nco.cpp:30-39) and g_fft cosine table (gfft.h:141-150)
     std::vector<float> nco(BE_NCO_N);
     for (int i = 0; i < BE_NCO_N; i++) nco[(size_t)i] = (float)std::cos((2.0 * PI_D * i) / BE_NCO_N);
-    BE_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_nco), BE_NCO_N * 4));
-    BE_TRY(hipMemcpy(b->d_nco, nco.data(), BE_NCO_N * 4, hipMemcpyHostToDevice));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_nco), BE_NCO_N * 4), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipMemcpy(b->d_nco, nco.data(), BE_NCO_N * 4, hipMemcpyHostToDevice), sdrx_backend_destroy(b));
     for (int n : { BE_FFT, BE_FFT_MAX }) {
         std::vector<float> utbl((size_t)n / 4 + 1);
         utbl[0] = 1.0f;
         for (int i = 1; i < n / 4; i++) utbl[(size_t)i] = (float)std::cos((2.0 * 3.141592653589793238462643383279502884197 * (float)i) / (float)n);
         utbl[(size_t)n / 4] = 0.0f;
         float*& dst = n == BE_FFT ? b->d_utbl : b->d_utbl2;
-        BE_TRY(hipMalloc(reinterpret_cast<void**>(&dst), ((size_t)n / 4 + 1) * 4));
-        BE_TRY(hipMemcpy(dst, utbl.data(), ((size_t)n / 4 + 1) * 4, hipMemcpyHostToDevice));
+        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&dst), ((size_t)n / 4 + 1) * 4), sdrx_backend_destroy(b));
+        SDRX_HIP_ELSE(hipMemcpy(dst, utbl.data(), ((size_t)n / 4 + 1) * 4, hipMemcpyHostToDevice), sdrx_backend_destroy(b));
     }
 
     // per channel design
-    BE_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_filters), (size_t)n_ch * 2 * BE_FFT_MAX * 8));   // [filter | filterOpp] per channel
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_filters), (size_t)n_ch * 2 * BE_FFT_MAX * 8), sdrx_backend_destroy(b));   // [filter | filterOpp] per channel
     b->filters_all.assign((size_t)n_ch * 2 * BE_FFT_MAX * 2, 0.0f);
     for (int c = 0; c < n_ch; c++) {
         const sdrx_backend_cfg& k = cfg[c];
@@ -202,10 +197,10 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
             for (int i = 0; i < h2; i++) { const float w = blackman(i, h2); f[(size_t)(2 * i)] *= w; f[(size_t)(2 * i + 1)] *= w; }
             float2* dst = b->d_filters + (size_t)c * 2 * BE_FFT_MAX + (size_t)which * BE_FFT_MAX;
             SDRX_HIP(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice));
-            if (flen == BE_FFT) hipLaunchKernelGGL(be_fft_design_kernel<BE_FFT>, dim3(1), dim3(BE_FFT / 8), 0, b->stream, dst, b->d_utbl);
-            else hipLaunchKernelGGL(be_fft_design_kernel<BE_FFT_MAX>, dim3(1), dim3(BE_FFT_MAX / 8), 0, b->stream, dst, b->d_utbl2);
+            if (flen == BE_FFT) hipLaunchKernelGGL(be_fft_design_kernel<BE_FFT>, dim3(1), dim3(BE_FFT / 8), 0, b->core.stream, dst, b->d_utbl);
+            else hipLaunchKernelGGL(be_fft_design_kernel<BE_FFT_MAX>, dim3(1), dim3(BE_FFT_MAX / 8), 0, b->core.stream, dst, b->d_utbl2);
             SDRX_HIP(hipGetLastError());
-            SDRX_HIP(hipStreamSynchronize(b->stream));
+            SDRX_HIP(hipStreamSynchronize(b->core.stream));
             SDRX_HIP(hipMemcpy(f.data(), dst, (size_t)flen * 8, hipMemcpyDeviceToHost));
             float scale = 0;
             for (int i = 0; i < h2; i++) { const float mag = hypotf(f[(size_t)(2 * i)], f[(size_t)(2 * i + 1)]); if (mag > scale) scale = mag; }
@@ -236,8 +231,8 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
         if (s.dy_q >= 0) b->any_dyadic = true;
         s.half = flen / 2;
         for (int i = 0; i < 2; i++) {
-            BE_TRY(hipMalloc(reinterpret_cast<void**>(&h.hist[i]), BE_HIST * 4));
-            BE_TRY(hipMemsetAsync(h.hist[i], 0, BE_HIST * 4, b->stream));   // on the handle's own (non-blocking) stream: ordered before its kernels
+            SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.hist[i]), BE_HIST * 4), sdrx_backend_destroy(b));
+            SDRX_HIP_ELSE(hipMemsetAsync(h.hist[i], 0, BE_HIST * 4, b->core.stream), sdrx_backend_destroy(b));   // on the handle's own (non-blocking) stream: ordered before its kernels
         }
     }
     // schedule columns: channels sorted by tap table, so that a FIR tile of 16 columns normally sees one design
@@ -245,19 +240,18 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
     for (int c = 0; c < n_ch; c++) b->perm[(size_t)c] = c;
     std::stable_sort(b->perm.begin(), b->perm.end(), [&](int x, int y) { return b->taps_off[(size_t)x] < b->taps_off[(size_t)y]; });
     for (int q = 0; q < n_ch; q++) b->col_of[(size_t)b->perm[(size_t)q]] = q;
-    BE_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_perm), (size_t)n_ch * sizeof(int)));
-    BE_TRY(hipMemcpy(b->d_perm, b->perm.data(), (size_t)n_ch * sizeof(int), hipMemcpyHostToDevice));
-    BE_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_taps), b->taps_all.size() * 4));
-    BE_TRY(hipMemcpy(b->d_taps, b->taps_all.data(), b->taps_all.size() * 4, hipMemcpyHostToDevice));
-    BE_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(BeChan)));
-    BE_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(BeBufs)));
-    BE_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(BeBufs), hipHostMallocDefault));
-    BE_TRY(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming));
-    BE_TRY(hipEventRecord(b->bufs_ev, b->stream));
-    BE_TRY(hipEventCreateWithFlags(&b->prod_ev, hipEventDisableTiming));
-    BE_TRY(hipEventCreateWithFlags(&b->cons_ev, hipEventDisableTiming));
-    BE_TRY(hipMemcpy(b->d_chan, b->h_chan.data(), (size_t)n_ch * sizeof(BeChan), hipMemcpyHostToDevice));
-#undef BE_TRY
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_perm), (size_t)n_ch * sizeof(int)), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipMemcpy(b->d_perm, b->perm.data(), (size_t)n_ch * sizeof(int), hipMemcpyHostToDevice), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_taps), b->taps_all.size() * 4), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipMemcpy(b->d_taps, b->taps_all.data(), b->taps_all.size() * 4, hipMemcpyHostToDevice), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(BeChan)), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(BeBufs)), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(BeBufs), hipHostMallocDefault), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipEventRecord(b->bufs_ev, b->core.stream), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->prod_ev, hipEventDisableTiming), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->cons_ev, hipEventDisableTiming), sdrx_backend_destroy(b));
+    SDRX_HIP_ELSE(hipMemcpy(b->d_chan, b->h_chan.data(), (size_t)n_ch * sizeof(BeChan), hipMemcpyHostToDevice), sdrx_backend_destroy(b));
     *out = b;
     return SDRX_OK;
 }
@@ -279,7 +273,7 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
     if (n_max + 1024 > b->sched_cap) {
         int64_t cap = b->sched_cap ? b->sched_cap : 8192;
         while (cap < n_max + 1024) cap *= 2;
-        SDRX_HIP(hipStreamSynchronize(b->stream));
+        SDRX_HIP(hipStreamSynchronize(b->core.stream));
         int rc = b->sched.reserve((size_t)cap * (size_t)b->n_ch * sizeof(uint2)); if (rc) return rc;
         b->sched_cap = cap;
     }
@@ -295,48 +289,48 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
         u.cplx_out = static_cast<float2*>(h.cplx_out.p); u.real_out = static_cast<float*>(h.real_out.p);
         u.n_in = n_per_ch[c];
     }
-    SDRX_HIP(hipMemcpyAsync(b->d_bufs, b->h_bufs, (size_t)b->n_ch * sizeof(BeBufs), hipMemcpyHostToDevice, b->stream));
-    SDRX_HIP(hipEventRecord(b->bufs_ev, b->stream));
+    SDRX_HIP(hipMemcpyAsync(b->d_bufs, b->h_bufs, (size_t)b->n_ch * sizeof(BeBufs), hipMemcpyHostToDevice, b->core.stream));
+    SDRX_HIP(hipEventRecord(b->bufs_ev, b->core.stream));
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (n_max + BE_HIST + 255) / 256));
     // closed-form schedule for dyadic ratios (prep decides per channel and feed), the serial walk for the rest
-    hipLaunchKernelGGL(be_sched_dyadic_prep_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
+    hipLaunchKernelGGL(be_sched_dyadic_prep_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
     SDRX_HIP(hipGetLastError());
     if (b->any_dyadic) {
         hipLaunchKernelGGL(be_sched_dyadic_fill_kernel, dim3((unsigned)((n_res_bound + 255) / 256), (unsigned)((b->n_ch + 63) / 64)), dim3(256), 0,
-                           b->stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
+                           b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
         SDRX_HIP(hipGetLastError());
     }
     // always launched: lanes whose channel the closed form took exit at once (prep's off-grid guard can hand a channel back)
-    hipLaunchKernelGGL(be_schedule_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
+    hipLaunchKernelGGL(be_schedule_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
     SDRX_HIP(hipGetLastError());
-    if (producer && producer != b->stream) {
+    if (producer && producer != b->core.stream) {
         SDRX_HIP(hipEventRecord(b->prod_ev, producer));
-        SDRX_HIP(hipStreamWaitEvent(b->stream, b->prod_ev, 0));
+        SDRX_HIP(hipStreamWaitEvent(b->core.stream, b->prod_ev, 0));
     }
     // be_mix stages the 16 KB NCO table per workgroup: at least 8192 samples each
     const unsigned gx_mix = (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (n_max + BE_HIST + 8191) / 8192));
-    hipLaunchKernelGGL(be_mix_kernel, dim3(gx_mix, (unsigned)b->n_ch), dim3(256), 0, b->stream, b->d_chan, b->d_bufs, b->d_nco);
+    hipLaunchKernelGGL(be_mix_kernel, dim3(gx_mix, (unsigned)b->n_ch), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_nco);
     SDRX_HIP(hipGetLastError());
-    if (producer && producer != b->stream) {
-        SDRX_HIP(hipEventRecord(b->cons_ev, b->stream));
+    if (producer && producer != b->core.stream) {
+        SDRX_HIP(hipEventRecord(b->cons_ev, b->core.stream));
         SDRX_HIP(hipStreamWaitEvent(producer, b->cons_ev, 0));
     }
     hipLaunchKernelGGL(be_fir_kernel, dim3((unsigned)((n_res_bound + BE_FIR_TO - 1) / BE_FIR_TO), (unsigned)((b->n_ch + BE_FIR_TC - 1) / BE_FIR_TC)), dim3(256), 0,
-                       b->stream, b->d_chan, b->d_bufs, b->d_taps, b->d_perm, b->n_ch);
+                       b->core.stream, b->d_chan, b->d_bufs, b->d_taps, b->d_perm, b->n_ch);
     SDRX_HIP(hipGetLastError());
     if (b->any1024) {
         const unsigned max_blocks = (unsigned)((n_max + BE_FFT) / (BE_FFT / 2) + 1);
-        hipLaunchKernelGGL(be_fft_kernel<BE_FFT>, dim3(max_blocks, (unsigned)b->n_ch), dim3(BE_FFT / 8), 0, b->stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl);
+        hipLaunchKernelGGL(be_fft_kernel<BE_FFT>, dim3(max_blocks, (unsigned)b->n_ch), dim3(BE_FFT / 8), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl);
         SDRX_HIP(hipGetLastError());
     }
     if (b->any2048) {
         const unsigned max_blocks = (unsigned)((n_max + BE_FFT_MAX) / (BE_FFT_MAX / 2) + 1);
-        hipLaunchKernelGGL(be_fft_kernel<BE_FFT_MAX>, dim3(max_blocks, (unsigned)b->n_ch), dim3(BE_FFT_MAX / 8), 0, b->stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl2);
+        hipLaunchKernelGGL(be_fft_kernel<BE_FFT_MAX>, dim3(max_blocks, (unsigned)b->n_ch), dim3(BE_FFT_MAX / 8), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl2);
         SDRX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(be_finish_kernel, dim3(gx, (unsigned)b->n_ch), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+    hipLaunchKernelGGL(be_finish_kernel, dim3(gx, (unsigned)b->n_ch), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(be_carry_kernel, dim3((unsigned)b->n_ch), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+    hipLaunchKernelGGL(be_carry_kernel, dim3((unsigned)b->n_ch), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
     for (auto& h : b->ch) h.cur ^= 1;
     return SDRX_OK;
@@ -345,14 +339,14 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
 int sdrx_backend_feed_dev(sdrx_backend_t* b, const int16_t* const* d_iq, const int64_t* n_per_ch)
 {
     if (!b || !d_iq || !n_per_ch) { set_error("sdrx_backend_feed_dev: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     return feed_common(b, d_iq, n_per_ch);
 }
 
 int sdrx_backend_feed_bank(sdrx_backend_t* b, sdrx_chan_bank_t* bank)
 {
     if (!b || !bank) { set_error("sdrx_backend_feed_bank: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     void* ps = nullptr;
     int rc = sdrx_chan_bank_get_stream(bank, &ps); if (rc) return rc;
     std::vector<const int16_t*> d((size_t)b->n_ch);
@@ -367,13 +361,13 @@ int sdrx_backend_feed_bank(sdrx_backend_t* b, sdrx_chan_bank_t* bank)
 int sdrx_backend_feed(sdrx_backend_t* b, const int16_t* const* iq, const int64_t* n_per_ch)
 {
     if (!b || !iq || !n_per_ch) { set_error("sdrx_backend_feed: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     std::vector<const int16_t*> d((size_t)b->n_ch);
     for (int c = 0; c < b->n_ch; c++) {
         ChanHost& h = b->ch[(size_t)c];
         int rc = h.stage_in.reserve((size_t)std::max<int64_t>(n_per_ch[c], 1) * 4); if (rc) return rc;
-        if (n_per_ch[c] > 0) SDRX_HIP(hipMemcpyAsync(h.stage_in.p, iq[c], (size_t)n_per_ch[c] * 4, hipMemcpyHostToDevice, b->stream));
+        if (n_per_ch[c] > 0) SDRX_HIP(hipMemcpyAsync(h.stage_in.p, iq[c], (size_t)n_per_ch[c] * 4, hipMemcpyHostToDevice, b->core.stream));
         d[(size_t)c] = static_cast<const int16_t*>(h.stage_in.p);
     }
     return feed_common(b, d.data(), n_per_ch);
@@ -382,10 +376,10 @@ int sdrx_backend_feed(sdrx_backend_t* b, const int16_t* const* iq, const int64_t
 int64_t sdrx_backend_read(sdrx_backend_t* b, int32_t c, float* out, int64_t cap_floats)
 {
     if (!b || c < 0 || c >= b->n_ch || cap_floats < 0 || (cap_floats > 0 && !out)) { set_error("sdrx_backend_read: bad argument"); return SDRX_EINVAL; }
-    if (hipSetDevice(b->device) != hipSuccess) return SDRX_EHIP;
+    if (hipSetDevice(b->core.device) != hipSuccess) return SDRX_EHIP;
     BeChan s;
-    hipError_t e = hipMemcpyAsync(&s, b->d_chan + c, sizeof s, hipMemcpyDeviceToHost, b->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    hipError_t e = hipMemcpyAsync(&s, b->d_chan + c, sizeof s, hipMemcpyDeviceToHost, b->core.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->core.stream);
     if (e != hipSuccess) return hip_fail(e, "read state", __FILE__, __LINE__);
     const bool real = s.discri != 0;
     int64_t n_floats = (int64_t)s.n_out * (real ? 1 : 2);
@@ -400,10 +394,10 @@ int64_t sdrx_backend_read(sdrx_backend_t* b, int32_t c, float* out, int64_t cap_
 int sdrx_backend_last_dev(sdrx_backend_t* b, int32_t c, const float** d_out, int64_t* n_floats)
 {
     if (!b || c < 0 || c >= b->n_ch || !d_out || !n_floats) { set_error("sdrx_backend_last_dev: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     BeChan s;
-    SDRX_HIP(hipMemcpyAsync(&s, b->d_chan + c, sizeof s, hipMemcpyDeviceToHost, b->stream));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipMemcpyAsync(&s, b->d_chan + c, sizeof s, hipMemcpyDeviceToHost, b->core.stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     const bool real = s.discri != 0;
     *d_out = static_cast<const float*>(real ? b->ch[(size_t)c].real_out.p : b->ch[(size_t)c].cplx_out.p);
     *n_floats = (int64_t)s.n_out * (real ? 1 : 2);
@@ -422,13 +416,7 @@ int sdrx_backend_get_design(sdrx_backend_t* b, int32_t c, int32_t* ntaps_per_pha
     return SDRX_OK;
 }
 
-int sdrx_backend_sync(sdrx_backend_t* b)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    return SDRX_OK;
-}
+int sdrx_backend_sync(sdrx_backend_t* b) { return b ? b->core.sync() : SDRX_EINVAL; }
 
 } // extern "C"
 
@@ -445,11 +433,7 @@ int backend_view(sdrx_backend_t* b, int32_t c, BackendView* v)
 
 int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream)
 {
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    b->stream = hip_stream ? hip_stream : b->own_stream;
-    return SDRX_OK;
+    return b ? b->core.set_stream(hip_stream) : SDRX_EINVAL;
 }
 
 } // namespace sdrx

@@ -52,9 +52,9 @@ struct Group {
 } // namespace
 
 struct sdrx_chan_bank {
-    int device = 0, cus = 256;
+    HandleCore core;
+    int cus = 256;
     int32_t in_rate = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
     std::vector<Channel> ch;
     std::vector<Group*> groups;
     DevBuf stage_in;              // host-pointer feeds are staged here
@@ -66,9 +66,6 @@ struct sdrx_chan_bank {
     size_t dyn_cap[RING] = { 0, 0, 0, 0 };
     hipEvent_t dyn_ev[RING] = { nullptr, nullptr, nullptr, nullptr };
     int dyn_next = 0;
-    char last_name[96] = "";
-    int last_grid = 0, last_block = 0, last_lds = 0;
-    EventTimer timer;
 };
 
 static void free_group(Group* g)
@@ -88,7 +85,7 @@ static int upload_group(sdrx_chan_bank* b, Group* g)
         const size_t bytes = (size_t)p.streams[si].hist_len * 4;
         for (uint32_t*& h : g->bufs[si].hist) {
             SDRX_HIP(hipMalloc(reinterpret_cast<void**>(&h), bytes));
-            SDRX_HIP(hipMemsetAsync(h, 0, bytes, b->stream));
+            SDRX_HIP(hipMemsetAsync(h, 0, bytes, b->core.stream));
         }
     }
     const size_t b0 = p.subtrees.size() * sizeof(TkSubtree), b1 = p.nodes.size() * sizeof(TkNode), b2 = p.arrays.size() * sizeof(TkArray);
@@ -154,7 +151,7 @@ static int retire_dead_groups(sdrx_chan_bank* b)
         bool live = false;
         for (int c : g->chans) if (b->ch[(size_t)c].group == g->index) { live = true; break; }
         if (live) { gi++; continue; }
-        SDRX_HIP(hipStreamSynchronize(b->stream));
+        SDRX_HIP(hipStreamSynchronize(b->core.stream));
         free_group(g);
         b->groups.erase(b->groups.begin() + (long)gi);
         for (size_t k = gi; k < b->groups.size(); k++) {
@@ -174,8 +171,8 @@ static int grow_keep(sdrx_chan_bank* b, DevBuf& buf, size_t used, size_t need)
     while (want < need) want *= 2;
     void* np = nullptr;
     SDRX_HIP(hipMalloc(&np, want));
-    if (used) SDRX_HIP(hipMemcpyAsync(np, buf.p, used, hipMemcpyDeviceToDevice, b->stream));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    if (used) SDRX_HIP(hipMemcpyAsync(np, buf.p, used, hipMemcpyDeviceToDevice, b->core.stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     if (buf.p) (void)hipFree(buf.p);
     buf.p = np; buf.cap = want;
     return SDRX_OK;
@@ -268,13 +265,13 @@ static int feed_group(sdrx_chan_bank* b, Group* g, const uint32_t* d_in, int64_t
             segs[si] = (std::max(0L, hs[si].c_last - hs[si].c_first + 1) + cps - 1) / cps;
         }
     }
-    SDRX_HIP(hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, b->stream));
-    SDRX_HIP(hipEventRecord(b->dyn_ev[slot], b->stream));
+    SDRX_HIP(hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, b->core.stream));
+    SDRX_HIP(hipEventRecord(b->dyn_ev[slot], b->core.stream));
 
     const TkStream* d_streams = reinterpret_cast<const TkStream*>(dp);
     const TkSink* d_sinks = reinterpret_cast<const TkSink*>(dp + o_sinks);
     const TkHistJob* d_hist = reinterpret_cast<const TkHistJob*>(dp + o_hist);
-    rc = b->timer.begin(b->stream); if (rc) return rc;
+    rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
     for (size_t p = 0; p < plan.passes.size(); p++) {
         // the streams of one pass are contiguous in creation order; launch them as grid.y
         const std::vector<int>& ps = plan.passes[p];
@@ -288,24 +285,21 @@ static int feed_group(sdrx_chan_bank* b, Group* g, const uint32_t* d_in, int64_t
         // an all-matrix-core pass (every default pass) runs the lean kernel; deeper passes (SDRX_CHAN_MAX_LEVELS / _LDS_KB)
         // have dot2 levels and keep tree_kernel<true>.  Both are the matrix-core engine: last_launch() names it tree_kernel<mfma>.
         if (g->low.pass_mx[p])
-            hipLaunchKernelGGL(tree_mx_kernel, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->stream,
+            hipLaunchKernelGGL(tree_mx_kernel, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->core.stream,
                                g->d_subtrees, g->d_arrays, d_streams + s0, d_sinks, g->d_ljobs, g->d_lroots);
         else if (plan.mfma)
-            hipLaunchKernelGGL(tree_kernel<true>, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->stream,
+            hipLaunchKernelGGL(tree_kernel<true>, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->core.stream,
                                g->d_subtrees, g->d_nodes, g->d_arrays, d_streams + s0, d_sinks, g->d_mjobs);
         else
-            hipLaunchKernelGGL(tree_kernel<false>, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->stream,
+            hipLaunchKernelGGL(tree_kernel<false>, dim3((unsigned)max_segs, (unsigned)cnt), dim3(TK_THREADS), lds_bytes, b->core.stream,
                                g->d_subtrees, g->d_nodes, g->d_arrays, d_streams + s0, d_sinks, g->d_mjobs);
         SDRX_HIP(hipGetLastError());
-        if (p == 0) {
-            snprintf(b->last_name, sizeof b->last_name, plan.mfma ? "tree_kernel<mfma>" : "tree_kernel<valu>");
-            b->last_grid = (int)(max_segs * cnt); b->last_block = TK_THREADS; b->last_lds = (int)lds_bytes;
-        }
+        if (p == 0) b->core.note_launch(plan.mfma ? "tree_kernel<mfma>" : "tree_kernel<valu>", (int)(max_segs * cnt), TK_THREADS, (int)lds_bytes);
     }
-    rc = b->timer.end(b->stream); if (rc) return rc;
+    rc = b->core.timer.end(b->core.stream); if (rc) return rc;
     long max_hist = TK_HIST;
     for (const PlanStream& s : plan.streams) max_hist = std::max(max_hist, s.hist_len);
-    hipLaunchKernelGGL(tree_hist_kernel, dim3((unsigned)(max_hist / 256), (unsigned)ns), dim3(256), 0, b->stream, d_hist);
+    hipLaunchKernelGGL(tree_hist_kernel, dim3((unsigned)(max_hist / 256), (unsigned)ns), dim3(256), 0, b->core.stream, d_hist);
     SDRX_HIP(hipGetLastError());
     for (StreamBuf& sb : g->bufs) sb.cur ^= 1;
     for (int c : g->chans) {
@@ -324,7 +318,7 @@ static int feed_passthrough(sdrx_chan_bank* b, const uint32_t* d_in, int64_t n)
     for (auto& ch : b->ch) {
         if (!ch.passthrough) continue;
         int rc = grow_keep(b, ch.out, (size_t)ch.avail * 4, (size_t)(ch.avail + n) * 4 + 64); if (rc) return rc;
-        SDRX_HIP(hipMemcpyAsync(static_cast<uint32_t*>(ch.out.p) + ch.avail, d_in, (size_t)n * 4, hipMemcpyDeviceToDevice, b->stream));
+        SDRX_HIP(hipMemcpyAsync(static_cast<uint32_t*>(ch.out.p) + ch.avail, d_in, (size_t)n * 4, hipMemcpyDeviceToDevice, b->core.stream));
         ch.last_off = ch.avail; ch.last_n = n; ch.avail += n;
     }
     return SDRX_OK;
@@ -344,15 +338,12 @@ int sdrx_chan_bank_create(sdrx_chan_bank_t** out, int device, int32_t in_rate, i
     if (!out) { set_error("sdrx_chan_bank_create: null out"); return SDRX_EINVAL; }
     *out = nullptr;
     if (n_ch <= 0 || !req_rate || !req_fc || in_rate <= 0) { set_error("sdrx_chan_bank_create: bad argument"); return SDRX_EINVAL; }
-    int rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_chan_bank* b = new (std::nothrow) sdrx_chan_bank;
     if (!b) return SDRX_ENOMEM;
-    b->device = device; b->in_rate = in_rate; b->cus = device_cu_count(device);
-    hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete b; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-    b->stream = b->own_stream;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tree_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    int rc = b->core.open(device);
+    if (rc) { delete b; return rc; }
+    b->in_rate = in_rate; b->cus = device_cu_count(device);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tree_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tree_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tree_mx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) { sdrx_chan_bank_destroy(b); return hip_fail(e, "hipFuncSetAttribute", __FILE__, __LINE__); }
@@ -364,7 +355,7 @@ int sdrx_chan_bank_create(sdrx_chan_bank_t** out, int device, int32_t in_rate, i
     }
     rc = new_group(b, all);
     if (rc) { sdrx_chan_bank_destroy(b); return rc; }
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     *out = b;
     return SDRX_OK;
 }
@@ -372,17 +363,17 @@ int sdrx_chan_bank_create(sdrx_chan_bank_t** out, int device, int32_t in_rate, i
 int sdrx_chan_bank_destroy(sdrx_chan_bank_t* b)
 {
     if (!b) return SDRX_OK;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    (void)hipSetDevice(b->core.device);
+    if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
     for (Group* g : b->groups) free_group(g);
     for (auto& c : b->ch) c.out.release();
-    b->stage_in.release(); b->scratch.release(); b->timer.release();
+    b->stage_in.release(); b->scratch.release();
     for (int i = 0; i < sdrx_chan_bank::RING; i++) {
         if (b->h_dyn[i]) (void)hipHostFree(b->h_dyn[i]);
         if (b->d_dyn[i]) (void)hipFree(b->d_dyn[i]);
         if (b->dyn_ev[i]) (void)hipEventDestroy(b->dyn_ev[i]);
     }
-    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+    b->core.close();
     delete b;
     return SDRX_OK;
 }
@@ -401,7 +392,7 @@ int sdrx_chan_bank_info(const sdrx_chan_bank_t* b, int32_t c, int32_t* n_stages,
 int sdrx_chan_bank_reconfigure(sdrx_chan_bank_t* b, int32_t c, int32_t req_rate, int32_t req_fc)
 {
     if (!b || c < 0 || c >= (int32_t)b->ch.size()) { set_error("sdrx_chan_bank_reconfigure: bad channel"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     Channel& ch = b->ch[(size_t)c];
     // the old chain keeps being evaluated inside its group (its prefixes are shared) but stops
     // storing; the new chain starts from zero history in a group of its own
@@ -418,7 +409,7 @@ int sdrx_chan_bank_reconfigure(sdrx_chan_bank_t* b, int32_t c, int32_t req_rate,
 int sdrx_chan_bank_add_channel(sdrx_chan_bank_t* b, int32_t req_rate, int32_t req_fc, int32_t* channel)
 {
     if (!b) { set_error("sdrx_chan_bank_add_channel: null bank"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     // a new DownChannelizer next to the existing ones: they keep their histories and queued output
     b->ch.emplace_back();
     const int c = (int)b->ch.size() - 1;
@@ -433,7 +424,7 @@ int sdrx_chan_bank_add_channel(sdrx_chan_bank_t* b, int32_t req_rate, int32_t re
 int sdrx_chan_bank_remove_channel(sdrx_chan_bank_t* b, int32_t c)
 {
     if (!b || c < 0 || c >= (int32_t)b->ch.size()) { set_error("sdrx_chan_bank_remove_channel: bad channel"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     // the index stays reserved (other channels keep theirs); the chain stops producing and its queue is dropped
     Channel& ch = b->ch[(size_t)c];
     ch.group = -1; ch.passthrough = false; ch.dead = true; ch.n = 0; ch.out_rate = 0; ch.ofs = 0;
@@ -458,7 +449,7 @@ int64_t sdrx_chan_bank_state_bytes(const sdrx_chan_bank_t* b)
 int sdrx_chan_bank_get_state(sdrx_chan_bank_t* b, void* host_buf)
 {
     if (!b || !host_buf) { set_error("sdrx_chan_bank_get_state: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     char* p = static_cast<char*>(host_buf);
     auto put = [&](int64_t v) { std::memcpy(p, &v, 8); p += 8; };
     put(CHAN_STATE_MAGIC); put((int64_t)b->groups.size());
@@ -467,18 +458,18 @@ int sdrx_chan_bank_get_state(sdrx_chan_bank_t* b, void* host_buf)
         for (size_t si = 0; si < g->bufs.size(); si++) {
             const long len = g->plan.streams[si].hist_len;
             put(len);
-            SDRX_HIP(hipMemcpyAsync(p, g->bufs[si].hist[g->bufs[si].cur], (size_t)len * 4, hipMemcpyDeviceToHost, b->stream));
+            SDRX_HIP(hipMemcpyAsync(p, g->bufs[si].hist[g->bufs[si].cur], (size_t)len * 4, hipMemcpyDeviceToHost, b->core.stream));
             p += (size_t)len * 4;
         }
     }
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     return SDRX_OK;
 }
 
 int sdrx_chan_bank_set_state(sdrx_chan_bank_t* b, const void* host_buf)
 {
     if (!b || !host_buf) { set_error("sdrx_chan_bank_set_state: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     const char* p = static_cast<const char*>(host_buf);
     auto get = [&]() { int64_t v; std::memcpy(&v, p, 8); p += 8; return v; };
     // first pass: the shape must be this bank's
@@ -493,17 +484,17 @@ int sdrx_chan_bank_set_state(sdrx_chan_bank_t* b, const void* host_buf)
     }
     if (!ok) { set_error("sdrx_chan_bank_set_state: the state was taken from a bank with another configuration"); return SDRX_EINVAL; }
     p = q; (void)get(); (void)get();
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     for (Group* g : b->groups) {
         g->T = get(); (void)get();
         for (size_t si = 0; si < g->bufs.size(); si++) {
             (void)get();
             const size_t bytes = (size_t)g->plan.streams[si].hist_len * 4;
-            SDRX_HIP(hipMemcpyAsync(g->bufs[si].hist[g->bufs[si].cur], p, bytes, hipMemcpyHostToDevice, b->stream));
+            SDRX_HIP(hipMemcpyAsync(g->bufs[si].hist[g->bufs[si].cur], p, bytes, hipMemcpyHostToDevice, b->core.stream));
             p += bytes;
         }
     }
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     for (auto& ch : b->ch) { ch.avail = 0; ch.last_off = 0; ch.last_n = 0; }     // the queues belong to the old timeline
     return SDRX_OK;
 }
@@ -513,8 +504,8 @@ int32_t sdrx_chan_bank_group_count(const sdrx_chan_bank_t* b) { return b ? (int3
 int sdrx_chan_bank_reset(sdrx_chan_bank_t* b)
 {
     if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     for (Group* g : b->groups) free_group(g);
     b->groups.clear();
     std::vector<int> all;
@@ -530,7 +521,7 @@ int sdrx_chan_bank_feed_dev(sdrx_chan_bank_t* b, const int16_t* d_iq, int64_t n_
     if (!b || n_cplx < 0 || (n_cplx > 0 && !d_iq)) { set_error("sdrx_chan_bank_feed_dev: bad argument"); return SDRX_EINVAL; }
     if (reinterpret_cast<uintptr_t>(d_iq) & 3u) { set_error("sdrx_chan_bank_feed_dev: d_iq must be 4-byte aligned"); return SDRX_EINVAL; }
     if (n_cplx == 0) return SDRX_OK;
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     const uint32_t* in = reinterpret_cast<const uint32_t*>(d_iq);
     int rc = feed_passthrough(b, in, n_cplx); if (rc) return rc;
     for (Group* g : b->groups) { rc = feed_group(b, g, in, n_cplx); if (rc) return rc; }
@@ -541,10 +532,10 @@ int sdrx_chan_bank_feed(sdrx_chan_bank_t* b, const int16_t* iq, int64_t n_cplx)
 {
     if (!b || n_cplx < 0 || (n_cplx > 0 && !iq)) { set_error("sdrx_chan_bank_feed: bad argument"); return SDRX_EINVAL; }
     if (n_cplx == 0) return SDRX_OK;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));            // staging buffer may still be read by the previous feed
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));            // staging buffer may still be read by the previous feed
     int rc = b->stage_in.reserve((size_t)n_cplx * 4); if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(b->stage_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, b->stream));
+    SDRX_HIP(hipMemcpyAsync(b->stage_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, b->core.stream));
     return sdrx_chan_bank_feed_dev(b, static_cast<const int16_t*>(b->stage_in.p), n_cplx);
 }
 
@@ -557,20 +548,20 @@ int64_t sdrx_chan_bank_available(sdrx_chan_bank_t* b, int32_t c)
 int64_t sdrx_chan_bank_read(sdrx_chan_bank_t* b, int32_t c, int16_t* out_iq, int64_t cap)
 {
     if (!b || c < 0 || c >= (int32_t)b->ch.size() || cap < 0 || (cap > 0 && !out_iq)) { set_error("sdrx_chan_bank_read: bad argument"); return SDRX_EINVAL; }
-    if (hipSetDevice(b->device) != hipSuccess) return SDRX_EHIP;
+    if (hipSetDevice(b->core.device) != hipSuccess) return SDRX_EHIP;
     Channel& ch = b->ch[(size_t)c];
     const int64_t n = std::min(cap, ch.avail);
     if (n == 0) return 0;
-    hipError_t e = hipMemcpyAsync(out_iq, ch.out.p, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream);
+    hipError_t e = hipMemcpyAsync(out_iq, ch.out.p, (size_t)n * 4, hipMemcpyDeviceToHost, b->core.stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(read)", __FILE__, __LINE__);
     const int64_t rest = ch.avail - n;
     if (rest > 0) {                                        // partial read: compact the queue
         int rc = b->scratch.reserve((size_t)rest * 4); if (rc) return rc;
-        e = hipMemcpyAsync(b->scratch.p, static_cast<uint32_t*>(ch.out.p) + n, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ch.out.p, b->scratch.p, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->stream);
+        e = hipMemcpyAsync(b->scratch.p, static_cast<uint32_t*>(ch.out.p) + n, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->core.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ch.out.p, b->scratch.p, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->core.stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(compact)", __FILE__, __LINE__);
     }
-    e = hipStreamSynchronize(b->stream);
+    e = hipStreamSynchronize(b->core.stream);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
     ch.avail = rest; ch.last_off = 0; ch.last_n = 0;
     return n;
@@ -582,11 +573,11 @@ int64_t sdrx_chan_bank_skip(sdrx_chan_bank_t* b, int32_t c, int64_t n)
     Channel& ch = b->ch[(size_t)c];
     if (n < 0 || n >= ch.avail) { const int64_t k = ch.avail; ch.avail = 0; ch.last_off = 0; ch.last_n = 0; return k; }
     if (n == 0) return 0;
-    if (hipSetDevice(b->device) != hipSuccess) return SDRX_EHIP;
+    if (hipSetDevice(b->core.device) != hipSuccess) return SDRX_EHIP;
     const int64_t rest = ch.avail - n;
     int rc = b->scratch.reserve((size_t)rest * 4); if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(b->scratch.p, static_cast<uint32_t*>(ch.out.p) + n, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ch.out.p, b->scratch.p, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->stream);
+    hipError_t e = hipMemcpyAsync(b->scratch.p, static_cast<uint32_t*>(ch.out.p) + n, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->core.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ch.out.p, b->scratch.p, (size_t)rest * 4, hipMemcpyDeviceToDevice, b->core.stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(skip)", __FILE__, __LINE__);
     ch.avail = rest; ch.last_off = 0; ch.last_n = 0;
     return n;
@@ -601,56 +592,20 @@ int sdrx_chan_bank_last_dev(sdrx_chan_bank_t* b, int32_t c, const int16_t** d_ou
     return SDRX_OK;
 }
 
-int sdrx_chan_bank_sync(sdrx_chan_bank_t* b)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    return SDRX_OK;
-}
+int sdrx_chan_bank_sync(sdrx_chan_bank_t* b) { return b ? b->core.sync() : SDRX_EINVAL; }
 
 int sdrx_chan_bank_get_stream(sdrx_chan_bank_t* b, void** hip_stream)
 {
     if (!b || !hip_stream) { set_error("sdrx_chan_bank_get_stream: null argument"); return SDRX_EINVAL; }
-    *hip_stream = b->stream;
-    return SDRX_OK;
+    return b->core.get_stream(hip_stream);
 }
 
-int sdrx_chan_bank_set_stream(sdrx_chan_bank_t* b, void* hip_stream)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    b->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : b->own_stream;
-    return SDRX_OK;
-}
+int sdrx_chan_bank_set_stream(sdrx_chan_bank_t* b, void* hip_stream) { return b ? b->core.set_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_chan_bank_set_timing(sdrx_chan_bank_t* b, int enabled)
-{
-    if (!b) return SDRX_EINVAL;
-    b->timer.enabled = enabled != 0;
-    return SDRX_OK;
-}
+int sdrx_chan_bank_set_timing(sdrx_chan_bank_t* b, int enabled) { return b ? b->core.set_timing(enabled) : SDRX_EINVAL; }
 
-int sdrx_chan_bank_get_timing(sdrx_chan_bank_t* b, double* total_ms, int64_t* feeds, int reset)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    int rc = b->timer.collect(b->stream); if (rc) return rc;
-    if (total_ms) *total_ms = b->timer.total_ms;
-    if (feeds) *feeds = b->timer.count;
-    if (reset) { b->timer.total_ms = 0; b->timer.count = 0; }
-    return SDRX_OK;
-}
+int sdrx_chan_bank_get_timing(sdrx_chan_bank_t* b, double* total_ms, int64_t* feeds, int reset) { return b ? b->core.get_timing(total_ms, feeds, reset) : SDRX_EINVAL; }
 
-int sdrx_chan_bank_last_launch(const sdrx_chan_bank_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes)
-{
-    if (!b) return SDRX_EINVAL;
-    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", b->last_name);
-    if (grid) *grid = b->last_grid;
-    if (block) *block = b->last_block;
-    if (lds_bytes) *lds_bytes = b->last_lds;
-    return SDRX_OK;
-}
+int sdrx_chan_bank_last_launch(const sdrx_chan_bank_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes) { return b ? b->core.last_launch(kernel_name, name_cap, grid, block, lds_bytes) : SDRX_EINVAL; }
 
 } // extern "C"

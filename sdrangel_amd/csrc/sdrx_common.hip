@@ -101,6 +101,78 @@ void EventTimer::release()
     ev.clear(); used = 0;
 }
 
+int HandleCore::open(int dev)
+{
+    int rc = check_device(dev); if (rc) return rc;
+    SDRX_HIP(hipSetDevice(dev));
+    device = dev;
+    hipError_t e = hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__);
+    stream = own_stream;
+    return SDRX_OK;
+}
+
+void HandleCore::close()
+{
+    if (own_stream) (void)hipStreamSynchronize(own_stream);
+    timer.release();
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    own_stream = stream = nullptr;
+}
+
+int HandleCore::sync()
+{
+    SDRX_HIP(hipSetDevice(device));
+    SDRX_HIP(hipStreamSynchronize(stream));
+    return SDRX_OK;
+}
+
+int HandleCore::set_stream(void* hip_stream)
+{
+    SDRX_HIP(hipSetDevice(device));
+    SDRX_HIP(hipStreamSynchronize(stream));               // order pending work before switching
+    stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : own_stream;
+    return SDRX_OK;
+}
+
+int HandleCore::get_stream(void** hip_stream) const
+{
+    if (!hip_stream) return SDRX_EINVAL;
+    *hip_stream = stream;
+    return SDRX_OK;
+}
+
+int HandleCore::set_timing(int enabled)
+{
+    timer.enabled = enabled != 0;
+    return SDRX_OK;
+}
+
+int HandleCore::get_timing(double* total_ms, int64_t* count, int reset)
+{
+    SDRX_HIP(hipSetDevice(device));
+    int rc = timer.collect(stream); if (rc) return rc;
+    if (total_ms) *total_ms = timer.total_ms;
+    if (count) *count = timer.count;
+    if (reset) { timer.total_ms = 0; timer.count = 0; }
+    return SDRX_OK;
+}
+
+void HandleCore::note_launch(const char* name, int grid, int block, int lds)
+{
+    snprintf(last.name, sizeof last.name, "%s", name);
+    last.grid = grid; last.block = block; last.lds = lds;
+}
+
+int HandleCore::last_launch(char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes) const
+{
+    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", last.name);
+    if (grid) *grid = last.grid;
+    if (block) *block = last.block;
+    if (lds_bytes) *lds_bytes = last.lds;
+    return SDRX_OK;
+}
+
 } // namespace sdrx
 
 extern "C" {

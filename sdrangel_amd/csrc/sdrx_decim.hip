@@ -186,12 +186,12 @@ static bool pick(int L, int fc, int pre, bool u8, ChainEntry* e)
 using namespace sdrx;
 
 struct sdrx_decim {
-    int device = 0, log2 = 0, fcpos = 2, bits = 12, pre = 0, post = 0, group = 2;
+    HandleCore core;
+    int log2 = 0, fcpos = 2, bits = 12, pre = 0, post = 0, group = 2;
     int cus = 256;
     bool u8 = false;              // DecimatorsU flavour: quint8 I/Q input, value = byte - in_shift
     int in_shift = 0;
     int bps = 4;                  // bytes per complex input sample
-    hipStream_t own_stream = nullptr, stream = nullptr;
     uint32_t* d_hist[2] = { nullptr, nullptr };
     int cur = 0;
     DevBuf d_in, d_out, d_flags;
@@ -203,9 +203,6 @@ struct sdrx_decim {
     int path = 0;                 // 0 auto (FAST + flagged EXACT), 1 exact only, 2 fast only (debug: no fallback)
     ChainEntry k{ nullptr, nullptr, "", "", 0, 0, nullptr, "", 0, nullptr, nullptr, 0, 0 };
     bool mfma = true;             // half-band engine of the FAST kernel: matrix cores unless SDRX_DECIM_ENGINE=valu (read at create)
-    char last_name[96] = "";
-    int last_grid = 0, last_block = 0, last_lds = 0;
-    EventTimer timer;
     // pinned, double-buffered host path (sdrx_decim_ring_*): the caller's receive buffers ARE slots of this ring
     struct Ring {
         int n_slots = 0, flush = 1;
@@ -317,7 +314,7 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
         d_iq[i] = d_iq_in[i]; n_cplx[i] = n_cplx_in[i]; d_out[i] = d_out_in[i];
         hs[i]->flag_chunks = 0;
         long used = 0;
-        int rc = run_transition(hs[i], h->stream, d_iq[i], n_cplx[i], d_out[i], &used); if (rc) return rc;
+        int rc = run_transition(hs[i], h->core.stream, d_iq[i], n_cplx[i], d_out[i], &used); if (rc) return rc;
         if (used) {
             d_iq[i] = static_cast<const char*>(d_iq[i]) + used * hs[i]->bps;
             d_out[i] += 2 * (used >> hs[i]->log2);
@@ -333,14 +330,13 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
             const int block = 256;
             long grid = (n_cplx[i] + block - 1) / block; if (grid > 4096) grid = 4096;
             if (h->u8)
-                hipLaunchKernelGGL(decim1_u8_kernel, dim3((unsigned)grid), dim3(block), 0, h->stream,
+                hipLaunchKernelGGL(decim1_u8_kernel, dim3((unsigned)grid), dim3(block), 0, h->core.stream,
                                    static_cast<const uint16_t*>(d_iq[i]), reinterpret_cast<uint32_t*>(d_out[i]), n_cplx[i], h->pre, h->in_shift);
             else
-                hipLaunchKernelGGL(decim1_kernel, dim3((unsigned)grid), dim3(block), 0, h->stream,
+                hipLaunchKernelGGL(decim1_kernel, dim3((unsigned)grid), dim3(block), 0, h->core.stream,
                                    static_cast<const uint32_t*>(d_iq[i]), reinterpret_cast<uint32_t*>(d_out[i]), n_cplx[i], h->pre);
             SDRX_HIP(hipGetLastError());
-            snprintf(h->last_name, sizeof h->last_name, "decim1_kernel");
-            h->last_grid = (int)grid; h->last_block = block; h->last_lds = 0;
+            h->core.note_launch("decim1_kernel", (int)grid, block, 0);
         }
         return SDRX_OK;
     }
@@ -354,7 +350,7 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
         j.flags = nullptr; j.n_in = n_cplx[i] > 0 ? n_cplx[i] : 0; j.n_units = 0;
     }
     bool have_flags = false;
-    int trc = h->timer.begin(h->stream); if (trc) return trc;
+    int trc = h->core.timer.begin(h->core.stream); if (trc) return trc;
     if (h->path != 1) {
         // FAST: one wave per segment of `spw` sub-chunks (multiple of 4 = one flag chunk), 4 warm-up sub-chunks -- or, for
         // calls too short for that (fast_nw), four waves per segment on sub-chunks of 4096 samples with one warm-up sub-chunk
@@ -415,11 +411,12 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
         }
         const long segs = (max_sub + spw - 1) / spw;
         hipLaunchKernelGGL(h->mfma ? (nw == 1 ? h->k.fast_mx : h->k.fast4_mx) : (nw == 1 ? h->k.fast : h->k.fast4),
-                           dim3((unsigned)segs, (unsigned)n), dim3(64 * nw), 0, h->stream, jobs, (int)spw, h->post, h->in_shift);
+                           dim3((unsigned)segs, (unsigned)n), dim3(64 * nw), 0, h->core.stream, jobs, (int)spw, h->post, h->in_shift);
         SDRX_HIP(hipGetLastError());
-        snprintf(h->last_name, sizeof h->last_name, "%s%s", nw == 1 ? h->k.fast_name : h->k.fast4_name, h->mfma ? "+mfma" : "");
-        h->last_grid = (int)(segs * n); h->last_block = 64 * nw;
-        h->last_lds = h->mfma ? (nw == 1 ? h->k.fast_mx_lds : h->k.fast4_mx_lds) : (nw == 1 ? h->k.fast_lds : h->k.fast4_lds);
+        char name[96];
+        snprintf(name, sizeof name, "%s%s", nw == 1 ? h->k.fast_name : h->k.fast4_name, h->mfma ? "+mfma" : "");
+        h->core.note_launch(name, (int)(segs * n), 64 * nw,
+                            h->mfma ? (nw == 1 ? h->k.fast_mx_lds : h->k.fast4_mx_lds) : (nw == 1 ? h->k.fast_lds : h->k.fast4_lds));
     }
     if (h->path != 2) {
         for (int i = 0; i < n; i++) jobs.j[i].n_units = (int)((jobs.j[i].n_in + DC_CHUNK - 1) / DC_CHUNK);
@@ -430,14 +427,11 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
             const long cap = (h->cus + n - 1) / n;
             if (segs > cap) segs = cap;
         }
-        hipLaunchKernelGGL(h->k.fn, dim3((unsigned)segs, (unsigned)n), dim3(DC_THREADS), 0, h->stream, jobs, cps, h->post, h->in_shift);
+        hipLaunchKernelGGL(h->k.fn, dim3((unsigned)segs, (unsigned)n), dim3(DC_THREADS), 0, h->core.stream, jobs, cps, h->post, h->in_shift);
         SDRX_HIP(hipGetLastError());
-        if (h->path == 1) {
-            snprintf(h->last_name, sizeof h->last_name, "%s", h->k.name);
-            h->last_grid = (int)(segs * n); h->last_block = DC_THREADS; h->last_lds = h->k.lds;
-        }
+        if (h->path == 1) h->core.note_launch(h->k.name, (int)(segs * n), DC_THREADS, h->k.lds);
     }
-    trc = h->timer.end(h->stream); if (trc) return trc;
+    trc = h->core.timer.end(h->core.stream); if (trc) return trc;
     const int hist_dw = DC_CHUNK * h->bps / 4;
     HistJobs hj;
     std::memset(&hj, 0, sizeof hj);
@@ -445,7 +439,7 @@ static int launch_batch(sdrx_decim* const* hs, int n, const void* const* d_iq_in
         hj.j[i].old_hist = hs[i]->d_hist[hs[i]->cur]; hj.j[i].in = static_cast<const uint32_t*>(d_iq[i]);
         hj.j[i].new_hist = hs[i]->d_hist[hs[i]->cur ^ 1]; hj.j[i].n_in_dw = jobs.j[i].n_in * h->bps / 4;
     }
-    hipLaunchKernelGGL(hist_update_kernel, dim3((unsigned)((hist_dw + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, hj, hist_dw);
+    hipLaunchKernelGGL(hist_update_kernel, dim3((unsigned)((hist_dw + 255) / 256), (unsigned)n), dim3(256), 0, h->core.stream, hj, hist_dw);
     SDRX_HIP(hipGetLastError());
     for (int i = 0; i < n; i++) hs[i]->cur ^= 1;
     return SDRX_OK;
@@ -494,9 +488,9 @@ static int ring_flush(sdrx_decim* h)
         const size_t last = (size_t)(s0 + run - 1);
         if (elems) SDRX_HIP(hipMemcpyAsync(r.d_in + in_off, r.h_in + in_off, (size_t)elems * esz, hipMemcpyHostToDevice, r.s_in));
         SDRX_HIP(hipEventRecord(r.ev_in[last], r.s_in));
-        SDRX_HIP(hipStreamWaitEvent(h->stream, r.ev_in[last], 0));
+        SDRX_HIP(hipStreamWaitEvent(h->core.stream, r.ev_in[last], 0));
         int rc = launch(h, r.d_in + in_off, n_cplx, reinterpret_cast<int16_t*>(r.d_out + out_off)); if (rc) return rc;
-        SDRX_HIP(hipEventRecord(r.ev_k[last], h->stream));
+        SDRX_HIP(hipEventRecord(r.ev_k[last], h->core.stream));
         SDRX_HIP(hipStreamWaitEvent(r.s_out, r.ev_k[last], 0));
         if (n_out) SDRX_HIP(hipMemcpyAsync(r.h_out + out_off, r.d_out + out_off, (size_t)n_out * 4, hipMemcpyDeviceToHost, r.s_out));
         SDRX_HIP(hipEventRecord(r.ev[last], r.s_out));
@@ -517,8 +511,8 @@ int sdrx_decim_ring_create(sdrx_decim_t* h, int32_t slot_elems, int32_t n_slots,
     if (!h || n_slots < 2 || slot_elems <= 0) { set_error("sdrx_decim_ring_create: need a handle, >= 2 slots, a positive slot size"); return SDRX_EINVAL; }
     if (slot_elems % h->group) { set_error("sdrx_decim_ring_create: the slot size must be a whole number of decimation groups (sdrx_decim_group_int16)"); return SDRX_EINVAL; }
     if ((size_t)slot_elems * (h->u8 ? 1 : 2) % 16) { set_error("sdrx_decim_ring_create: slot bytes must be a multiple of 16"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     ring_free(h);
     sdrx_decim::Ring& r = h->ring;
     r.n_slots = n_slots; r.flush = flush_slots < 1 ? 1 : (flush_slots > n_slots - 1 ? n_slots - 1 : flush_slots);
@@ -544,8 +538,8 @@ int sdrx_decim_ring_create(sdrx_decim_t* h, int32_t slot_elems, int32_t n_slots,
 int sdrx_decim_ring_destroy(sdrx_decim_t* h)
 {
     if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     ring_free(h);
     return SDRX_OK;
 }
@@ -567,7 +561,7 @@ int sdrx_decim_ring_submit(sdrx_decim_t* h, int32_t n_elems)
     const size_t sl = (size_t)(r.head % r.n_slots);
     if (r.state[sl] != 1) { set_error("sdrx_decim_ring_submit: no acquired slot"); return SDRX_ESTATE; }
     if (n_elems < 0 || n_elems > r.slot_elems) { set_error("sdrx_decim_ring_submit: more elements than the slot holds"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     r.n_elems[sl] = n_elems; r.state[sl] = 2; r.head++;
     // launch once `flush` slots are waiting, when the run reaches the end of the ring, or when the slot is short
     if (r.head - r.flushed >= r.flush || r.head % r.n_slots == 0 || n_elems != r.slot_elems) return ring_flush(h);
@@ -579,7 +573,7 @@ int sdrx_decim_ring_retire(sdrx_decim_t* h, const int16_t** out_iq, int32_t* n_o
     if (!h || !h->ring.n_slots || !out_iq || !n_out_cplx) { set_error("sdrx_decim_ring_retire: bad argument"); return SDRX_EINVAL; }
     sdrx_decim::Ring& r = h->ring;
     if (r.tail >= r.head) { set_error("sdrx_decim_ring_retire: nothing submitted"); return SDRX_ESTATE; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     const size_t sl = (size_t)(r.tail % r.n_slots);
     if (r.state[sl] == 2) { int rc = ring_flush(h); if (rc) return rc; }
     SDRX_HIP(hipEventSynchronize(r.ev[(size_t)r.ev_of[sl]]));
@@ -617,12 +611,11 @@ static int create_common(sdrx_decim_t** out, int device, int log2_decim, int fcp
         set_error("sdrx_decim_create: log2 0..6, fcpos 0..2, input_bits 8|12|16");
         return SDRX_EINVAL;
     }
-    int rc = check_device(device);
-    if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_decim* h = new (std::nothrow) sdrx_decim;
     if (!h) return SDRX_ENOMEM;
-    h->device = device; h->log2 = log2_decim; h->fcpos = fcpos; h->bits = input_bits;
+    int rc = h->core.open(device);
+    if (rc) { delete h; return rc; }
+    h->log2 = log2_decim; h->fcpos = fcpos; h->bits = input_bits;
     h->u8 = u8; h->in_shift = shift; h->bps = u8 ? 2 : 4;
     shifts(input_bits, log2_decim, &h->pre, &h->post);
     h->group = group_int16(log2_decim, fcpos);
@@ -630,13 +623,10 @@ static int create_common(sdrx_decim_t** out, int device, int log2_decim, int fcp
     { const char* pe = getenv("SDRX_DECIM_PATH"); h->path = !pe ? 0 : !strcmp(pe, "exact") ? 1 : !strcmp(pe, "fast") ? 2 : 0; }
     { const char* pe = getenv("SDRX_DECIM_ENGINE"); h->mfma = !(pe && !strcmp(pe, "valu")); }
     if (log2_decim > 0 && !pick(log2_decim, fcpos, h->pre, u8, &h->k)) {
-        delete h; set_error("sdrx_decim_create: no kernel for this configuration"); return SDRX_EINVAL;
+        sdrx_decim_destroy(h); set_error("sdrx_decim_create: no kernel for this configuration"); return SDRX_EINVAL;
     }
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-    h->stream = h->own_stream;
     for (int i = 0; i < 2; i++) {
-        e = hipMalloc(reinterpret_cast<void**>(&h->d_hist[i]), (size_t)DC_CHUNK * h->bps);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_hist[i]), (size_t)DC_CHUNK * h->bps);
         if (e != hipSuccess) { sdrx_decim_destroy(h); return hip_fail(e, "hipMalloc(hist)", __FILE__, __LINE__); }
     }
     *out = h;
@@ -646,13 +636,12 @@ static int create_common(sdrx_decim_t** out, int device, int log2_decim, int fcp
 int sdrx_decim_destroy(sdrx_decim_t* h)
 {
     if (!h) return SDRX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->own_stream) { (void)hipStreamSynchronize(h->own_stream); }
+    (void)hipSetDevice(h->core.device);
     for (int i = 0; i < 2; i++) if (h->d_hist[i]) (void)hipFree(h->d_hist[i]);
     if (h->d_rings) (void)hipFree(h->d_rings);
-    h->d_in.release(); h->d_out.release(); h->d_flags.release(); h->timer.release();
+    h->d_in.release(); h->d_out.release(); h->d_flags.release();
     ring_free(h);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->core.close();
     delete h;
     return SDRX_OK;
 }
@@ -660,35 +649,22 @@ int sdrx_decim_destroy(sdrx_decim_t* h)
 int sdrx_decim_reset(sdrx_decim_t* h)
 {
     if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     // a zero SAMPLE: all-zero bytes for int16 input, the byte `in_shift` for the unsigned 8-bit flavour
-    SDRX_HIP(hipMemsetAsync(h->d_hist[h->cur], h->u8 ? h->in_shift : 0, (size_t)DC_CHUNK * h->bps, h->stream));
+    SDRX_HIP(hipMemsetAsync(h->d_hist[h->cur], h->u8 ? h->in_shift : 0, (size_t)DC_CHUNK * h->bps, h->core.stream));
     h->rings_live = false; h->since_load = 0;
     return SDRX_OK;
 }
 
-int sdrx_decim_set_stream(sdrx_decim_t* h, void* hip_stream)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));            // order pending work before switching
-    h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
-    return SDRX_OK;
-}
+int sdrx_decim_set_stream(sdrx_decim_t* h, void* hip_stream) { return h ? h->core.set_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_decim_sync(sdrx_decim_t* h)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    return SDRX_OK;
-}
+int sdrx_decim_sync(sdrx_decim_t* h) { return h ? h->core.sync() : SDRX_EINVAL; }
 
 int sdrx_decim_process_u8(sdrx_decim_t* h, const uint8_t* iq, int32_t n_uint8, int16_t* out_iq, int32_t* n_out_cplx)
 {
     if (!h || !h->u8) { set_error("sdrx_decim_process_u8: handle was not made by sdrx_decim_create_u8"); return SDRX_ESTATE; }
     if (n_uint8 < 0 || (n_uint8 > 0 && (!iq || !out_iq))) { set_error("sdrx_decim_process_u8: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     const int64_t groups = n_uint8 / h->group;
     const int64_t n_cplx = groups * (h->group / 2);
     const int64_t n_out = n_cplx >> h->log2;
@@ -696,11 +672,11 @@ int sdrx_decim_process_u8(sdrx_decim_t* h, const uint8_t* iq, int32_t n_uint8, i
     if (n_cplx == 0) { h->flag_chunks = 0; return SDRX_OK; }
     int rc = h->d_in.reserve((size_t)n_cplx * 2); if (rc) return rc;
     rc = h->d_out.reserve((size_t)n_out * 4); if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 2, hipMemcpyHostToDevice, h->stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 2, hipMemcpyHostToDevice, h->core.stream));
     rc = launch(h, h->d_in.p, (long)n_cplx, static_cast<int16_t*>(h->d_out.p));
     if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(out_iq, h->d_out.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipMemcpyAsync(out_iq, h->d_out.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
@@ -711,7 +687,7 @@ int sdrx_decim_process_dev_u8(sdrx_decim_t* h, const uint8_t* d_iq, int64_t n_ui
     if ((reinterpret_cast<uintptr_t>(d_iq) & 7u) || (reinterpret_cast<uintptr_t>(d_out_iq) & 3u)) {
         set_error("sdrx_decim_process_dev_u8: d_iq must be 8-byte aligned"); return SDRX_EINVAL;
     }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     const int64_t groups = n_uint8 / h->group;
     const int64_t n_cplx = groups * (h->group / 2);
     if (n_out_cplx) *n_out_cplx = n_cplx >> h->log2;
@@ -725,7 +701,7 @@ int sdrx_decim_process_dev(sdrx_decim_t* h, const int16_t* d_iq, int64_t n_int16
     if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) || (reinterpret_cast<uintptr_t>(d_out_iq) & 3u)) {
         set_error("sdrx_decim_process_dev: d_iq must be 16-byte aligned"); return SDRX_EINVAL;
     }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     const int64_t groups = n_int16 / h->group;            // trailing partial group dropped (decimators.h:3492)
     const int64_t n_cplx = groups * (h->group / 2);
     if (n_out_cplx) *n_out_cplx = n_cplx >> h->log2;
@@ -738,10 +714,10 @@ int sdrx_decim_process_dev_batch(sdrx_decim_t* const* handles, int32_t n_handles
     if (!handles || n_handles <= 0 || !d_iq || !n_int16 || !d_out_iq) { set_error("sdrx_decim_process_dev_batch: bad argument"); return SDRX_EINVAL; }
     sdrx_decim* h0 = handles[0];
     if (!h0) { set_error("sdrx_decim_process_dev_batch: null handle"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h0->device));
+    SDRX_HIP(hipSetDevice(h0->core.device));
     for (int i = 0; i < n_handles; i++) {
         sdrx_decim* h = handles[i];
-        if (!h || h->u8 != h0->u8 || h->device != h0->device || h->log2 != h0->log2 || h->fcpos != h0->fcpos || h->bits != h0->bits ||
+        if (!h || h->u8 != h0->u8 || h->core.device != h0->core.device || h->log2 != h0->log2 || h->fcpos != h0->fcpos || h->bits != h0->bits ||
             h->in_shift != h0->in_shift || h->path != h0->path) {
             set_error("sdrx_decim_process_dev_batch: all handles must share one configuration and device"); return SDRX_EINVAL;
         }
@@ -750,9 +726,9 @@ int sdrx_decim_process_dev_batch(sdrx_decim_t* const* handles, int32_t n_handles
         if ((reinterpret_cast<uintptr_t>(d_iq[i]) & (h0->u8 ? 7u : 15u)) || (reinterpret_cast<uintptr_t>(d_out_iq[i]) & 3u)) {
             set_error("sdrx_decim_process_dev_batch: d_iq must be 16-byte aligned (8 for the u8 flavour)"); return SDRX_EINVAL;
         }
-        if (h->stream != h0->stream) {                       // the batch runs on handles[0]'s stream: join it once
-            SDRX_HIP(hipStreamSynchronize(h->stream));
-            h->stream = h0->stream;
+        if (h->core.stream != h0->core.stream) {                       // the batch runs on handles[0]'s stream: join it once
+            SDRX_HIP(hipStreamSynchronize(h->core.stream));
+            h->core.stream = h0->core.stream;
         }
     }
     for (int base = 0; base < n_handles; base += DJ_MAX) {
@@ -766,12 +742,12 @@ int sdrx_decim_process_dev_batch(sdrx_decim_t* const* handles, int32_t n_handles
         }
         sdrx_decim* first = handles[base];
         if (base) {                                          // later sub-batches: keep timing / last_launch on handles[0]
-            std::swap(first->timer, h0->timer);
+            std::swap(first->core.timer, h0->core.timer);
         }
         const int rc = launch_batch(handles + base, n, in, nc, out);
         if (base) {
-            std::swap(first->timer, h0->timer);
-            snprintf(h0->last_name, sizeof h0->last_name, "%s", first->last_name);
+            std::swap(first->core.timer, h0->core.timer);
+            snprintf(h0->core.last.name, sizeof h0->core.last.name, "%s", first->core.last.name);
         }
         if (rc) return rc;
     }
@@ -782,7 +758,7 @@ int sdrx_decim_process(sdrx_decim_t* h, const int16_t* iq, int32_t n_int16, int1
 {
     if (h && h->u8) { set_error("sdrx_decim_process: handle takes unsigned 8-bit input, use the _u8 call"); return SDRX_ESTATE; }
     if (!h || n_int16 < 0 || (n_int16 > 0 && (!iq || !out_iq))) { set_error("sdrx_decim_process: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     const int64_t groups = n_int16 / h->group;
     const int64_t n_cplx = groups * (h->group / 2);
     const int64_t n_out = n_cplx >> h->log2;
@@ -790,11 +766,11 @@ int sdrx_decim_process(sdrx_decim_t* h, const int16_t* iq, int32_t n_int16, int1
     if (n_cplx == 0) { h->flag_chunks = 0; return SDRX_OK; }
     int rc = h->d_in.reserve((size_t)n_cplx * 4); if (rc) return rc;
     rc = h->d_out.reserve((size_t)n_out * 4); if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, h->stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, h->core.stream));
     rc = launch(h, h->d_in.p, (long)n_cplx, static_cast<int16_t*>(h->d_out.p));
     if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(out_iq, h->d_out.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipMemcpyAsync(out_iq, h->d_out.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
@@ -804,55 +780,33 @@ int sdrx_decim_get_state(sdrx_decim_t* h, void* host_buf)
 {
     if (!h || !host_buf) return SDRX_EINVAL;
     if (h->rings_live) { set_error("sdrx_decim_get_state: the handle still runs on loaded stage states (first 4096 samples after sdrx_decim_load_stages); save those with sdrx_decim_save_stages"); return SDRX_ESTATE; }
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipMemcpyAsync(host_buf, h->d_hist[h->cur], (size_t)DC_CHUNK * h->bps, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipMemcpyAsync(host_buf, h->d_hist[h->cur], (size_t)DC_CHUNK * h->bps, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
 int sdrx_decim_set_state(sdrx_decim_t* h, const void* host_buf)
 {
     if (!h || !host_buf) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipMemcpyAsync(h->d_hist[h->cur], host_buf, (size_t)DC_CHUNK * h->bps, hipMemcpyHostToDevice, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipMemcpyAsync(h->d_hist[h->cur], host_buf, (size_t)DC_CHUNK * h->bps, hipMemcpyHostToDevice, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     h->rings_live = false;
     return SDRX_OK;
 }
 
-int sdrx_decim_set_timing(sdrx_decim_t* h, int enabled)
-{
-    if (!h) return SDRX_EINVAL;
-    h->timer.enabled = enabled != 0;
-    return SDRX_OK;
-}
+int sdrx_decim_set_timing(sdrx_decim_t* h, int enabled) { return h ? h->core.set_timing(enabled) : SDRX_EINVAL; }
 
-int sdrx_decim_get_timing(sdrx_decim_t* h, double* total_ms, int64_t* launches, int reset)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    int rc = h->timer.collect(h->stream); if (rc) return rc;
-    if (total_ms) *total_ms = h->timer.total_ms;
-    if (launches) *launches = h->timer.count;
-    if (reset) { h->timer.total_ms = 0; h->timer.count = 0; }
-    return SDRX_OK;
-}
+int sdrx_decim_get_timing(sdrx_decim_t* h, double* total_ms, int64_t* launches, int reset) { return h ? h->core.get_timing(total_ms, launches, reset) : SDRX_EINVAL; }
 
-int sdrx_decim_last_launch(const sdrx_decim_t* h, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes)
-{
-    if (!h) return SDRX_EINVAL;
-    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", h->last_name);
-    if (grid) *grid = h->last_grid;
-    if (block) *block = h->last_block;
-    if (lds_bytes) *lds_bytes = h->last_lds;
-    return SDRX_OK;
-}
+int sdrx_decim_last_launch(const sdrx_decim_t* h, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes) { return h ? h->core.last_launch(kernel_name, name_cap, grid, block, lds_bytes) : SDRX_EINVAL; }
 
 int sdrx_decim_last_fallback(sdrx_decim_t* h, int64_t* flagged_chunks, int64_t* total_chunks, uint8_t* flags_out, int64_t cap)
 {
     if (!h || cap < 0) { set_error("sdrx_decim_last_fallback: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     const long total = h->flag_chunks;
     long flagged = 0;
     if (total > 0) {
@@ -905,27 +859,27 @@ int sdrx_decim_stages_destroy(sdrx_decim_stages_t* s)
 
 int sdrx_decim_save_stages(sdrx_decim_t* h, sdrx_decim_stages_t* s)
 {
-    if (!h || !s || h->device != s->device) { set_error("sdrx_decim_save_stages: bad argument (handle and stage set must live on one device)"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    if (!h || !s || h->core.device != s->device) { set_error("sdrx_decim_save_stages: bad argument (handle and stage set must live on one device)"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(h->core.device));
     if (h->log2 == 0) return SDRX_OK;                                       // decimate1 touches no filter
     if (h->rings_live) {
-        SDRX_HIP(hipMemcpyAsync(s->d_rings, h->d_rings, (size_t)h->log2 * SG_STAGE_DW * 4, hipMemcpyDeviceToDevice, h->stream));
+        SDRX_HIP(hipMemcpyAsync(s->d_rings, h->d_rings, (size_t)h->log2 * SG_STAGE_DW * 4, hipMemcpyDeviceToDevice, h->core.stream));
     } else {
         // steady state: the rings are a function of the last DC_CHUNK input samples (zero state in front of them is exact)
-        int rc = launch_serial(h, h->stream, h->d_hist[h->cur], DC_CHUNK, nullptr, s->d_rings, true); if (rc) return rc;
+        int rc = launch_serial(h, h->core.stream, h->d_hist[h->cur], DC_CHUNK, nullptr, s->d_rings, true); if (rc) return rc;
     }
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
 int sdrx_decim_load_stages(sdrx_decim_t* h, const sdrx_decim_stages_t* s)
 {
-    if (!h || !s || h->device != s->device) { set_error("sdrx_decim_load_stages: bad argument (handle and stage set must live on one device)"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    if (!h || !s || h->core.device != s->device) { set_error("sdrx_decim_load_stages: bad argument (handle and stage set must live on one device)"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(h->core.device));
     if (h->log2 == 0) return SDRX_OK;
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     if (!h->d_rings) SDRX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_rings), SG_DW * 4));
-    SDRX_HIP(hipMemcpyAsync(h->d_rings, s->d_rings, SG_DW * 4, hipMemcpyDeviceToDevice, h->stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_rings, s->d_rings, SG_DW * 4, hipMemcpyDeviceToDevice, h->core.stream));
     h->rings_live = true; h->since_load = 0;
     return SDRX_OK;
 }

@@ -83,8 +83,7 @@ __global__ void dccorr_hist_kernel(const uint32_t* __restrict__ old_hist, const 
 } // namespace
 
 struct sdrx_dccorr {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
     uint32_t* d_hist[2] = { nullptr, nullptr };
     int cur = 0;
     DevBuf d_in, d_out;
@@ -94,10 +93,10 @@ static int launch(sdrx_dccorr* h, const void* d_in, void* d_out, long n)
 {
     if (n <= 0) return SDRX_OK;
     const long tiles = (n + DC_TILE - 1) / DC_TILE;
-    hipLaunchKernelGGL(dccorr_kernel, dim3((unsigned)tiles), dim3(DC_NT), 0, h->stream,
+    hipLaunchKernelGGL(dccorr_kernel, dim3((unsigned)tiles), dim3(DC_NT), 0, h->core.stream,
                        h->d_hist[h->cur], static_cast<const uint32_t*>(d_in), static_cast<uint32_t*>(d_out), n);
     SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dccorr_hist_kernel, dim3(DC_WIN / 256), dim3(256), 0, h->stream,
+    hipLaunchKernelGGL(dccorr_hist_kernel, dim3(DC_WIN / 256), dim3(256), 0, h->core.stream,
                        h->d_hist[h->cur], static_cast<const uint32_t*>(d_in), h->d_hist[h->cur ^ 1], n);
     SDRX_HIP(hipGetLastError());
     h->cur ^= 1;
@@ -110,16 +109,12 @@ int sdrx_dccorr_create(sdrx_dccorr_t** out, int device)
 {
     if (!out) { set_error("sdrx_dccorr_create: null out"); return SDRX_EINVAL; }
     *out = nullptr;
-    int rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_dccorr* h = new (std::nothrow) sdrx_dccorr;
     if (!h) return SDRX_ENOMEM;
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-    h->stream = h->own_stream;
+    int rc = h->core.open(device);
+    if (rc) { delete h; return rc; }
     for (int i = 0; i < 2; i++) {
-        e = hipMalloc(reinterpret_cast<void**>(&h->d_hist[i]), DC_WIN * 4);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_hist[i]), DC_WIN * 4);
         if (e != hipSuccess) { sdrx_dccorr_destroy(h); return hip_fail(e, "hipMalloc(hist)", __FILE__, __LINE__); }
     }
     *out = h;
@@ -129,11 +124,10 @@ int sdrx_dccorr_create(sdrx_dccorr_t** out, int device)
 int sdrx_dccorr_destroy(sdrx_dccorr_t* h)
 {
     if (!h) return SDRX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
+    (void)hipSetDevice(h->core.device);
     for (int i = 0; i < 2; i++) if (h->d_hist[i]) (void)hipFree(h->d_hist[i]);
     h->d_in.release(); h->d_out.release();
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->core.close();
     delete h;
     return SDRX_OK;
 }
@@ -141,34 +135,21 @@ int sdrx_dccorr_destroy(sdrx_dccorr_t* h)
 int sdrx_dccorr_reset(sdrx_dccorr_t* h)
 {
     if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipMemsetAsync(h->d_hist[h->cur], 0, DC_WIN * 4, h->stream));     // == freshly constructed MovingAverageUtil members
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipMemsetAsync(h->d_hist[h->cur], 0, DC_WIN * 4, h->core.stream));     // == freshly constructed MovingAverageUtil members
     return SDRX_OK;
 }
 
-int sdrx_dccorr_set_stream(sdrx_dccorr_t* h, void* hip_stream)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
-    return SDRX_OK;
-}
+int sdrx_dccorr_set_stream(sdrx_dccorr_t* h, void* hip_stream) { return h ? h->core.set_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_dccorr_sync(sdrx_dccorr_t* h)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    return SDRX_OK;
-}
+int sdrx_dccorr_sync(sdrx_dccorr_t* h) { return h ? h->core.sync() : SDRX_EINVAL; }
 
 int sdrx_dccorr_process_dev(sdrx_dccorr_t* h, const int16_t* d_iq, int16_t* d_out_iq, int64_t n_cplx)
 {
     if (!h || n_cplx < 0 || (n_cplx > 0 && (!d_iq || !d_out_iq))) { set_error("sdrx_dccorr_process_dev: bad argument"); return SDRX_EINVAL; }
     if (d_iq == d_out_iq) { set_error("sdrx_dccorr_process_dev: not in place (a tile reads its neighbour's input)"); return SDRX_EINVAL; }
     if ((reinterpret_cast<uintptr_t>(d_iq) & 3u) || (reinterpret_cast<uintptr_t>(d_out_iq) & 3u)) { set_error("sdrx_dccorr_process_dev: 4-byte alignment"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     return launch(h, d_iq, d_out_iq, (long)n_cplx);
 }
 
@@ -176,13 +157,13 @@ int sdrx_dccorr_process(sdrx_dccorr_t* h, int16_t* iq, int64_t n_cplx)
 {
     if (!h || n_cplx < 0 || (n_cplx > 0 && !iq)) { set_error("sdrx_dccorr_process: bad argument"); return SDRX_EINVAL; }
     if (n_cplx == 0) return SDRX_OK;
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     int rc = h->d_in.reserve((size_t)n_cplx * 4); if (rc) return rc;
     rc = h->d_out.reserve((size_t)n_cplx * 4); if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, h->stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, h->core.stream));
     rc = launch(h, h->d_in.p, h->d_out.p, (long)n_cplx); if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(iq, h->d_out.p, (size_t)n_cplx * 4, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipMemcpyAsync(iq, h->d_out.p, (size_t)n_cplx * 4, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
@@ -271,8 +252,8 @@ void iqimb_kernel(IqImbState* __restrict__ states, const IqImbJob* __restrict__ 
 } // namespace
 
 struct sdrx_iqimb {
-    int device = 0, n_streams = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
+    int n_streams = 0;
     IqImbState* d_state = nullptr;
     IqImbJob* d_jobs = nullptr;
     IqImbJob* h_jobs = nullptr;               // pinned
@@ -286,13 +267,12 @@ int sdrx_iqimb_create(sdrx_iqimb_t** out, int device, int32_t n_streams)
 {
     if (!out || n_streams <= 0) { set_error("sdrx_iqimb_create: bad argument"); return SDRX_EINVAL; }
     *out = nullptr;
-    int rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_iqimb* h = new (std::nothrow) sdrx_iqimb;
     if (!h) return SDRX_ENOMEM;
-    h->device = device; h->n_streams = n_streams; h->stage.resize((size_t)n_streams);
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) { h->stream = h->own_stream; e = hipMalloc(reinterpret_cast<void**>(&h->d_state), sizeof(IqImbState) * (size_t)n_streams); }
+    int rc = h->core.open(device);
+    if (rc) { delete h; return rc; }
+    h->n_streams = n_streams; h->stage.resize((size_t)n_streams);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_state), sizeof(IqImbState) * (size_t)n_streams);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_jobs), sizeof(IqImbJob) * (size_t)n_streams);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_jobs), sizeof(IqImbJob) * (size_t)n_streams, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->jobs_ev, hipEventDisableTiming);
@@ -304,14 +284,14 @@ int sdrx_iqimb_create(sdrx_iqimb_t** out, int device, int32_t n_streams)
 int sdrx_iqimb_destroy(sdrx_iqimb_t* h)
 {
     if (!h) return SDRX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)hipSetDevice(h->core.device);
+    if (h->core.stream) (void)hipStreamSynchronize(h->core.stream);
     if (h->d_state) (void)hipFree(h->d_state);
     if (h->d_jobs) (void)hipFree(h->d_jobs);
     if (h->h_jobs) (void)hipHostFree(h->h_jobs);
     if (h->jobs_ev) (void)hipEventDestroy(h->jobs_ev);
     for (auto& b : h->stage) b.release();
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->core.close();
     delete h;
     return SDRX_OK;
 }
@@ -319,32 +299,19 @@ int sdrx_iqimb_destroy(sdrx_iqimb_t* h)
 int sdrx_iqimb_reset(sdrx_iqimb_t* h)
 {
     if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipMemsetAsync(h->d_state, 0, sizeof(IqImbState) * (size_t)h->n_streams, h->stream));   // == freshly constructed members
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipMemsetAsync(h->d_state, 0, sizeof(IqImbState) * (size_t)h->n_streams, h->core.stream));   // == freshly constructed members
     return SDRX_OK;
 }
 
-int sdrx_iqimb_set_stream(sdrx_iqimb_t* h, void* hip_stream)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
-    return SDRX_OK;
-}
+int sdrx_iqimb_set_stream(sdrx_iqimb_t* h, void* hip_stream) { return h ? h->core.set_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_iqimb_sync(sdrx_iqimb_t* h)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    return SDRX_OK;
-}
+int sdrx_iqimb_sync(sdrx_iqimb_t* h) { return h ? h->core.sync() : SDRX_EINVAL; }
 
 int sdrx_iqimb_process_dev(sdrx_iqimb_t* h, const int16_t* const* d_iq, int16_t* const* d_out_iq, const int64_t* n_cplx)
 {
     if (!h || !d_iq || !d_out_iq || !n_cplx) { set_error("sdrx_iqimb_process_dev: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     SDRX_HIP(hipEventSynchronize(h->jobs_ev));                 // the previous call's table has been uploaded
     for (int s = 0; s < h->n_streams; s++) {
         if (n_cplx[s] < 0 || (n_cplx[s] > 0 && (!d_iq[s] || !d_out_iq[s])) || (reinterpret_cast<uintptr_t>(d_iq[s]) & 3u) || (reinterpret_cast<uintptr_t>(d_out_iq[s]) & 3u)) {
@@ -352,9 +319,9 @@ int sdrx_iqimb_process_dev(sdrx_iqimb_t* h, const int16_t* const* d_iq, int16_t*
         }
         h->h_jobs[s] = IqImbJob{ reinterpret_cast<const uint32_t*>(d_iq[s]), reinterpret_cast<uint32_t*>(d_out_iq[s]), (long)n_cplx[s] };
     }
-    SDRX_HIP(hipMemcpyAsync(h->d_jobs, h->h_jobs, sizeof(IqImbJob) * (size_t)h->n_streams, hipMemcpyHostToDevice, h->stream));
-    SDRX_HIP(hipEventRecord(h->jobs_ev, h->stream));
-    hipLaunchKernelGGL(iqimb_kernel, dim3((unsigned)h->n_streams), dim3(64), 0, h->stream, h->d_state, h->d_jobs);
+    SDRX_HIP(hipMemcpyAsync(h->d_jobs, h->h_jobs, sizeof(IqImbJob) * (size_t)h->n_streams, hipMemcpyHostToDevice, h->core.stream));
+    SDRX_HIP(hipEventRecord(h->jobs_ev, h->core.stream));
+    hipLaunchKernelGGL(iqimb_kernel, dim3((unsigned)h->n_streams), dim3(64), 0, h->core.stream, h->d_state, h->d_jobs);
     SDRX_HIP(hipGetLastError());
     return SDRX_OK;
 }
@@ -362,18 +329,18 @@ int sdrx_iqimb_process_dev(sdrx_iqimb_t* h, const int16_t* const* d_iq, int16_t*
 int sdrx_iqimb_process(sdrx_iqimb_t* h, int16_t* const* iq, const int64_t* n_cplx)
 {
     if (!h || !iq || !n_cplx) { set_error("sdrx_iqimb_process: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     std::vector<const int16_t*> din((size_t)h->n_streams); std::vector<int16_t*> dout((size_t)h->n_streams);
     for (int s = 0; s < h->n_streams; s++) {
         if (n_cplx[s] < 0 || (n_cplx[s] > 0 && !iq[s])) { set_error("sdrx_iqimb_process: bad stream argument"); return SDRX_EINVAL; }
         int rc = h->stage[(size_t)s].reserve((size_t)(n_cplx[s] > 0 ? n_cplx[s] : 1) * 4); if (rc) return rc;
-        if (n_cplx[s]) SDRX_HIP(hipMemcpyAsync(h->stage[(size_t)s].p, iq[s], (size_t)n_cplx[s] * 4, hipMemcpyHostToDevice, h->stream));
+        if (n_cplx[s]) SDRX_HIP(hipMemcpyAsync(h->stage[(size_t)s].p, iq[s], (size_t)n_cplx[s] * 4, hipMemcpyHostToDevice, h->core.stream));
         din[(size_t)s] = static_cast<const int16_t*>(h->stage[(size_t)s].p); dout[(size_t)s] = static_cast<int16_t*>(h->stage[(size_t)s].p);
     }
     int rc = sdrx_iqimb_process_dev(h, din.data(), dout.data(), n_cplx); if (rc) return rc;   // in place on the device: a lane reads a sample before it overwrites it
     for (int s = 0; s < h->n_streams; s++)
-        if (n_cplx[s]) SDRX_HIP(hipMemcpyAsync(iq[s], h->stage[(size_t)s].p, (size_t)n_cplx[s] * 4, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+        if (n_cplx[s]) SDRX_HIP(hipMemcpyAsync(iq[s], h->stage[(size_t)s].p, (size_t)n_cplx[s] * 4, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 

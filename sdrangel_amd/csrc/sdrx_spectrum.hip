@@ -54,8 +54,7 @@ int validate(const sdrx_spectrum_cfg* c, const char* who, int* n_out, int* ov_ou
 } // namespace
 
 struct sdrx_spectrum {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
     // configuration (handleConfigure)
     sdrx_spectrum_cfg cfg{};
     int n = 0, log2n = 0, ov = 0, r = 0, nst = 0, last_radix = 4, mode = 0;   // mode: 0 none, 1 moving, 2 fixed (depth > 1)
@@ -79,9 +78,6 @@ struct sdrx_spectrum {
     float* d_q = nullptr;
     size_t q_floats = 0;
     long q_head = 0, q_count = 0;
-    EventTimer timer;
-    char last_name[64] = "";
-    int last_grid = 0, last_block = 0, last_lds = 0;
 };
 
 static int apply_config(sdrx_spectrum* h, const sdrx_spectrum_cfg* c, int n, int ov)
@@ -107,20 +103,20 @@ static int apply_config(sdrx_spectrum* h, const sdrx_spectrum_cfg* c, int n, int
         const std::complex<float> t = std::exp(std::complex<float>(0, i * phinc));
         tw[(size_t)i] = make_float2(t.real(), t.imag());
     }
-    SDRX_HIP(hipMemcpyAsync(h->d_win, h->win.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    SDRX_HIP(hipMemcpyAsync(h->d_tw, tw.data(), sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_win, h->win.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, h->core.stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_tw, tw.data(), sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, h->core.stream));
     // MovingAverage2D::resize / FixedAverage2D::resize: zeroed state, index 0
     const size_t want = h->mode == 1 ? (size_t)n * h->depth : 0;
     if (want > h->avg_data_cap) {
-        SDRX_HIP(hipStreamSynchronize(h->stream));
+        SDRX_HIP(hipStreamSynchronize(h->core.stream));
         if (h->d_avg_data) { (void)hipFree(h->d_avg_data); h->d_avg_data = nullptr; h->avg_data_cap = 0; }
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_avg_data), want * sizeof(double));
         if (e != hipSuccess) { h->d_avg_data = nullptr; set_error("sdrx_spectrum: averaging state does not fit (fft_size x avg_nb doubles)"); return SDRX_ENOMEM; }
         h->avg_data_cap = want;
     }
-    if (want) SDRX_HIP(hipMemsetAsync(h->d_avg_data, 0, want * sizeof(double), h->stream));
-    SDRX_HIP(hipMemsetAsync(h->d_avg_sum, 0, sizeof(double) * BUF, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));           // the host tables above are released on return
+    if (want) SDRX_HIP(hipMemsetAsync(h->d_avg_data, 0, want * sizeof(double), h->core.stream));
+    SDRX_HIP(hipMemsetAsync(h->d_avg_sum, 0, sizeof(double) * BUF, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));           // the host tables above are released on return
     return SDRX_OK;
 }
 
@@ -135,8 +131,8 @@ static int queue_reserve(sdrx_spectrum* h, long more)
     float* nq = nullptr;
     SDRX_HIP(hipMalloc(reinterpret_cast<void**>(&nq), sizeof(float) * cap));
     hipError_t e = hipSuccess;
-    if (h->q_count) e = hipMemcpyAsync(nq, h->d_q + h->q_head * h->n, sizeof(float) * (size_t)h->q_count * (size_t)h->n, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (h->q_count) e = hipMemcpyAsync(nq, h->d_q + h->q_head * h->n, sizeof(float) * (size_t)h->q_count * (size_t)h->n, hipMemcpyDeviceToDevice, h->core.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->core.stream);
     if (e != hipSuccess) { (void)hipFree(nq); return hip_fail(e, "sdrx_spectrum queue grow", __FILE__, __LINE__); }
     if (h->d_q) (void)hipFree(h->d_q);
     h->d_q = nq; h->q_floats = cap; h->q_head = 0;
@@ -165,7 +161,7 @@ static int feed_device(sdrx_spectrum* h, const uint32_t* d_in, long n_in, int po
     g.frames = (int)frames; g.stale_zero = h->stale_zero ? 1 : 0; g.scalef = h->cfg.scalef;
     Post o{ h->cfg.linear ? 1 : 0, positive_only ? 1 : 0, h->mult, h->ofs, h->powdiv };
 
-    int rc = h->timer.begin(h->stream); if (rc) return rc;
+    int rc = h->core.timer.begin(h->core.stream); if (rc) return rc;
     if (frames > 0) {
         rc = queue_reserve(h, emitted); if (rc) return rc;
         float* qtail = h->d_q + (h->q_head + h->q_count) * n;
@@ -176,23 +172,22 @@ static int feed_device(sdrx_spectrum* h, const uint32_t* d_in, long n_in, int po
         }
         const unsigned grid = (unsigned)((frames + g.fpb - 1) / g.fpb);
         const int lds = (int)sizeof(float2) * g.fpb * n;
-        hipLaunchKernelGGL(spectrum_fft_kernel, dim3(grid), dim3(NT), lds, h->stream,
+        hipLaunchKernelGGL(spectrum_fft_kernel, dim3(grid), dim3(NT), lds, h->core.stream,
                            d_in, h->d_buf[h->cur], h->d_win, h->d_tw, dst, g, o, h->mode ? 1 : 0);
         SDRX_HIP(hipGetLastError());
-        snprintf(h->last_name, sizeof(h->last_name), "%s", "spectrum_fft_kernel");
-        h->last_grid = (int)grid; h->last_block = NT; h->last_lds = lds;
+        h->core.note_launch("spectrum_fft_kernel", (int)grid, NT, lds);
         if (h->mode) {
             Avg a{ h->mode, h->depth, h->avg_idx, (int)frames };
-            hipLaunchKernelGGL(spectrum_avg_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, h->stream,
+            hipLaunchKernelGGL(spectrum_avg_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, h->core.stream,
                                static_cast<const float*>(h->d_raw.p), h->d_avg_data, h->d_avg_sum, qtail, n, a, o);
             SDRX_HIP(hipGetLastError());
             h->avg_idx = (unsigned)(((unsigned long)h->avg_idx + (unsigned long)frames) % h->depth);   // nextAverage() per frame
         }
     }
-    hipLaunchKernelGGL(spectrum_buf_kernel, dim3(BUF / NT), dim3(NT), 0, h->stream,
+    hipLaunchKernelGGL(spectrum_buf_kernel, dim3(BUF / NT), dim3(NT), 0, h->core.stream,
                        d_in, h->d_buf[h->cur], h->d_buf[h->cur ^ 1], g, consumed, fill_f, rem);
     SDRX_HIP(hipGetLastError());
-    rc = h->timer.end(h->stream); if (rc) return rc;
+    rc = h->core.timer.end(h->core.stream); if (rc) return rc;
     h->cur ^= 1;
     h->fill = fill_f + rem;
     h->q_count += emitted;
@@ -208,13 +203,11 @@ int sdrx_spectrum_create(sdrx_spectrum_t** out, int device, const sdrx_spectrum_
     *out = nullptr;
     int n = 0, ov = 0;
     int rc = validate(cfg, "sdrx_spectrum_create", &n, &ov); if (rc) return rc;
-    rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_spectrum* h = new (std::nothrow) sdrx_spectrum;
     if (!h) return SDRX_ENOMEM;
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) { h->stream = h->own_stream; e = hipMalloc(reinterpret_cast<void**>(&h->d_buf[0]), sizeof(float2) * BUF); }
+    rc = h->core.open(device);
+    if (rc) { delete h; return rc; }
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_buf[0]), sizeof(float2) * BUF);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_buf[1]), sizeof(float2) * BUF);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_win), sizeof(float) * BUF);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_tw), sizeof(float2) * BUF);
@@ -230,16 +223,16 @@ int sdrx_spectrum_create(sdrx_spectrum_t** out, int device, const sdrx_spectrum_
 int sdrx_spectrum_destroy(sdrx_spectrum_t* h)
 {
     if (!h) return SDRX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)hipSetDevice(h->core.device);
+    if (h->core.stream) (void)hipStreamSynchronize(h->core.stream);
     for (int i = 0; i < 2; i++) if (h->d_buf[i]) (void)hipFree(h->d_buf[i]);
     if (h->d_win) (void)hipFree(h->d_win);
     if (h->d_tw) (void)hipFree(h->d_tw);
     if (h->d_avg_data) (void)hipFree(h->d_avg_data);
     if (h->d_avg_sum) (void)hipFree(h->d_avg_sum);
     if (h->d_q) (void)hipFree(h->d_q);
-    h->d_in.release(); h->d_raw.release(); h->timer.release();
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->d_in.release(); h->d_raw.release();
+    h->core.close();
     delete h;
     return SDRX_OK;
 }
@@ -247,8 +240,8 @@ int sdrx_spectrum_destroy(sdrx_spectrum_t* h)
 int sdrx_spectrum_reset(sdrx_spectrum_t* h)
 {
     if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    for (int i = 0; i < 2; i++) SDRX_HIP(hipMemsetAsync(h->d_buf[i], 0, sizeof(float2) * BUF, h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    for (int i = 0; i < 2; i++) SDRX_HIP(hipMemsetAsync(h->d_buf[i], 0, sizeof(float2) * BUF, h->core.stream));
     h->dirty = false; h->stale_zero = true;
     h->q_head = h->q_count = 0;
     const sdrx_spectrum_cfg c = h->cfg;
@@ -261,7 +254,7 @@ int sdrx_spectrum_configure(sdrx_spectrum_t* h, const sdrx_spectrum_cfg* cfg)
     int n = 0, ov = 0;
     int rc = validate(cfg, "sdrx_spectrum_configure", &n, &ov); if (rc) return rc;
     if (n != h->n && h->q_count) { set_error("sdrx_spectrum_configure: read or skip the queued frames before changing fft_size"); return SDRX_ESTATE; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     return apply_config(h, cfg, n, ov);
 }
 
@@ -269,7 +262,7 @@ int sdrx_spectrum_feed_dev(sdrx_spectrum_t* h, const int16_t* d_iq, int64_t n_cp
 {
     if (!h || n_cplx < 0 || (n_cplx > 0 && !d_iq)) { set_error("sdrx_spectrum_feed_dev: bad argument"); return SDRX_EINVAL; }
     if (reinterpret_cast<uintptr_t>(d_iq) & 3u) { set_error("sdrx_spectrum_feed_dev: 4-byte alignment"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     return feed_device(h, reinterpret_cast<const uint32_t*>(d_iq), (long)n_cplx, positive_only);
 }
 
@@ -277,11 +270,11 @@ int sdrx_spectrum_feed(sdrx_spectrum_t* h, const int16_t* iq, int64_t n_cplx, in
 {
     if (!h || n_cplx < 0 || (n_cplx > 0 && !iq)) { set_error("sdrx_spectrum_feed: bad argument"); return SDRX_EINVAL; }
     if (n_cplx == 0) return SDRX_OK;
-    SDRX_HIP(hipSetDevice(h->device));
+    SDRX_HIP(hipSetDevice(h->core.device));
     int rc = h->d_in.reserve((size_t)n_cplx * 4); if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, h->stream));
+    SDRX_HIP(hipMemcpyAsync(h->d_in.p, iq, (size_t)n_cplx * 4, hipMemcpyHostToDevice, h->core.stream));
     rc = feed_device(h, static_cast<const uint32_t*>(h->d_in.p), (long)n_cplx, positive_only); if (rc) return rc;
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     return SDRX_OK;
 }
 
@@ -296,9 +289,9 @@ int64_t sdrx_spectrum_read(sdrx_spectrum_t* h, float* out, int64_t max_frames)
     if (!h || max_frames < 0 || (max_frames > 0 && !out)) { set_error("sdrx_spectrum_read: bad argument"); return SDRX_EINVAL; }
     const long k = max_frames < h->q_count ? (long)max_frames : h->q_count;
     if (k == 0) return 0;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipMemcpyAsync(out, h->d_q + h->q_head * h->n, sizeof(float) * (size_t)k * (size_t)h->n, hipMemcpyDeviceToHost, h->stream));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
+    SDRX_HIP(hipSetDevice(h->core.device));
+    SDRX_HIP(hipMemcpyAsync(out, h->d_q + h->q_head * h->n, sizeof(float) * (size_t)k * (size_t)h->n, hipMemcpyDeviceToHost, h->core.stream));
+    SDRX_HIP(hipStreamSynchronize(h->core.stream));
     h->q_head += k; h->q_count -= k;
     if (!h->q_count) h->q_head = 0;
     return k;
@@ -321,56 +314,16 @@ int sdrx_spectrum_window(const sdrx_spectrum_t* h, float* out, int32_t cap)
     return h->n;
 }
 
-int sdrx_spectrum_sync(sdrx_spectrum_t* h)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    return SDRX_OK;
-}
+int sdrx_spectrum_sync(sdrx_spectrum_t* h) { return h ? h->core.sync() : SDRX_EINVAL; }
 
-int sdrx_spectrum_set_stream(sdrx_spectrum_t* h, void* hip_stream)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    SDRX_HIP(hipStreamSynchronize(h->stream));
-    h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
-    return SDRX_OK;
-}
+int sdrx_spectrum_set_stream(sdrx_spectrum_t* h, void* hip_stream) { return h ? h->core.set_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_spectrum_get_stream(sdrx_spectrum_t* h, void** hip_stream)
-{
-    if (!h || !hip_stream) return SDRX_EINVAL;
-    *hip_stream = h->stream;
-    return SDRX_OK;
-}
+int sdrx_spectrum_get_stream(sdrx_spectrum_t* h, void** hip_stream) { return h ? h->core.get_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_spectrum_set_timing(sdrx_spectrum_t* h, int enabled)
-{
-    if (!h) return SDRX_EINVAL;
-    h->timer.enabled = enabled != 0;
-    return SDRX_OK;
-}
+int sdrx_spectrum_set_timing(sdrx_spectrum_t* h, int enabled) { return h ? h->core.set_timing(enabled) : SDRX_EINVAL; }
 
-int sdrx_spectrum_get_timing(sdrx_spectrum_t* h, double* total_ms, int64_t* feeds, int reset)
-{
-    if (!h) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(h->device));
-    int rc = h->timer.collect(h->stream); if (rc) return rc;
-    if (total_ms) *total_ms = h->timer.total_ms;
-    if (feeds) *feeds = h->timer.count;
-    if (reset) { h->timer.total_ms = 0; h->timer.count = 0; }
-    return SDRX_OK;
-}
+int sdrx_spectrum_get_timing(sdrx_spectrum_t* h, double* total_ms, int64_t* feeds, int reset) { return h ? h->core.get_timing(total_ms, feeds, reset) : SDRX_EINVAL; }
 
-int sdrx_spectrum_last_launch(const sdrx_spectrum_t* h, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes)
-{
-    if (!h) return SDRX_EINVAL;
-    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", h->last_name);
-    if (grid) *grid = h->last_grid;
-    if (block) *block = h->last_block;
-    if (lds_bytes) *lds_bytes = h->last_lds;
-    return SDRX_OK;
-}
+int sdrx_spectrum_last_launch(const sdrx_spectrum_t* h, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes) { return h ? h->core.last_launch(kernel_name, name_cap, grid, block, lds_bytes) : SDRX_EINVAL; }
 
 } // extern "C"

@@ -5,6 +5,7 @@
 #include "sdrx_common.hpp"
 #include "wfm_kernels.hpp"
 #include "backend_design.hpp"
+#include "demod_common.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -31,8 +32,7 @@ constexpr size_t BLK_BYTES = sizeof(WfmClamp) + sizeof(double) + sizeof(float) +
 } // namespace
 
 struct sdrx_wfm {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    HandleCore core;
     int n_ch = 0;
     std::vector<sdrx_wfm_cfg> cfg;
     std::vector<WfmHost> ch;
@@ -45,9 +45,6 @@ struct sdrx_wfm {
     std::vector<float> taps_all, filters_all;
     std::vector<int> taps_off, ntaps;
     bool any_dyadic = false, any_serial = false;
-    EventTimer timer;
-    char last_name[64] = "";
-    int last_grid = 0, last_block = 0, last_lds = 0;
 };
 
 static int validate(int32_t n_ch, const sdrx_wfm_cfg* cfg)
@@ -81,9 +78,9 @@ static int ensure_capacity(sdrx_wfm* b, int c, int64_t n_in)
         if (bytes <= buf.cap) return SDRX_OK;
         void* np = nullptr;
         SDRX_HIP(hipMalloc(&np, bytes));
-        SDRX_HIP(hipMemsetAsync(np, 0, bytes, b->stream));
-        if (buf.p && keep) SDRX_HIP(hipMemcpyAsync(np, buf.p, keep, hipMemcpyDeviceToDevice, b->stream));
-        SDRX_HIP(hipStreamSynchronize(b->stream));
+        SDRX_HIP(hipMemsetAsync(np, 0, bytes, b->core.stream));
+        if (buf.p && keep) SDRX_HIP(hipMemcpyAsync(np, buf.p, keep, hipMemcpyDeviceToDevice, b->core.stream));
+        SDRX_HIP(hipStreamSynchronize(b->core.stream));
         if (buf.p) (void)hipFree(buf.p);
         buf.p = np; buf.cap = bytes;
         return SDRX_OK;
@@ -104,14 +101,14 @@ static int ensure_capacity(sdrx_wfm* b, int c, int64_t n_in)
 
 static int upload_fresh_state(sdrx_wfm* b)
 {
-    SDRX_HIP(hipMemcpyAsync(b->d_chan, b->h_chan.data(), (size_t)b->n_ch * sizeof(WfmChan), hipMemcpyHostToDevice, b->stream));
+    SDRX_HIP(hipMemcpyAsync(b->d_chan, b->h_chan.data(), (size_t)b->n_ch * sizeof(WfmChan), hipMemcpyHostToDevice, b->core.stream));
     for (auto& h : b->ch) {
-        for (int i = 0; i < 2; i++) SDRX_HIP(hipMemsetAsync(h.pend[i], 0, WFM_H * 4, b->stream));
-        if (h.tail.p) SDRX_HIP(hipMemsetAsync(h.tail.p, 0, WFM_H * 8, b->stream));
-        if (h.dem.p) SDRX_HIP(hipMemsetAsync(h.dem.p, 0, WFM_HIST * 4, b->stream));
+        for (int i = 0; i < 2; i++) SDRX_HIP(hipMemsetAsync(h.pend[i], 0, WFM_H * 4, b->core.stream));
+        if (h.tail.p) SDRX_HIP(hipMemsetAsync(h.tail.p, 0, WFM_H * 8, b->core.stream));
+        if (h.dem.p) SDRX_HIP(hipMemsetAsync(h.dem.p, 0, WFM_HIST * 4, b->core.stream));
         h.pending = 0;
     }
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     return SDRX_OK;
 }
 
@@ -120,8 +117,8 @@ extern "C" {
 int sdrx_wfm_destroy(sdrx_wfm_t* b)
 {
     if (!b) return SDRX_OK;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    (void)hipSetDevice(b->core.device);
+    if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
     for (auto& h : b->ch) {
         h.head.release(); h.tail.release(); h.arg.release(); h.flag.release(); h.blk.release();
         h.dem.release(); h.sched.release(); h.audio.release(); h.stage_in.release();
@@ -137,8 +134,7 @@ int sdrx_wfm_destroy(sdrx_wfm_t* b)
     if (b->d_taps) (void)hipFree(b->d_taps);
     if (b->d_filters) (void)hipFree(b->d_filters);
     if (b->d_utbl) (void)hipFree(b->d_utbl);
-    b->timer.release();
-    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+    b->core.close();
     delete b;
     return SDRX_OK;
 }
@@ -148,34 +144,30 @@ int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_c
     if (!out) { set_error("sdrx_wfm_create: null out"); return SDRX_EINVAL; }
     *out = nullptr;
     int rc = validate(n_ch, cfg); if (rc) return rc;
-    rc = check_device(device); if (rc) return rc;
-    SDRX_HIP(hipSetDevice(device));
     sdrx_wfm* b = new (std::nothrow) sdrx_wfm;
     if (!b) return SDRX_ENOMEM;
-    b->device = device; b->n_ch = n_ch;
-    hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete b; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-    b->stream = b->own_stream;
+    rc = b->core.open(device);
+    if (rc) { delete b; return rc; }
+    b->n_ch = n_ch;
     b->cfg.assign(cfg, cfg + n_ch);
     b->ch.resize((size_t)n_ch); b->h_chan.resize((size_t)n_ch);
     b->taps_off.resize((size_t)n_ch); b->ntaps.resize((size_t)n_ch);
 
-#define WFM_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = hip_fail(e_, #call, __FILE__, __LINE__); sdrx_wfm_destroy(b); return r_; } } while (0)
     // NCO table (nco.cpp:30-39) and g_fft cosine table (gfft.h:141-150)
     std::vector<float> nco(WFM_NCO_N);
     for (int i = 0; i < WFM_NCO_N; i++) nco[(size_t)i] = (float)std::cos((2.0 * PI_D * i) / WFM_NCO_N);
-    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_nco), WFM_NCO_N * 4));
-    WFM_TRY(hipMemcpy(b->d_nco, nco.data(), WFM_NCO_N * 4, hipMemcpyHostToDevice));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_nco), WFM_NCO_N * 4), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipMemcpy(b->d_nco, nco.data(), WFM_NCO_N * 4, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
     {
         const int n = WFM_FFT;
         std::vector<float> utbl((size_t)n / 4 + 1);
         utbl[0] = 1.0f;
         for (int i = 1; i < n / 4; i++) utbl[(size_t)i] = (float)std::cos((2.0 * 3.141592653589793238462643383279502884197 * (float)i) / (float)n);
         utbl[(size_t)n / 4] = 0.0f;
-        WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_utbl), ((size_t)n / 4 + 1) * 4));
-        WFM_TRY(hipMemcpy(b->d_utbl, utbl.data(), ((size_t)n / 4 + 1) * 4, hipMemcpyHostToDevice));
+        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_utbl), ((size_t)n / 4 + 1) * 4), sdrx_wfm_destroy(b));
+        SDRX_HIP_ELSE(hipMemcpy(b->d_utbl, utbl.data(), ((size_t)n / 4 + 1) * 4, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
     }
-    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_filters), (size_t)n_ch * WFM_FFT * 8));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_filters), (size_t)n_ch * WFM_FFT * 8), sdrx_wfm_destroy(b));
     b->filters_all.assign((size_t)n_ch * WFM_FFT * 2, 0.0f);
     for (int c = 0; c < n_ch; c++) {
         const sdrx_wfm_cfg& k = cfg[c];
@@ -209,15 +201,15 @@ int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_c
             if (hp && f2 < f1) f[(size_t)(2 * (h2 / 2))] += 1;
             for (int i = 0; i < h2; i++) { const float w = blackman(i, h2); f[(size_t)(2 * i)] *= w; f[(size_t)(2 * i + 1)] *= w; }
             float2* dst = b->d_filters + (size_t)c * WFM_FFT;
-            WFM_TRY(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(be_fft_design_kernel<WFM_FFT>, dim3(1), dim3(WFM_FFT / 8), 0, b->stream, dst, b->d_utbl);
-            WFM_TRY(hipGetLastError());
-            WFM_TRY(hipStreamSynchronize(b->stream));
-            WFM_TRY(hipMemcpy(f.data(), dst, (size_t)flen * 8, hipMemcpyDeviceToHost));
+            SDRX_HIP_ELSE(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
+            hipLaunchKernelGGL(be_fft_design_kernel<WFM_FFT>, dim3(1), dim3(WFM_FFT / 8), 0, b->core.stream, dst, b->d_utbl);
+            SDRX_HIP_ELSE(hipGetLastError(), sdrx_wfm_destroy(b));
+            SDRX_HIP_ELSE(hipStreamSynchronize(b->core.stream), sdrx_wfm_destroy(b));
+            SDRX_HIP_ELSE(hipMemcpy(f.data(), dst, (size_t)flen * 8, hipMemcpyDeviceToHost), sdrx_wfm_destroy(b));
             float scale = 0;
             for (int i = 0; i < h2; i++) { const float mag = hypotf(f[(size_t)(2 * i)], f[(size_t)(2 * i + 1)]); if (mag > scale) scale = mag; }
             if (scale != 0) for (int i = 0; i < flen * 2; i++) f[(size_t)i] /= scale;
-            WFM_TRY(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice));
+            SDRX_HIP_ELSE(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
             std::memcpy(&b->filters_all[(size_t)c * WFM_FFT * 2], f.data(), (size_t)flen * 8);
         }
         WfmChan& s = b->h_chan[(size_t)c];
@@ -241,18 +233,17 @@ int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_c
         (s.dy_q >= 0 ? b->any_dyadic : b->any_serial) = true;
         s.distance = s.step;                                                               // m_interpolatorDistanceRemain starts at in / audio
         if (s.ntaps > WFM_HIST) { set_error("sdrx_wfm_create: resampler window does not fit"); sdrx_wfm_destroy(b); return SDRX_EINVAL; }
-        for (int i = 0; i < 2; i++) WFM_TRY(hipMalloc(reinterpret_cast<void**>(&h.pend[i]), WFM_H * 4));
+        for (int i = 0; i < 2; i++) SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.pend[i]), WFM_H * 4), sdrx_wfm_destroy(b));
     }
-    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_taps), b->taps_all.size() * 4));
-    WFM_TRY(hipMemcpy(b->d_taps, b->taps_all.data(), b->taps_all.size() * 4, hipMemcpyHostToDevice));
-    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(WfmChan)));
-    WFM_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(WfmBufs)));
-    WFM_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(WfmBufs), hipHostMallocDefault));
-    WFM_TRY(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming));
-    WFM_TRY(hipEventRecord(b->bufs_ev, b->stream));
-    WFM_TRY(hipEventCreateWithFlags(&b->prod_ev, hipEventDisableTiming));
-    WFM_TRY(hipEventCreateWithFlags(&b->cons_ev, hipEventDisableTiming));
-#undef WFM_TRY
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_taps), b->taps_all.size() * 4), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipMemcpy(b->d_taps, b->taps_all.data(), b->taps_all.size() * 4, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(WfmChan)), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(WfmBufs)), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(WfmBufs), hipHostMallocDefault), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipEventRecord(b->bufs_ev, b->core.stream), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->prod_ev, hipEventDisableTiming), sdrx_wfm_destroy(b));
+    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->cons_ev, hipEventDisableTiming), sdrx_wfm_destroy(b));
     rc = upload_fresh_state(b);
     if (rc) { sdrx_wfm_destroy(b); return rc; }
     *out = b;
@@ -262,8 +253,8 @@ int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_c
 int sdrx_wfm_reset(sdrx_wfm_t* b)
 {
     if (!b) { set_error("sdrx_wfm_reset: null handle"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
     return upload_fresh_state(b);
 }
 
@@ -274,12 +265,10 @@ int sdrx_wfm_reset(sdrx_wfm_t* b)
 static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n_per_ch, hipStream_t producer = nullptr)
 {
     int64_t max_blocks = 0, max_out = 0;
+    int rc = demod_check_lengths(b->n_ch, n_per_ch, "sdrx_wfm_feed"); if (rc) return rc;
+    rc = demod_check_dev_pointers(b->n_ch, d_iq, n_per_ch, "sdrx_wfm_feed"); if (rc) return rc;
     for (int c = 0; c < b->n_ch; c++) {
-        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff) { set_error("sdrx_wfm_feed: bad length"); return SDRX_EINVAL; }
-        if (n_per_ch[c] > 0 && (!d_iq[c] || (reinterpret_cast<uintptr_t>(d_iq[c]) & 3u))) { set_error("sdrx_wfm_feed: null or misaligned channel pointer"); return SDRX_EINVAL; }
-    }
-    for (int c = 0; c < b->n_ch; c++) {
-        int rc = ensure_capacity(b, c, std::max<int64_t>(n_per_ch[c], 1)); if (rc) return rc;
+        rc = ensure_capacity(b, c, std::max<int64_t>(n_per_ch[c], 1)); if (rc) return rc;
         const int64_t nb = (b->ch[(size_t)c].pending + n_per_ch[c]) / WFM_H;
         max_blocks = std::max(max_blocks, nb);
         // every audio sample after the first of a feed consumes >= floor(step) demodulated samples
@@ -305,51 +294,49 @@ static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n
         u.dem = static_cast<float*>(h.dem.p); u.sched = static_cast<uint2*>(h.sched.p); u.audio = static_cast<int16_t*>(h.audio.p);
         u.n_in = n_per_ch[c];
     }
-    int rc = b->timer.begin(b->stream); if (rc) return rc;
-    SDRX_HIP(hipMemcpyAsync(b->d_bufs, b->h_bufs, (size_t)b->n_ch * sizeof(WfmBufs), hipMemcpyHostToDevice, b->stream));
-    SDRX_HIP(hipEventRecord(b->bufs_ev, b->stream));
+    rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
+    rc = demod_upload_bufs(b->d_bufs, b->h_bufs, b->n_ch, b->bufs_ev, b->core.stream); if (rc) return rc;
     const unsigned nc = (unsigned)b->n_ch, gc = (nc + 63) / 64, nblk = (unsigned)max_blocks;
-    hipLaunchKernelGGL(wfm_prep_kernel, dim3(gc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->n_ch);
+    hipLaunchKernelGGL(wfm_prep_kernel, dim3(gc), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch);
     SDRX_HIP(hipGetLastError());
     if (nblk && b->any_dyadic) {
-        hipLaunchKernelGGL(wfm_sched_fill_kernel, dim3((unsigned)((max_out + 255) / 256), nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+        hipLaunchKernelGGL(wfm_sched_fill_kernel, dim3((unsigned)((max_out + 255) / 256), nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
         SDRX_HIP(hipGetLastError());
     }
     // lanes whose channel the closed form took exit at once (prep's off-grid guard can hand a channel back)
-    hipLaunchKernelGGL(wfm_sched_walk_kernel, dim3(gc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs, b->n_ch);
+    hipLaunchKernelGGL(wfm_sched_walk_kernel, dim3(gc), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch);
     SDRX_HIP(hipGetLastError());
-    const bool cross = producer && producer != b->stream;
+    const bool cross = producer && producer != b->core.stream;
     if (cross) {
         SDRX_HIP(hipEventRecord(b->prod_ev, producer));
-        SDRX_HIP(hipStreamWaitEvent(b->stream, b->prod_ev, 0));
+        SDRX_HIP(hipStreamWaitEvent(b->core.stream, b->prod_ev, 0));
     }
     if (nblk) {
-        hipLaunchKernelGGL(wfm_fft_kernel, dim3(nblk, nc), dim3(WFM_FFT / 8), 0, b->stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl, b->d_nco);
+        hipLaunchKernelGGL(wfm_fft_kernel, dim3(nblk, nc), dim3(WFM_FFT / 8), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl, b->d_nco);
         SDRX_HIP(hipGetLastError());
-        snprintf(b->last_name, sizeof(b->last_name), "%s", "wfm_fft_kernel");
-        b->last_grid = (int)(nblk * nc); b->last_block = WFM_FFT / 8; b->last_lds = (int)(2 * WFM_FFT * sizeof(float2) + (WFM_FFT / 4 + 1) * sizeof(float));
+        b->core.note_launch("wfm_fft_kernel", (int)(nblk * nc), WFM_FFT / 8, (int)(2 * WFM_FFT * sizeof(float2) + (WFM_FFT / 4 + 1) * sizeof(float)));
     }
-    hipLaunchKernelGGL(wfm_pend_kernel, dim3(nc), dim3(WFM_H), 0, b->stream, b->d_chan, b->d_bufs);
+    hipLaunchKernelGGL(wfm_pend_kernel, dim3(nc), dim3(WFM_H), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
     if (cross) {
-        SDRX_HIP(hipEventRecord(b->cons_ev, b->stream));
+        SDRX_HIP(hipEventRecord(b->cons_ev, b->core.stream));
         SDRX_HIP(hipStreamWaitEvent(producer, b->cons_ev, 0));
     }
     if (nblk) {
-        hipLaunchKernelGGL(wfm_level_kernel, dim3(nblk, nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+        hipLaunchKernelGGL(wfm_level_kernel, dim3(nblk, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
         SDRX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(wfm_blockscan_kernel, dim3(nc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs);
+        hipLaunchKernelGGL(wfm_blockscan_kernel, dim3(nc), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs);
         SDRX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(wfm_demod_kernel, dim3(nblk, nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs);
+        hipLaunchKernelGGL(wfm_demod_kernel, dim3(nblk, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
         SDRX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(wfm_fixup_kernel, dim3(nc), dim3(64), 0, b->stream, b->d_chan, b->d_bufs);
+        hipLaunchKernelGGL(wfm_fixup_kernel, dim3(nc), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs);
         SDRX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(wfm_fir_kernel, dim3((unsigned)((max_out + 255) / 256), nc), dim3(256), 0, b->stream, b->d_chan, b->d_bufs, b->d_taps);
+        hipLaunchKernelGGL(wfm_fir_kernel, dim3((unsigned)((max_out + 255) / 256), nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_taps);
         SDRX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(wfm_carry_kernel, dim3(nc), dim3(WFM_H), 0, b->stream, b->d_chan, b->d_bufs);
+    hipLaunchKernelGGL(wfm_carry_kernel, dim3(nc), dim3(WFM_H), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
-    rc = b->timer.end(b->stream); if (rc) return rc;
+    rc = b->core.timer.end(b->core.stream); if (rc) return rc;
     for (int c = 0; c < b->n_ch; c++) {
         WfmHost& h = b->ch[(size_t)c];
         h.cur ^= 1;
@@ -361,48 +348,30 @@ static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n
 int sdrx_wfm_feed_dev(sdrx_wfm_t* b, const int16_t* const* d_iq, const int64_t* n_per_ch)
 {
     if (!b || !d_iq || !n_per_ch) { set_error("sdrx_wfm_feed_dev: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     return feed_common(b, d_iq, n_per_ch);
 }
 
 int sdrx_wfm_feed_bank(sdrx_wfm_t* b, sdrx_chan_bank_t* bank)
 {
     if (!b || !bank) { set_error("sdrx_wfm_feed_bank: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
+    SDRX_HIP(hipSetDevice(b->core.device));
     void* ps = nullptr;
     int rc = sdrx_chan_bank_get_stream(bank, &ps); if (rc) return rc;
-    std::vector<const int16_t*> d((size_t)b->n_ch);
-    std::vector<int64_t> n((size_t)b->n_ch);
-    for (int c = 0; c < b->n_ch; c++) {
-        rc = sdrx_chan_bank_last_dev(bank, c, &d[(size_t)c], &n[(size_t)c]);
-        if (rc) { set_error("sdrx_wfm_feed_bank: the bank has fewer channels than the demodulator bank"); return rc; }
-    }
+    std::vector<const int16_t*> d;
+    std::vector<int64_t> n;
+    rc = demod_gather_bank(bank, b->n_ch, "sdrx_wfm_feed_bank", d, n); if (rc) return rc;
     return feed_common(b, d.data(), n.data(), static_cast<hipStream_t>(ps));
 }
 
 int sdrx_wfm_feed(sdrx_wfm_t* b, const int16_t* const* iq, const int64_t* n_per_ch)
 {
     if (!b || !iq || !n_per_ch) { set_error("sdrx_wfm_feed: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    std::vector<const int16_t*> d((size_t)b->n_ch);
-    for (int c = 0; c < b->n_ch; c++) {
-        if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff || (n_per_ch[c] > 0 && !iq[c])) { set_error("sdrx_wfm_feed: bad length or null channel pointer"); return SDRX_EINVAL; }
-        WfmHost& h = b->ch[(size_t)c];
-        int rc = h.stage_in.reserve((size_t)std::max<int64_t>(n_per_ch[c], 1) * 4); if (rc) return rc;
-        if (n_per_ch[c] > 0) SDRX_HIP(hipMemcpyAsync(h.stage_in.p, iq[c], (size_t)n_per_ch[c] * 4, hipMemcpyHostToDevice, b->stream));
-        d[(size_t)c] = static_cast<const int16_t*>(h.stage_in.p);
-    }
-    int rc = feed_common(b, d.data(), n_per_ch); if (rc) return rc;
-    SDRX_HIP(hipStreamSynchronize(b->stream));            // the caller's buffers are free again on return
-    return SDRX_OK;
-}
-
-static int fetch_state(sdrx_wfm* b, int32_t c, WfmChan* s)
-{
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipMemcpyAsync(s, b->d_chan + c, sizeof *s, hipMemcpyDeviceToHost, b->stream));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
+    SDRX_HIP(hipSetDevice(b->core.device));
+    std::vector<const int16_t*> d;
+    int rc = demod_stage_inputs(b->ch, b->core.stream, iq, n_per_ch, "sdrx_wfm_feed", d); if (rc) return rc;
+    rc = feed_common(b, d.data(), n_per_ch); if (rc) return rc;
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));            // the caller's buffers are free again on return
     return SDRX_OK;
 }
 
@@ -410,7 +379,7 @@ int64_t sdrx_wfm_read(sdrx_wfm_t* b, int32_t c, int16_t* audio, int64_t cap)
 {
     if (!b || c < 0 || c >= b->n_ch || cap < 0 || (cap > 0 && !audio)) { set_error("sdrx_wfm_read: bad argument"); return SDRX_EINVAL; }
     WfmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     const int64_t n = std::min<int64_t>(s.n_out, cap);
     if (n == 0) return 0;
     SDRX_HIP(hipMemcpy(audio, b->ch[(size_t)c].audio.p, (size_t)n * 2, hipMemcpyDeviceToHost));
@@ -421,7 +390,7 @@ int sdrx_wfm_last_dev(sdrx_wfm_t* b, int32_t c, const int16_t** d_audio, int64_t
 {
     if (!b || c < 0 || c >= b->n_ch || !d_audio || !n) { set_error("sdrx_wfm_last_dev: bad argument"); return SDRX_EINVAL; }
     WfmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     *d_audio = static_cast<const int16_t*>(b->ch[(size_t)c].audio.p);
     *n = s.n_out;
     return SDRX_OK;
@@ -431,7 +400,7 @@ int sdrx_wfm_squelch_open(sdrx_wfm_t* b, int32_t c)
 {
     if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_wfm_squelch_open: bad argument"); return SDRX_EINVAL; }
     WfmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     return s.sq_open;
 }
 
@@ -439,18 +408,12 @@ int sdrx_wfm_levels(sdrx_wfm_t* b, int32_t c, double* sum, double* peak, int64_t
 {
     if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_wfm_levels: bad argument"); return SDRX_EINVAL; }
     WfmChan s;
-    int rc = fetch_state(b, c, &s); if (rc) return rc;
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     if (sum) *sum = s.magsq_sum;
     if (peak) *peak = s.magsq_peak;
     if (count) *count = s.magsq_count;
-    if (reset) {                                          // getMagSqLevels: sum, peak and count back to 0
-        char* base = reinterpret_cast<char*>(b->d_chan + c);
-        SDRX_HIP(hipMemsetAsync(base + offsetof(WfmChan, magsq_sum), 0, sizeof(double), b->stream));
-        SDRX_HIP(hipMemsetAsync(base + offsetof(WfmChan, magsq_peak), 0, sizeof(double), b->stream));
-        SDRX_HIP(hipMemsetAsync(base + offsetof(WfmChan, magsq_count), 0, sizeof(long long), b->stream));
-        SDRX_HIP(hipStreamSynchronize(b->stream));
-    }
-    return SDRX_OK;
+    if (!reset) return SDRX_OK;                           // getMagSqLevels: sum, peak and count back to 0
+    return demod_zero_levels(b->core, b->d_chan + c, offsetof(WfmChan, magsq_sum), offsetof(WfmChan, magsq_peak), offsetof(WfmChan, magsq_count));
 }
 
 int sdrx_wfm_get_design(sdrx_wfm_t* b, int32_t c, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
@@ -466,56 +429,16 @@ int sdrx_wfm_get_design(sdrx_wfm_t* b, int32_t c, int32_t* ntaps_per_phase, floa
     return SDRX_OK;
 }
 
-int sdrx_wfm_sync(sdrx_wfm_t* b)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    return SDRX_OK;
-}
+int sdrx_wfm_sync(sdrx_wfm_t* b) { return b ? b->core.sync() : SDRX_EINVAL; }
 
-int sdrx_wfm_set_stream(sdrx_wfm_t* b, void* hip_stream)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    SDRX_HIP(hipStreamSynchronize(b->stream));
-    b->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : b->own_stream;
-    return SDRX_OK;
-}
+int sdrx_wfm_set_stream(sdrx_wfm_t* b, void* hip_stream) { return b ? b->core.set_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_wfm_get_stream(sdrx_wfm_t* b, void** hip_stream)
-{
-    if (!b || !hip_stream) return SDRX_EINVAL;
-    *hip_stream = b->stream;
-    return SDRX_OK;
-}
+int sdrx_wfm_get_stream(sdrx_wfm_t* b, void** hip_stream) { return b ? b->core.get_stream(hip_stream) : SDRX_EINVAL; }
 
-int sdrx_wfm_set_timing(sdrx_wfm_t* b, int enabled)
-{
-    if (!b) return SDRX_EINVAL;
-    b->timer.enabled = enabled != 0;
-    return SDRX_OK;
-}
+int sdrx_wfm_set_timing(sdrx_wfm_t* b, int enabled) { return b ? b->core.set_timing(enabled) : SDRX_EINVAL; }
 
-int sdrx_wfm_get_timing(sdrx_wfm_t* b, double* total_ms, int64_t* feeds, int reset)
-{
-    if (!b) return SDRX_EINVAL;
-    SDRX_HIP(hipSetDevice(b->device));
-    int rc = b->timer.collect(b->stream); if (rc) return rc;
-    if (total_ms) *total_ms = b->timer.total_ms;
-    if (feeds) *feeds = b->timer.count;
-    if (reset) { b->timer.total_ms = 0; b->timer.count = 0; }
-    return SDRX_OK;
-}
+int sdrx_wfm_get_timing(sdrx_wfm_t* b, double* total_ms, int64_t* feeds, int reset) { return b ? b->core.get_timing(total_ms, feeds, reset) : SDRX_EINVAL; }
 
-int sdrx_wfm_last_launch(const sdrx_wfm_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes)
-{
-    if (!b) return SDRX_EINVAL;
-    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", b->last_name);
-    if (grid) *grid = b->last_grid;
-    if (block) *block = b->last_block;
-    if (lds_bytes) *lds_bytes = b->last_lds;
-    return SDRX_OK;
-}
+int sdrx_wfm_last_launch(const sdrx_wfm_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes) { return b ? b->core.last_launch(kernel_name, name_cap, grid, block, lds_bytes) : SDRX_EINVAL; }
 
 } // extern "C"

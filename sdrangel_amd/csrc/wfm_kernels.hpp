@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include "gfft_kernel.hpp"
 #include "wfm_scan.hpp"
+#include "dsp_device.hpp"
 
 namespace sdrx {
 
@@ -252,19 +253,6 @@ void wfm_level_kernel(const WfmChan* __restrict__ ch, const WfmBufs* __restrict_
     if (tid == 0) { b.blk_map[blk] = maps[0]; b.blk_sum[blk] = sums[0]; b.blk_peak[blk] = peaks[0]; }
 }
 
-__device__ __forceinline__ WfmClamp wfm_shfl_up(WfmClamp m, int o)
-{
-    WfmClamp r; r.a = __shfl_up(m.a, o, 64); r.lo = __shfl_up(m.lo, o, 64); r.hi = __shfl_up(m.hi, o, 64);
-    return r;
-}
-__device__ __forceinline__ WfmClamp wfm_wave_scan(WfmClamp m, int lane)     // inclusive, in lane order
-{
-    for (int o = 1; o < 64; o *= 2) {
-        const WfmClamp t = wfm_shfl_up(m, o);
-        if (lane >= o) m = wfm_compose(t, m);
-    }
-    return m;
-}
 __device__ __forceinline__ int wfm_wave_max_scan(int v, int lane)           // inclusive
 {
     for (int o = 1; o < 64; o *= 2) {
@@ -390,13 +378,6 @@ void wfm_fixup_kernel(WfmChan* __restrict__ ch, const WfmBufs* __restrict__ bufs
     if (lane == 0) s.prev_arg = carry;
 }
 
-__device__ __forceinline__ int wfm_to_q16(float v)
-{
-    // (qint16) of a float as x86-64 does it: cvttss2si (0x80000000 when out of range or NaN), then the low 16 bits
-    const int i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u;
-    return (int)(short)i;
-}
-
 // ---- 7. real polyphase FIR, one lane per audio sample: taps summed newest-first like the ring walk (mul and add separate,
 // in order; the reference's iAcc of the zero imaginary part does not touch rAcc), then the qint16 conversion
 __global__ __launch_bounds__(256)
@@ -416,7 +397,7 @@ void wfm_fir_kernel(const WfmChan* __restrict__ ch, const WfmBufs* __restrict__ 
     float acc = 0.0f;
 #pragma unroll 8
     for (int i = 0; i < nt; i++) acc += t[i] * x[-i];
-    b.audio[o] = (int16_t)wfm_to_q16(acc * 3276.8f * s.volume);
+    b.audio[o] = (int16_t)sdrx_to_q16(acc * 3276.8f * s.volume);
 }
 
 // ---- 8. carry: ovlbuf, the resampler window, NCO phase, pending count (one workgroup per channel, after everything else)

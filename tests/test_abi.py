@@ -74,6 +74,50 @@ def test_bad_arguments_are_rejected():
     assert b"log2" in L.sdrx_last_error()
 
 
+# the stream / timing / launch-record accessors each handle family exports (include/sdrx.h); sdrx_iir_* exports none
+ACCESSORS = {
+    "decim": ("sync", "set_stream", "set_timing", "get_timing", "last_launch"),
+    "fdecim": ("sync", "set_stream", "set_timing", "get_timing", "last_launch"),
+    "chan_bank": ("sync", "set_stream", "get_stream", "set_timing", "get_timing", "last_launch"),
+    "spectrum": ("sync", "set_stream", "get_stream", "set_timing", "get_timing", "last_launch"),
+    "wfm": ("sync", "set_stream", "get_stream", "set_timing", "get_timing", "last_launch"),
+    "am": ("sync", "set_stream", "get_stream", "set_timing", "get_timing", "last_launch"),
+    "dccorr": ("sync", "set_stream"),
+    "iqimb": ("sync", "set_stream"),
+    "backend": ("sync",),
+    "audiotail": ("sync",),
+    "iir": (),
+}
+
+
+def test_accessor_table_is_what_the_header_declares():
+    names = set(sa.exported_symbols())
+    for fam, acc in ACCESSORS.items():
+        have = {a for a in ("sync", "set_stream", "get_stream", "set_timing", "get_timing", "last_launch") if f"sdrx_{fam}_{a}" in names}
+        assert have == set(acc), fam
+
+
+@pytest.mark.parametrize("fam", sorted(ACCESSORS))
+def test_accessors_reject_a_null_handle(fam):
+    """every accessor returns SDRX_EINVAL for a null handle, before any HIP call (this runs without a device)"""
+    L = sa.lib()
+    ms, n, p = C.c_double(), C.c_int64(), C.c_void_p()
+    name = C.create_string_buffer(128)
+    g, b, l = C.c_int(), C.c_int(), C.c_int()
+    args = {
+        "sync": [()],
+        "set_stream": [(None,)],
+        "get_stream": [(C.byref(p),), (None,)],         # and a null out pointer
+        "set_timing": [(1,)],
+        "get_timing": [(C.byref(ms), C.byref(n), 1), (None, None, 0)],
+        "last_launch": [(name, 128, C.byref(g), C.byref(b), C.byref(l)), (None, 0, None, None, None)],
+    }
+    for acc in ACCESSORS[fam]:
+        fn = getattr(L, f"sdrx_{fam}_{acc}")
+        for a in args[acc]:
+            assert fn(None, *a) == -1, (fam, acc, a)
+
+
 # ---------------------------------------------------------------- SampleSinkFifo mirror
 class RefFifoModel:
     """The reference's semantics (samplesinkfifo.cpp:70-231) in ten lines of Python."""
