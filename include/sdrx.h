@@ -684,6 +684,80 @@ int sdrx_am_get_timing(sdrx_am_t* h, double* total_ms, int64_t* feeds, int reset
 int sdrx_am_last_launch(const sdrx_am_t* h, char* kernel_name, int name_cap,
                         int* grid, int* block, int* lds_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * NFM demodulator bank: NFMDemod::feed (plugins/channelrx/demodnfm/nfmdemod.cpp:140-332) with m_deltaSquelch = false and
+ * m_ctcssOn = false (the defaults), N channels per handle, each fed with int16 I/Q at the channelizer's output rate:
+ *     c = Complex(re, im) * m_nco.nextIQ();  m_interpolator.decimate(&dist, c, &ci)        as sdrx_backend_* (filt_mode 0)
+ *     per ci: demod = m_phaseDiscri.phaseDiscriminatorDelta(ci, magsqRaw, dev); magsq = (Real)(magsqRaw / 2^30);
+ *             m_movingAverage(magsq) (MovingAverageUtil<Real, double, 32>); level sum, peak, count;
+ *             below = (Real) m_movingAverage < m_squelchLevel; m_squelchDelayLine.write(below ? 0 : demod * m_discriCompensation);
+ *             counter-- down to 0 when below, ++ up to 2 * m_squelchGate otherwise; open = counter > m_squelchGate
+ *     muted: 0;  open: (qint16)(m_bandpass.filter(m_squelchDelayLine.readBack(m_squelchGate)) * volume);  closed: 0
+ * The Bandpass (301 taps, 300 Hz .. af_bandwidth at the audio rate) advances on open, unmuted samples only.
+ * Output: mono qint16 audio, the value the reference writes to .l and .r, bit-identical to the strict-IEEE scalar reference
+ * build.  Any feed length is valid (0 included); NCO phase, resampler window and distance, m_prevArg, moving average, delay
+ * line, counter, Bandpass ring and level accumulators carry across feeds.
+ * A fresh handle is the object constructed with the audio device at audio_rate, after applySettings(settings, true) and
+ * start():
+ *   - m_phaseDiscri.setFMScaling((8.0f * audio_rate) / (float) fm_deviation)
+ *   - m_discriCompensation = audio_rate / 48000.0f, times its own (Real) square root (nfmdemod.cpp:82-83)
+ *   - m_squelchGate = (audio_rate / 100) * squelch_gate;  m_squelchLevel = (Real) pow(10.0, squelch / 100.0)
+ *   - distanceRemain = 0 (the first input already emits an output), counter 0, moving average empty
+ *   - m_prevArg starts at 0 (PhaseDiscriminators has no initialiser for it; as sdrx_audiotail_*)
+ *   - the delay line has the constructor's 24000 entries, contents 0 (DoubleBufferFIFO allocates with new T[] and does not
+ *     clear; applyAudioSampleRate's resize(rate / 2) is not on this path)
+ *   - readBack clamps its delay to the line's size, and at delay == size the slot it names is the one just written: for
+ *     m_squelchGate >= 24000 the Bandpass is given the current sample, not one 24000 back
+ *   - left out: the AF squelch (m_deltaSquelch) and CTCSS (Goertzel recurrences on libm cosines that feed the GUI), AudioFifo,
+ *     the interpolating branch (audio_rate > in_rate: SDRX_EINVAL), and mid-stream retune -- a channel is configured at creation
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_nfm sdrx_nfm_t;
+typedef struct sdrx_nfm_cfg {
+    int32_t in_rate;          /* channelizer output rate (m_inputSampleRate) */
+    int32_t nco_freq;         /* m_nco.setFreq(nco_freq, in_rate): the demod passes -frequencyOffset */
+    int32_t audio_rate;       /* m_audioSampleRate; 1000 <= audio_rate <= in_rate; distance = (Real) in_rate / (Real) audio_rate */
+    float   rf_bandwidth;     /* m_rfBandwidth: m_interpolator.create(16, in_rate, rfBW / 2.2f); 0 < rfBW <= 1e7 */
+    float   af_bandwidth;     /* m_afBandwidth: m_bandpass.create(301, audio_rate, 300.0, afBW); 300 < afBW <= 1e7 */
+    int32_t fm_deviation;     /* m_fmDeviation, Hz; > 0 */
+    float   volume;           /* m_volume */
+    float   squelch;          /* m_squelch, centi-Bels */
+    int32_t squelch_gate;     /* m_squelchGate of the settings, in 10s of ms; 0 .. 1000 */
+    int32_t audio_mute;       /* m_audioMute */
+} sdrx_nfm_cfg;
+int sdrx_nfm_create(sdrx_nfm_t** out, int device, int32_t n_ch, const sdrx_nfm_cfg* cfg);
+int sdrx_nfm_destroy(sdrx_nfm_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_nfm_reset(sdrx_nfm_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to NFMDemod::feed) */
+int sdrx_nfm_feed(sdrx_nfm_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_nfm_feed_dev(sdrx_nfm_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_nfm_feed_bank(sdrx_nfm_t* h, sdrx_chan_bank_t* bank);
+/* audio of the last feed for channel ch; returns the number of samples written (<0: error) */
+int64_t sdrx_nfm_read(sdrx_nfm_t* h, int32_t ch, int16_t* audio, int64_t cap);
+/* device-side view of the same (valid until the next feed) */
+int sdrx_nfm_last_dev(sdrx_nfm_t* h, int32_t ch, const int16_t** d_audio, int64_t* n);
+/* m_squelchOpen after the last feed: 1 / 0 (<0: error) */
+int sdrx_nfm_squelch_open(sdrx_nfm_t* h, int32_t ch);
+/* magsq: m_movingAverage.asDouble(), the 32-sample moving average after the last sample; sum / peak / count: m_magsqSum /
+ * m_magsqPeak / m_magsqCount of getMagSqLevels, zeroed by reset != 0 as getMagSqLevels does.  magsq, peak and count are exact;
+ * sum is a parallel double reduction (relative difference <= 2 * count * 2^-53) */
+int sdrx_nfm_levels(sdrx_nfm_t* h, int32_t ch, double* magsq, double* sum, double* peak, int64_t* count, int reset);
+/* design products, for inspection: polyphase taps [16][ntaps], the 151 folded Bandpass taps, NCO increment, m_squelchLevel,
+ * m_squelchGate in samples */
+int sdrx_nfm_get_design(sdrx_nfm_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
+                        float* bandpass_taps, int32_t* nco_inc, float* squelch_level, int32_t* squelch_gate);
+int sdrx_nfm_sync(sdrx_nfm_t* h);
+int sdrx_nfm_set_stream(sdrx_nfm_t* h, void* hip_stream);
+int sdrx_nfm_get_stream(sdrx_nfm_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_nfm_set_timing(sdrx_nfm_t* h, int enabled);
+int sdrx_nfm_get_timing(sdrx_nfm_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the output kernel of the last feed (Bandpass, volume, conversion): nfm_out_kernel, its grid, block and LDS bytes */
+int sdrx_nfm_last_launch(const sdrx_nfm_t* h, char* kernel_name, int name_cap,
+                         int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,17 @@ def lib() -> C.CDLL:
         "sdrx_am_squelch_open": (C.c_int, [vp, i32]),
         "sdrx_am_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_am_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
+        "sdrx_nfm_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_nfm_destroy": (C.c_int, [vp]),
+        "sdrx_nfm_reset": (C.c_int, [vp]),
+        "sdrx_nfm_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_nfm_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_nfm_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_nfm_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_nfm_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_nfm_squelch_open": (C.c_int, [vp, i32]),
+        "sdrx_nfm_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_nfm_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(i32)]),
         "sdrx_fdecim_state_bytes": (i64, [vp]),
         "sdrx_fdecim_get_state": (C.c_int, [vp, vp]),
         "sdrx_fdecim_set_state": (C.c_int, [vp, vp]),
@@ -219,7 +230,7 @@ def lib() -> C.CDLL:
     }
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
-                "wfm": five + ("get_stream",), "am": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "wfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
         for name in names:
@@ -826,6 +837,13 @@ class AmCfg(C.Structure):
                 ("audio_mute", C.c_int32), ("bandpass_enable", C.c_int32)]
 
 
+class NfmCfg(C.Structure):
+    """sdrx_nfm_cfg: one NFMDemod, power squelch, no CTCSS (in_rate, nco_freq = -frequencyOffset, audio_rate, NFMDemodSettings)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
+                ("rf_bandwidth", C.c_float), ("af_bandwidth", C.c_float), ("fm_deviation", C.c_int32), ("volume", C.c_float),
+                ("squelch", C.c_float), ("squelch_gate", C.c_int32), ("audio_mute", C.c_int32)]
+
+
 def wfm_required_bw(rf_bw: int) -> int:
     """WFMDemod::requiredBW: the rate the demodulator asks its channelizer for"""
     return 48000 if rf_bw <= 48000 else (3 * rf_bw) // 2
@@ -918,6 +936,25 @@ class AmDemodBank(_DemodBank):
     def design(self, ch: int):
         """(taps per phase, taps [16 * ntaps], the 151 folded Bandpass taps, NCO increment, squelch level)"""
         return self._design(ch, np.zeros(151, np.float32))
+
+
+class NfmDemodBank(_DemodBank):
+    """N narrowband-FM demodulators (NFMDemod::feed, power squelch, no CTCSS): int16 I/Q at the channelizer's output rate in,
+    mono qint16 audio out."""
+    _prefix, _cfg = "nfm", NfmCfg
+
+    def levels(self, ch: int, reset: bool = False):
+        """(m_movingAverage, m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
+        m, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        self._call("levels", ch, C.byref(m), C.byref(s), C.byref(p), C.byref(n), int(reset))
+        return m.value, s.value, p.value, n.value
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], the 151 folded Bandpass taps, NCO increment, squelch level, gate in samples)"""
+        nt, inc, lvl, gate = C.c_int32(), C.c_int32(), C.c_float(), C.c_int32()
+        taps, bp = np.zeros(16 * 128, np.float32), np.zeros(151, np.float32)
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, bp.ctypes.data, C.byref(inc), C.byref(lvl), C.byref(gate))
+        return nt.value, taps[: 16 * nt.value].copy(), bp, inc.value, lvl.value, gate.value
 
 
 class AudioTailCfg(C.Structure):

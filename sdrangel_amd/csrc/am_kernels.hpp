@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "am_scan.hpp"
+#include "demod_psum.hpp"
 #include "dsp_device.hpp"
 
 namespace sdrx {
@@ -88,58 +89,21 @@ void am_level_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
 }
 
 // ---- 2. rounded prefix sum along time: acc += term.  which = 0: moving-average total; 1: AGC sum over the fed samples.
-// One wave per 16 channels, 64 terms per channel and trip.  The wave loads each channel's 64 terms with one coalesced
-// 512-byte instruction into LDS (row pitch 65 doubles: the 16 chain lanes fall into 16 different bank pairs), lane c then
-// walks row c -- LDS read, one double add, LDS write of its result -- and the rows go back out coalesced.  (A lane reading
-// its own channel's terms straight from memory touches 64 different lines per instruction: measured 8.4 ms per launch for
-// 256 channels x 48 000 terms)
-constexpr int AM_PS_CH = 16, AM_PS_T = 64;
+// One wave per 16 channels, 64 terms per channel and trip: psum_rows (demod_psum.hpp).
+constexpr int AM_PS_CH = PS_CH;
 __global__ __launch_bounds__(64)
 void am_psum_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs, int n_ch, int which)
 {
-    __shared__ double tile[AM_PS_CH][AM_PS_T + 1];
-    __shared__ const double* st[AM_PS_CH];
-    __shared__ double* so[AM_PS_CH];
-    __shared__ int sn[AM_PS_CH];
     const int lane = threadIdx.x, c = blockIdx.x * AM_PS_CH + lane;
     const bool chain = lane < AM_PS_CH && c < n_ch;
-    double acc = 0.0;
-    int n_mine = 0;
-    if (lane < AM_PS_CH) {
+    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
         const int cc = min(c, n_ch - 1);                    // rows past the last channel: its pointers, no terms
         const AmChan& s = ch[cc];
         const AmBufs& b = bufs[cc];
-        st[lane] = which ? b.uterm : b.dterm;
-        so[lane] = which ? b.agc : b.tot;
-        if (chain) { n_mine = which ? s.n_fed : s.n; acc = which ? s.agc_sum : s.total; }
-        sn[lane] = n_mine;
-    }
-    __syncthreads();
-    int n_max = 0;
-    for (int q = 0; q < AM_PS_CH; q++) n_max = max(n_max, sn[q]);
-    for (int i = 0; i < n_max; i += AM_PS_T) {
-        // unconditional loads with the index clamped into the channel's terms, so that all sixteen are in flight together;
-        // what lies past a channel's end is never added and never stored
-        double v[AM_PS_CH];
-#pragma unroll
-        for (int q = 0; q < AM_PS_CH; q++) v[q] = st[q][min(i + lane, max(sn[q] - 1, 0))];
-#pragma unroll
-        for (int q = 0; q < AM_PS_CH; q++) tile[q][lane] = v[q];
-        __syncthreads();
-        if (chain) {
-            const int m = min(AM_PS_T, n_mine - i);
-            if (m == AM_PS_T) {
-#pragma unroll 16
-                for (int k = 0; k < AM_PS_T; k++) { acc += tile[lane][k]; tile[lane][k] = acc; }
-            } else {
-                for (int k = 0; k < m; k++) { acc += tile[lane][k]; tile[lane][k] = acc; }
-            }
-        }
-        __syncthreads();
-        for (int q = 0; q < AM_PS_CH; q++)
-            if (i + lane < sn[q]) so[q][i + lane] = tile[q][lane];
-        __syncthreads();
-    }
+        term = which ? b.uterm : b.dterm;
+        out = which ? b.agc : b.tot;
+        if (chain) { n_mine = which ? s.n_fed : s.n; sum = which ? s.agc_sum : s.total; }
+    });
     if (chain) { if (which) ch[c].agc_sum_next = acc; else ch[c].total_next = acc; }
 }
 

@@ -1,8 +1,9 @@
-// host code the demodulator banks share (sdrx_wfm.hip, sdrx_am.hip): input staging and checks, the hand-over from a
-// channelizer bank, one channel's device state, the per-feed pointer table.  `who` is the entry point named in the error text.
+// host code the demodulator banks share (sdrx_wfm.hip, sdrx_am.hip, sdrx_nfm.hip): input staging and checks, the hand-over
+// from a channelizer bank, one channel's device state, the per-feed pointer table, the Bandpass design.  `who` is the entry point named in the error text.
 #pragma once
 #include "sdrx_common.hpp"
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -81,6 +82,34 @@ int demod_upload_bufs(Bufs* d_bufs, const Bufs* h_bufs, int n_ch, hipEvent_t ev,
     SDRX_HIP(hipMemcpyAsync(d_bufs, h_bufs, (size_t)n_ch * sizeof(Bufs), hipMemcpyHostToDevice, stream));
     SDRX_HIP(hipEventRecord(ev, stream));
     return SDRX_OK;
+}
+
+// Bandpass<Real>::create(301, sampleRate, lowCutoff, highCutoff) (bandpass.h:15-75): the folded taps [0 .. 150]
+inline void demod_bandpass_design(double rate, double f1, double f2, float* t)
+{
+    const double PI = 3.14159265358979323846;
+    const int ntaps = 301, nt = 151;
+    const double mid = ((double)ntaps - 1.0) / 2.0;
+    const double Wcl = 2.0 * PI * f1 / rate, Wch = 2.0 * PI * f2 / rate;
+    std::vector<float> lp((size_t)nt), hp((size_t)nt);
+    for (int i = 0; i < nt; i++) {
+        if (i == (ntaps - 1) / 2) { lp[(size_t)i] = (float)(Wch / PI); hp[(size_t)i] = (float)(-(Wcl / PI)); }
+        else {
+            lp[(size_t)i] = (float)(std::sin(((double)i - mid) * Wch) / (((double)i - mid) * PI));
+            hp[(size_t)i] = (float)(-std::sin(((double)i - mid) * Wcl) / (((double)i - mid) * PI));
+        }
+    }
+    hp[(size_t)((ntaps - 1) / 2)] += 1;
+    for (int i = 0; i < nt; i++) {
+        const double w = 0.54 + 0.46 * std::cos((2.0 * PI * ((double)i - mid)) / (double)ntaps);
+        lp[(size_t)i] = (float)(lp[(size_t)i] * w); hp[(size_t)i] = (float)(hp[(size_t)i] * w);
+        t[i] = -(lp[(size_t)i] + hp[(size_t)i]);
+    }
+    t[(ntaps - 1) / 2] += 1;
+    float sum = 0; int i;
+    for (i = 0; i < nt - 1; i++) sum += t[i] * 2;
+    sum += t[i];
+    for (i = 0; i < nt; i++) t[i] /= sum;
 }
 
 } // namespace sdrx

@@ -29,34 +29,6 @@ struct AmHost {
 
 constexpr size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// Bandpass<Real>::create(301, sampleRate, lowCutoff, highCutoff) (bandpass.h:15-75): the folded taps [0 .. 150]
-void bandpass_design(double rate, double f1, double f2, float* t)
-{
-    const double PI = 3.14159265358979323846;
-    const int ntaps = AM_BP_TAPS, nt = AM_BP_H + 1;
-    const double mid = ((double)ntaps - 1.0) / 2.0;
-    const double Wcl = 2.0 * PI * f1 / rate, Wch = 2.0 * PI * f2 / rate;
-    std::vector<float> lp((size_t)nt), hp((size_t)nt);
-    for (int i = 0; i < nt; i++) {
-        if (i == (ntaps - 1) / 2) { lp[(size_t)i] = (float)(Wch / PI); hp[(size_t)i] = (float)(-(Wcl / PI)); }
-        else {
-            lp[(size_t)i] = (float)(std::sin(((double)i - mid) * Wch) / (((double)i - mid) * PI));
-            hp[(size_t)i] = (float)(-std::sin(((double)i - mid) * Wcl) / (((double)i - mid) * PI));
-        }
-    }
-    hp[(size_t)((ntaps - 1) / 2)] += 1;
-    for (int i = 0; i < nt; i++) {
-        const double w = 0.54 + 0.46 * std::cos((2.0 * PI * ((double)i - mid)) / (double)ntaps);
-        lp[(size_t)i] = (float)(lp[(size_t)i] * w); hp[(size_t)i] = (float)(hp[(size_t)i] * w);
-        t[i] = -(lp[(size_t)i] + hp[(size_t)i]);
-    }
-    t[(ntaps - 1) / 2] += 1;
-    float sum = 0; int i;
-    for (i = 0; i < nt - 1; i++) sum += t[i] * 2;
-    sum += t[i];
-    for (i = 0; i < nt; i++) t[i] /= sum;
-}
-
 } // namespace
 
 struct sdrx_am {
@@ -188,7 +160,7 @@ int sdrx_am_create(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg*
         s.bp_off = c * (AM_BP_H + 1);
         s.agc_sum = (double)s.H * am_agc_initial();         // m_sum = (Type) m_history.size() * initial
         // m_bandpass.create(301, audioSampleRate, 300.0, rfBandwidth / 2.0f)
-        bandpass_design((double)k.audio_rate, 300.0, (double)(k.rf_bandwidth / 2.0f), &b->bp_all[(size_t)s.bp_off]);
+        demod_bandpass_design((double)k.audio_rate, 300.0, (double)(k.rf_bandwidth / 2.0f), &b->bp_all[(size_t)s.bp_off]);
         AmHost& h = b->ch[(size_t)c];
         h.hist_set = al(AM_MA * 4) + al((size_t)s.D * 4) + al((size_t)s.H * 8) + al(AM_BP_HIST * 4);
         SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.hist), 2 * h.hist_set), sdrx_am_destroy(b));
