@@ -758,6 +758,104 @@ int sdrx_nfm_get_timing(sdrx_nfm_t* h, double* total_ms, int64_t* feeds, int res
 int sdrx_nfm_last_launch(const sdrx_nfm_t* h, char* kernel_name, int name_cap,
                          int* grid, int* block, int* lds_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * SSB / DSB demodulator bank: SSBDemod::feed (plugins/channelrx/demodssb/ssbdemod.cpp:147-285), N channels per handle, each
+ * fed with int16 I/Q at the channelizer's output rate:
+ *     c = Complex(re, im) * m_nco.nextIQ();  m_interpolator.decimate(&dist, c, &ci);  runSSB(ci, &sideband, usb) | runDSB
+ *                                                        as sdrx_backend_* (filt_mode 2 USB, 3 LSB, 4 DSB; taps_per_phase 2.0)
+ *     per sideband sample s: m_sum += s; when the pre-increment m_undersampleCount is a multiple of 1 << (span_log2 - 1):
+ *             avg = m_sum / decim, m_magsq = |avg|^2 / 2^30, level sum, peak, count, one spectrum Sample (re and im swapped
+ *             for LSB), m_sum = 0 -- the very first group holds one sample
+ *         agcVal = agc ? m_agc.feedAndGetValue(s) : 10.0        MagAGC (sdrbase/dsp/agc.cpp:98-182), history hn, steps hn / 2
+ *         x = m_squelchDelayLine.readBack(hn);  m_audioActive = x.re != 0;  m_squelchDelayLine.write(s * agcVal)
+ *         muted: {0, 0};  else z = x * m_agc.getStepValue();
+ *             mono: l = r = (qint16)((Real)((z.re + z.im) * 0.7) * m_volume)
+ *             binaural: r = (qint16)(z.re * m_volume), l = (qint16)(z.im * m_volume); audio_flip swaps l and r
+ * Output: qint16 l,r pairs and the spectrum Samples of the last feed, bit-identical to the strict-IEEE scalar reference
+ * build.  The sideband stream arrives in blocks of 512 samples (DSB: 1024), so many feeds produce no audio.  Any feed length
+ * is valid (0 included); NCO phase, resampler window and distance, the filter's overlap, the moving average, the four AGC
+ * counters, the delay line, the open spectrum group and the level accumulators carry across feeds.
+ * A fresh handle is the object constructed with the audio device at audio_rate, after applySettings(settings, true) and
+ * start():
+ *   - rf_bandwidth < 0 is LSB: band = -rf_bandwidth, low cutoff = -low_cutoff; band < 100 becomes 100 with a low cutoff of 0
+ *   - m_interpolator.create(16, in_rate, band * 1.5f, 2.0f); create_filter(low / rate, band / rate), fftfilt length 1024;
+ *     DSB: create_dsb_filter(2 * band / rate), length 2048
+ *   - hn = (audio_rate / 1000) << agc_time_log2: MagAGC::resize(hn, hn / 2, agcTarget = 3276.8 as a Real), setStepDownDelay(hn);
+ *     the history is 0 with sum 0 (resize, then fill(0)), m_stepUpCounter 0, m_stepDownCounter hn / 2, clampMax 327.68
+ *   - hn == 12000 would skip resize() and leave the constructor's object (history filled with R, step length 2400); it needs
+ *     audio_rate / 1000 in {375, 750, ...}, and audio_rate <= 192000 keeps it out of reach
+ *   - setGate((audio_rate / 1000) * agc_threshold_gate); setThreshold(powerFromdB(agc_power_threshold) * 32768^2);
+ *     setThresholdEnable(agc_power_threshold != -m_minPowerThresholdDB), which compares against +100 in the 16-bit build: every
+ *     negative threshold enables it
+ *   - m_volume = volume / 4.0
+ *   - with agc = 0 the AGC is never fed, m_stepUpCounter stays 0 and getStepValue() is smootherstep(0) = 0: the audio is
+ *     SILENCE (agcVal 10.0 goes into the delay line only).  The same holds with the threshold disabled, where
+ *     feedAndGetValue returns m_u0 and moves no counter.  This is the reference's behaviour and is reproduced
+ *   - the delay line has the constructor's 96000 entries, contents 0 (DoubleBufferFIFO allocates with new T[] and does not
+ *     clear); readBack runs before this sample's write and clamps its delay to the line's size, where the slot it names is
+ *     the last one written: x[j] = w[j - 1 - hn] for hn < 96000 and w[j - 1] from there on
+ *   - zero input with the AGC on gives m_u0 = R / sqrt(0) = inf and 0 * inf = NaN in the delay line; (qint16) of a NaN is
+ *     what x86-64 gives (0), as sdrx_audiotail_*
+ *   - left out: AudioFifo, the interpolating branch (audio_rate > in_rate: SDRX_EINVAL), mid-stream retune or settings
+ *     change -- a channel is configured at creation
+ * SDRX_EINVAL also for hn < 2 or hn > 131072 and span_log2 outside 1 .. 8 (decim_mask is an unsigned char).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_ssb sdrx_ssb_t;
+typedef struct sdrx_ssb_cfg {
+    int32_t in_rate;              /* channelizer output rate (m_inputSampleRate) */
+    int32_t nco_freq;             /* m_nco.setFreq(nco_freq, in_rate): the demod passes -frequencyOffset */
+    int32_t audio_rate;           /* m_audioSampleRate; 1000 <= audio_rate <= min(in_rate, 192000) */
+    float   rf_bandwidth;         /* m_rfBandwidth; negative: LSB */
+    float   low_cutoff;           /* m_lowCutoff; negative for LSB */
+    float   volume;               /* m_volume of the settings */
+    int32_t span_log2;            /* m_spanLog2, 1 .. 8: spectrum decimation 1 << (span_log2 - 1) */
+    int32_t audio_binaural;       /* m_audioBinaural */
+    int32_t audio_flip;           /* m_audioFlipChannels */
+    int32_t dsb;                  /* m_dsb */
+    int32_t audio_mute;           /* m_audioMute */
+    int32_t agc;                  /* m_agc */
+    int32_t agc_clamping;         /* m_agcClamping */
+    int32_t agc_time_log2;        /* m_agcTimeLog2: hn = (audio_rate / 1000) << agc_time_log2, 2 .. 131072 */
+    int32_t agc_power_threshold;  /* m_agcPowerThreshold, dB; +100 disables the threshold; -300 .. 300 */
+    int32_t agc_threshold_gate;   /* m_agcThresholdGate, ms; 0 .. 10000 */
+} sdrx_ssb_cfg;
+int sdrx_ssb_create(sdrx_ssb_t** out, int device, int32_t n_ch, const sdrx_ssb_cfg* cfg);
+int sdrx_ssb_destroy(sdrx_ssb_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_ssb_reset(sdrx_ssb_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to SSBDemod::feed) */
+int sdrx_ssb_feed(sdrx_ssb_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_ssb_feed_dev(sdrx_ssb_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_ssb_feed_bank(sdrx_ssb_t* h, sdrx_chan_bank_t* bank);
+/* audio of the last feed for channel ch as AudioSample {l, r} pairs; returns the number of PAIRS written (<0: error) */
+int64_t sdrx_ssb_read(sdrx_ssb_t* h, int32_t ch, int16_t* audio_lr, int64_t cap_pairs);
+/* device-side view of the same (valid until the next feed): pointer and number of pairs */
+int sdrx_ssb_last_dev(sdrx_ssb_t* h, int32_t ch, const int16_t** d_audio_lr, int64_t* n_pairs);
+/* the Samples {re, im} the last feed handed to the spectrum sink (m_sampleBuffer); returns their number (<0: error) */
+int64_t sdrx_ssb_read_spectrum(sdrx_ssb_t* h, int32_t ch, int16_t* samples_iq, int64_t cap_samples);
+int sdrx_ssb_spectrum_last_dev(sdrx_ssb_t* h, int32_t ch, const int16_t** d_samples_iq, int64_t* n_samples);
+/* m_audioActive after the last feed: 1 / 0 (<0: error) */
+int sdrx_ssb_audio_active(sdrx_ssb_t* h, int32_t ch);
+/* magsq: m_magsq of the last closed spectrum group; sum / peak / count: m_magsqSum / m_magsqPeak / m_magsqCount of
+ * getMagSqLevels, zeroed by reset != 0 as getMagSqLevels does.  magsq, peak and count are exact; sum is a parallel double
+ * reduction (relative difference <= 2 * count * 2^-53) */
+int sdrx_ssb_levels(sdrx_ssb_t* h, int32_t ch, double* magsq, double* sum, double* peak, int64_t* count, int reset);
+/* design products, for inspection: polyphase taps [16][ntaps], the filter spectrum (2048 complex slots; 1024 used unless DSB),
+ * NCO increment, hn, the gate in samples, the threshold (linear power) and m_volume */
+int sdrx_ssb_get_design(sdrx_ssb_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap, float* filter_iq,
+                        int32_t* nco_inc, int32_t* agc_nb_samples, int32_t* agc_gate, double* agc_threshold, float* volume);
+int sdrx_ssb_sync(sdrx_ssb_t* h);
+int sdrx_ssb_set_stream(sdrx_ssb_t* h, void* hip_stream);
+int sdrx_ssb_get_stream(sdrx_ssb_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_ssb_set_timing(sdrx_ssb_t* h, int enabled);
+int sdrx_ssb_get_timing(sdrx_ssb_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the output kernel of the last feed (delay line, step value, volume, conversion): ssb_out_kernel, its grid, block and LDS bytes */
+int sdrx_ssb_last_launch(const sdrx_ssb_t* h, char* kernel_name, int name_cap,
+                         int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

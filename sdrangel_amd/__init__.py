@@ -182,6 +182,20 @@ def lib() -> C.CDLL:
         "sdrx_nfm_squelch_open": (C.c_int, [vp, i32]),
         "sdrx_nfm_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_nfm_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(i32)]),
+        "sdrx_ssb_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_ssb_destroy": (C.c_int, [vp]),
+        "sdrx_ssb_reset": (C.c_int, [vp]),
+        "sdrx_ssb_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_ssb_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_ssb_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_ssb_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_ssb_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_ssb_read_spectrum": (i64, [vp, i32, vp, i64]),
+        "sdrx_ssb_spectrum_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_ssb_audio_active": (C.c_int, [vp, i32]),
+        "sdrx_ssb_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_ssb_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_float)]),
         "sdrx_fdecim_state_bytes": (i64, [vp]),
         "sdrx_fdecim_get_state": (C.c_int, [vp, vp]),
         "sdrx_fdecim_set_state": (C.c_int, [vp, vp]),
@@ -230,7 +244,8 @@ def lib() -> C.CDLL:
     }
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
-                "wfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "wfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
+                "ssb": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
         for name in names:
@@ -844,6 +859,15 @@ class NfmCfg(C.Structure):
                 ("squelch", C.c_float), ("squelch_gate", C.c_int32), ("audio_mute", C.c_int32)]
 
 
+class SsbCfg(C.Structure):
+    """sdrx_ssb_cfg: one SSBDemod (in_rate, nco_freq = -frequencyOffset, audio_rate, SSBDemodSettings; rf_bandwidth < 0 is LSB)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
+                ("rf_bandwidth", C.c_float), ("low_cutoff", C.c_float), ("volume", C.c_float), ("span_log2", C.c_int32),
+                ("audio_binaural", C.c_int32), ("audio_flip", C.c_int32), ("dsb", C.c_int32), ("audio_mute", C.c_int32),
+                ("agc", C.c_int32), ("agc_clamping", C.c_int32), ("agc_time_log2", C.c_int32), ("agc_power_threshold", C.c_int32),
+                ("agc_threshold_gate", C.c_int32)]
+
+
 def wfm_required_bw(rf_bw: int) -> int:
     """WFMDemod::requiredBW: the rate the demodulator asks its channelizer for"""
     return 48000 if rf_bw <= 48000 else (3 * rf_bw) // 2
@@ -955,6 +979,58 @@ class NfmDemodBank(_DemodBank):
         taps, bp = np.zeros(16 * 128, np.float32), np.zeros(151, np.float32)
         self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, bp.ctypes.data, C.byref(inc), C.byref(lvl), C.byref(gate))
         return nt.value, taps[: 16 * nt.value].copy(), bp, inc.value, lvl.value, gate.value
+
+
+class SsbDemodBank(_DemodBank):
+    """N SSB / DSB demodulators (SSBDemod::feed): int16 I/Q at the channelizer's output rate in; qint16 l,r audio and the
+    decimated sideband stream of the spectrum sink out."""
+    _prefix, _cfg = "ssb", SsbCfg
+
+    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
+        """the last feed's audio as an [n, 2] array of (l, r)"""
+        if cap is None:
+            cap = self.last_dev(ch)[1]
+        out = np.empty((max(cap, 1), 2), np.int16)
+        n = self._fn("read")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_ssb_read rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def spectrum_last_dev(self, ch: int):
+        """(device pointer, count) of the spectrum Samples of the last feed of channel ch"""
+        p, n = C.c_void_p(), C.c_int64()
+        self._call("spectrum_last_dev", ch, C.byref(p), C.byref(n))
+        return p.value or 0, n.value
+
+    def read_spectrum(self, ch: int, cap: int | None = None) -> np.ndarray:
+        """the Samples the last feed handed to the spectrum sink, as an [n, 2] array of (re, im)"""
+        if cap is None:
+            cap = self.spectrum_last_dev(ch)[1]
+        out = np.empty((max(cap, 1), 2), np.int16)
+        n = self._fn("read_spectrum")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_ssb_read_spectrum rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def audio_active(self, ch: int) -> bool:
+        rc = self._fn("audio_active")(self._h, ch)
+        if rc < 0:
+            raise SdrxError(f"sdrx_ssb_audio_active rc={rc}: {lib().sdrx_last_error().decode()}")
+        return bool(rc)
+
+    def levels(self, ch: int, reset: bool = False):
+        """(m_magsq, m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
+        m, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        self._call("levels", ch, C.byref(m), C.byref(s), C.byref(p), C.byref(n), int(reset))
+        return m.value, s.value, p.value, n.value
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], filter spectrum as 4096 floats, NCO increment, hn, gate in samples, threshold, m_volume)"""
+        nt, inc, hn, gate, thr, vol = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_float()
+        taps, filt = np.zeros(16 * 256, np.float32), np.zeros(4096, np.float32)
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc), C.byref(hn), C.byref(gate),
+                   C.byref(thr), C.byref(vol))
+        return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value, hn.value, gate.value, thr.value, vol.value
 
 
 class AudioTailCfg(C.Structure):

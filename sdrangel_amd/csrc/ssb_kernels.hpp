@@ -1,0 +1,308 @@
+// SSB / DSB demodulator bank kernels: the tail of SSBDemod::feed (plugins/channelrx/demodssb/ssbdemod.cpp:181-250).  The
+// front (NCO, Interpolator::decimate, fftfilt runSSB / runDSB) is the channel back-end's (backend_kernels.hpp); these kernels
+// start from its sideband stream `s` at the audio rate, which arrives in blocks of 512 (DSB: 1024) samples.
+//     m_sum += s[j]; every decim-th sample: avg, m_magsq, level sums, one spectrum Sample
+//     agcVal = m_agcActive ? m_agc.feedAndGetValue(s[j]) : 10.0;  x = m_squelchDelayLine.readBack(hn);  write(s[j] * agcVal)
+//     muted: {0, 0};  else z = x * m_agc.getStepValue(): mono (qint16)((z.re + z.im) * 0.7 * volume), or binaural
+// Audio and spectrum are bit-identical to the strict-IEEE scalar reference build: every float and double expression keeps
+// the reference's operand order and the file is compiled with -ffp-contract=off.  ssb_scan.hpp has the cut of the
+// recurrences; DESIGN.md 4.13 the kernel table.  The only loop that is serial along time is psum_rows' (demod_psum.hpp): a
+// load, one double add, a store.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "ssb_scan.hpp"
+#include "demod_psum.hpp"
+#include "dsp_device.hpp"
+
+namespace sdrx {
+
+struct SsbChan {                        // device resident: config + carried state of one channel
+    // --- config
+    int hn;                             // m_agcNbSamples = m_stepDownDelay = the moving average's length; L = hn / 2
+    int D;                              // ssb_delay(hn)
+    int gate;                           // m_agc.setGate: (rate / 1000) * agc_threshold_gate
+    int decim;                          // 1 << (span_log2 - 1)
+    int agc, thr_enable, clamping;      // m_agcActive, m_thresholdEnable, m_clamping
+    int mute, binaural, flip, swap_iq;  // swap_iq: !m_dsb & !m_usb, the spectrum Sample is (avgi, avgr)
+    float volume;                       // m_volume / 4.0
+    double threshold, step_delta;       // powerFromdB(dB) * 32768^2; 1.0 / L
+    // --- state
+    int g, count, U, Dn;                // m_gateCounter, m_count, m_stepUpCounter, m_stepDownCounter
+    unsigned usc;                       // m_undersampleCount
+    float2 open_sum;                    // m_sum of the open spectrum group
+    double total;                       // MovingAverage::m_sum
+    double u0;                          // m_u0
+    double magsq, magsq_sum, magsq_peak;
+    long long magsq_count;
+    int audio_active;                   // m_audioActive
+    // --- per feed
+    int n, n_spec;                      // sideband samples; spectrum Samples
+    double total_next;                  // written by ssb_psum_kernel, committed by ssb_carry_kernel
+};
+
+struct SsbBufs {                        // per channel device pointers (per feed capacity ensured by the host)
+    const float2* s;                    // the front's sideband output of this feed
+    const int* n_ptr;                   // its count (device side)
+    const float* phist; float* phist_next;        // last hn powers
+    const float2* whist; float2* whist_next;      // last D + 1 delay-line writes
+    float* pw;                          // per sample: re * re + im * im
+    double* dterm; double* tot;         // moving-average terms and sums
+    float2* w;                          // per sample: what the delay line was given
+    float* sv;                          // per sample: getStepValue() after it
+    int16_t* audio;                     // l, r pairs, 4-byte aligned
+    int16_t* spec;                      // re, im pairs of the spectrum Samples, 4-byte aligned
+    double* blk_sum; double* blk_peak;  // per 256 spectrum groups
+};
+
+// ---- 1. per sample: power and the moving-average term; per closed spectrum group: average, m_magsq, the Sample; per 256
+// groups the level partials.  Thread q of the channel's grid owns sample q and group q (there are never more groups than samples).
+__global__ __launch_bounds__(256)
+void ssb_level_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs)
+{
+    __shared__ double sums[256];
+    __shared__ double peaks[256];
+    const int c = blockIdx.y, tid = threadIdx.x;
+    const SsbBufs b = bufs[c];
+    const int n = *b.n_ptr;
+    SsbChan& s = ch[c];
+    const int decim = s.decim, hn = s.hn;
+    const int i0 = ssb_first_close(s.usc, decim), ncl = ssb_closes(n, i0, decim);
+    if (blockIdx.x == 0 && tid == 0) { s.n = n; s.n_spec = ncl; }
+    const long i = (long)blockIdx.x * 256 + tid;
+    if ((long)blockIdx.x * 256 >= n) return;
+    if (i < n && s.agc) {
+        const float2 v = b.s[i];
+        const float p = v.x * v.x + v.y * v.y;
+        float old = b.phist[min(i, (long)hn - 1)];
+        if (i >= hn) { const float2 o = b.s[i - hn]; old = o.x * o.x + o.y * o.y; }
+        b.pw[i] = p;
+        b.dterm[i] = (double)p - (double)old;
+    }
+    double m = 0.0;
+    if (i < ncl) {
+        const int last = i0 + (int)i * decim, first = last - decim + 1;
+        float2 acc = make_float2(0.0f, 0.0f);
+        if (first < 0) acc = s.open_sum;                    // the group that was open when the feed began
+        for (int j = max(first, 0); j <= last; j++) { const float2 v = b.s[j]; acc.x += v.x; acc.y += v.y; }
+        const float avgr = acc.x / (float)decim, avgi = acc.y / (float)decim;
+        m = (double)(avgr * avgr + avgi * avgi) / (32768.0 * 32768.0);
+        const int re = sdrx_to_q16(s.swap_iq ? avgi : avgr), im = sdrx_to_q16(s.swap_iq ? avgr : avgi);
+        reinterpret_cast<short2*>(b.spec)[i] = make_short2((short)re, (short)im);
+        if (i == ncl - 1) s.magsq = m;
+    }
+    sums[tid] = m; peaks[tid] = m;
+    __syncthreads();
+    for (int st = 128; st; st >>= 1) {
+        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmax(peaks[tid], peaks[tid + st]); }
+        __syncthreads();
+    }
+    if (tid == 0) { b.blk_sum[blockIdx.x] = sums[0]; b.blk_peak[blockIdx.x] = peaks[0]; }
+}
+
+// ---- 2. the moving-average sum after every sample: one wave per 16 channels (psum_rows); channels with the AGC off have no terms
+__global__ __launch_bounds__(64)
+void ssb_psum_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs, int n_ch)
+{
+    const int lane = threadIdx.x, c = blockIdx.x * PS_CH + lane;
+    const bool chain = lane < PS_CH && c < n_ch;
+    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
+        const int cc = min(c, n_ch - 1);                    // rows past the last channel: its pointers, no terms
+        term = bufs[cc].dterm; out = bufs[cc].tot;
+        if (chain) { n_mine = ch[cc].agc ? ch[cc].n : 0; sum = ch[cc].total; }
+    });
+    if (chain) ch[c].total_next = acc;
+}
+
+// ---- 3. one workgroup per channel, 1024 samples per trip, four consecutive samples per lane: m_u0, the gate counter, m_count
+// and the step pair as three scans in a row (wave scan by shuffles, the four wave totals through LDS), the factor, the
+// delay-line write and getStepValue() per sample; then the level accumulators
+__global__ __launch_bounds__(256)
+void ssb_gate_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs)
+{
+    __shared__ WfmClamp gmap[4], cmap[4];
+    __shared__ SsbPair pmap[4];
+    __shared__ double sums[256];
+    __shared__ double peaks[256];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    SsbChan& s = ch[c];
+    const SsbBufs b = bufs[c];
+    const int n = s.n, hn = s.hn, L = hn / 2, gate = s.gate;
+    const double thr = s.threshold, sd = s.step_delta;
+    const bool clamping = s.clamping != 0;
+    SsbCounters st; st.g = s.g; st.count = s.count; st.ud.U = s.U; st.ud.D = s.Dn;
+    if (!s.agc || !s.thr_enable) {
+        // no counter moves: agcVal is 10.0 or m_u0, getStepValue() is what the carried pair gives
+        const float svc = ssb_step_value(ssb_up(st.count, hn), st.ud, sd);
+        for (int i = tid; i < n; i += 256) {
+            const float2 v = b.s[i];
+            float a = 10.0f;
+            if (s.agc) {
+                const double u0 = ssb_u0((double)b.pw[i], b.tot[i], hn, clamping);
+                a = (float)u0;
+                if (i == n - 1) s.u0 = u0;
+            }
+            b.w[i] = make_float2(v.x * a, v.y * a);
+            b.sv[i] = svc;
+        }
+    } else {
+        for (int base = 0; base < n; base += 1024) {
+            const int i0 = base + tid * 4;
+            bool above[4], rst[4], up[4];
+            double magsq[4];
+            WfmClamp gm = wfm_identity(gate);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                above[k] = false; magsq[k] = 0.0;
+                if (i0 + k < n) {
+                    magsq[k] = (double)b.pw[i0 + k];
+                    above[k] = magsq[k] > thr;
+                    gm = wfm_compose(gm, ssb_gate_step(above[k], gate));
+                }
+            }
+            // a. gate counter
+            WfmClamp gi = wfm_wave_scan(gm, lane);
+            if (lane == 63) gmap[w] = gi;
+            __syncthreads();
+            WfmClamp pre = wfm_identity(gate);
+            for (int q = 0; q < w; q++) pre = wfm_compose(pre, gmap[q]);
+            WfmClamp ex = wfm_shfl_up(gi, 1);
+            if (lane == 0) ex = wfm_identity(gate);
+            int g = wfm_apply(wfm_compose(pre, ex), st.g);
+            WfmClamp all = gmap[0];
+            for (int q = 1; q < 4; q++) all = wfm_compose(all, gmap[q]);
+            st.g = wfm_apply(all, st.g);
+            WfmClamp cm = wfm_identity(hn);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                rst[k] = false;
+                if (i0 + k < n) {
+                    rst[k] = ssb_reset(above[k], g, gate);
+                    g = wfm_apply(ssb_gate_step(above[k], gate), g);
+                    cm = wfm_compose(cm, ssb_count_step(rst[k], above[k], hn));
+                }
+            }
+            // b. m_count
+            WfmClamp ci = wfm_wave_scan(cm, lane);
+            if (lane == 63) cmap[w] = ci;
+            __syncthreads();
+            pre = wfm_identity(hn);
+            for (int q = 0; q < w; q++) pre = wfm_compose(pre, cmap[q]);
+            ex = wfm_shfl_up(ci, 1);
+            if (lane == 0) ex = wfm_identity(hn);
+            int cnt = wfm_apply(wfm_compose(pre, ex), st.count);
+            all = cmap[0];
+            for (int q = 1; q < 4; q++) all = wfm_compose(all, cmap[q]);
+            st.count = wfm_apply(all, st.count);
+            SsbPair pm = ssb_pair_identity(L);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                up[k] = false;
+                if (i0 + k < n) {
+                    cnt = wfm_apply(ssb_count_step(rst[k], above[k], hn), cnt);
+                    up[k] = ssb_up(cnt, hn);
+                    pm = ssb_pair_compose(pm, ssb_pair_step(up[k], L));
+                }
+            }
+            // c. the step pair
+            SsbPair pi = ssb_pair_wave_scan(pm, lane);
+            if (lane == 63) pmap[w] = pi;
+            __syncthreads();
+            SsbPair ppre = ssb_pair_identity(L);
+            for (int q = 0; q < w; q++) ppre = ssb_pair_compose(ppre, pmap[q]);
+            SsbPair pex = ssb_pair_shfl_up(pi, 1);
+            if (lane == 0) pex = ssb_pair_identity(L);
+            SsbUD ud = ssb_pair_apply(ssb_pair_compose(ppre, pex), st.ud);
+            SsbPair pall = pmap[0];
+            for (int q = 1; q < 4; q++) pall = ssb_pair_compose(pall, pmap[q]);
+            st.ud = ssb_pair_apply(pall, st.ud);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (i0 + k < n) {
+                    const SsbUD was = ud;
+                    ud = ssb_pair_apply(ssb_pair_step(up[k], L), ud);
+                    const double u0 = ssb_u0(magsq[k], b.tot[i0 + k], hn, clamping);
+                    const float a = (float)ssb_agc_value(up[k], was, ud, L, sd, u0);
+                    const float2 v = b.s[i0 + k];
+                    b.w[i0 + k] = make_float2(v.x * a, v.y * a);
+                    b.sv[i0 + k] = ssb_step_value(up[k], ud, sd);
+                    if (i0 + k == n - 1) s.u0 = u0;
+                }
+            }
+            // no barrier here: each of gmap, cmap and pmap is read between its own barrier and the next one, and two
+            // barriers lie between those reads and the next trip's write of the same array
+        }
+    }
+    // level accumulators: the 256-group partials of ssb_level_kernel, in a fixed order
+    const int ncl = s.n_spec, nblk = (ncl + 255) / 256;
+    double ps = 0.0, pk = 0.0;
+    for (int j = tid; j < nblk; j += 256) { ps += b.blk_sum[j]; pk = fmax(pk, b.blk_peak[j]); }
+    sums[tid] = ps; peaks[tid] = pk;
+    __syncthreads();
+    for (int k = 128; k; k >>= 1) {
+        if (tid < k) { sums[tid] += sums[tid + k]; peaks[tid] = fmax(peaks[tid], peaks[tid + k]); }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        s.g = st.g; s.count = st.count; s.U = st.ud.U; s.Dn = st.ud.D;
+        if (ncl > 0) {
+            s.magsq_sum += sums[0];
+            if (peaks[0] > s.magsq_peak) s.magsq_peak = peaks[0];
+            s.magsq_count += ncl;
+        }
+    }
+}
+
+// what the delay line holds for stream index j of this feed (j < 0: the carried history of D + 1 writes)
+__device__ __forceinline__ float2 ssb_w_at(const SsbBufs& b, int D, long j) { return am_stream_at(b.whist, D + 1, (const float2*)b.w, j); }
+
+// ---- 4. per sample: the delayed sample times the step value, volume, conversion to the l, r pair
+__global__ __launch_bounds__(256)
+void ssb_out_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs)
+{
+    const int c = blockIdx.y;
+    SsbChan& s = ch[c];
+    const int n = s.n;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const SsbBufs& b = bufs[c];
+    const float2 x = ssb_w_at(b, s.D, i - 1 - s.D);
+    if (i == n - 1) s.audio_active = x.x != 0.0f ? 1 : 0;
+    int l = 0, r = 0;
+    if (!s.mute) {
+        const float sv = b.sv[i], vol = s.volume;
+        const float zr = x.x * sv, zi = x.y * sv;
+        if (s.binaural) {
+            const int a = sdrx_to_q16(zr * vol), q = sdrx_to_q16(zi * vol);
+            if (s.flip) { r = q; l = a; } else { r = a; l = q; }
+        } else {
+            const float demod = (float)((double)(zr + zi) * 0.7);
+            l = r = sdrx_to_q16(demod * vol);
+        }
+    }
+    reinterpret_cast<short2*>(b.audio)[i] = make_short2((short)l, (short)r);
+}
+
+// ---- 5. carry: the histories of the next feed (double-buffered: this feed's are still being read), the moving-average sum,
+// the spectrum counter and the open group's partial sum
+__global__ __launch_bounds__(256)
+void ssb_carry_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs)
+{
+    const int c = blockIdx.x, tid = threadIdx.x;
+    SsbChan& s = ch[c];
+    const SsbBufs b = bufs[c];
+    const int n = s.n, K = s.D + 1;
+    if (s.agc) for (int i = tid; i < s.hn; i += 256) b.phist_next[i] = am_hist_next(b.phist, s.hn, (const float*)b.pw, n, i);
+    for (int i = tid; i < K; i += 256) b.whist_next[i] = am_hist_next(b.whist, K, (const float2*)b.w, n, i);
+    if (tid == 0) {
+        s.total = s.total_next;
+        // the open group: what was carried if nothing closed, then the samples after the last close (fewer than decim)
+        const int i0 = ssb_first_close(s.usc, s.decim), ncl = s.n_spec;
+        float2 acc = ncl > 0 ? make_float2(0.0f, 0.0f) : s.open_sum;
+        for (int j = ncl > 0 ? i0 + (ncl - 1) * s.decim + 1 : 0; j < n; j++) { const float2 v = b.s[j]; acc.x += v.x; acc.y += v.y; }
+        s.open_sum = acc;
+        s.usc += (unsigned)n;
+    }
+}
+
+} // namespace sdrx
