@@ -856,6 +856,115 @@ int sdrx_ssb_get_timing(sdrx_ssb_t* h, double* total_ms, int64_t* feeds, int res
 int sdrx_ssb_last_launch(const sdrx_ssb_t* h, char* kernel_name, int name_cap,
                          int* grid, int* block, int* lds_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * UDPSrc bank: UDPSrc::feed (plugins/channelrx/udpsrc/udpsrc.cpp:136-321), N channels per handle, each fed with int16 I/Q at
+ * the channelizer's output rate; every feed produces the samples UDPSrc hands to its UDPSink, i.e. the datagram payload:
+ *     c = Complex(re, im) * m_nco.nextIQ();  m_interpolator.decimate(&dist, c, &ci)        as sdrx_backend_* (filt_mode 0)
+ *     per ci: inMagSq = (double)(re*re + im*im);  m_inMovingAverage.feed(inMagSq / 2^30);  m_inMagsq = average();
+ *             Sample((qint16) re, (qint16) im) to m_sampleBuffer (the spectrum);  calculateSquelch(m_inMagsq);
+ *             one payload sample by format (open = m_squelchOpen after this sample's calculateSquelch):
+ *       0 FormatIQ16         {int16, int16}  open: (qint16)(re * gain), (qint16)(im * gain); closed: 0, 0
+ *       1 FormatIQ24         {int32, int32}  the same two qint16, each << 8
+ *       2 FormatNFM          {int16, int16}  d = open ? m_phaseDiscri.phaseDiscriminator(ci) * gain : 0; both (int16)(d * 32768.0)
+ *       3 FormatNFMMono      int16           (int16)(d * 32768.0)
+ *       8 FormatAMMono       int16           (qint16)(Real)(open ? sqrt(inMagSq) * agcFactor * gain : 0)
+ *       9 FormatAMNoDCMono   int16           open: r = sqrt(inMagSq); m_amMovingAverage.feed(r); (qint16)(Real)((r - average()) * agcFactor * gain)
+ *      10 FormatAMBPFMono    int16           open: (qint16)(Real)(m_bandpass.filter(sqrt(inMagSq)) / 301.0 * agcFactor * gain);  closed: 0
+ * The payload element is 4, 8, 4, 2, 2, 2, 2 bytes for formats 0, 1, 2, 3, 8, 9, 10 (sdrx_udpsrc_sample_bytes).
+ * Formats 0, 1, 8, 9, 10, the spectrum Samples, m_inMagsq and the squelch state are bit-identical to the strict-IEEE scalar
+ * reference build.  Formats 2 and 3 inherit the back-end's std::arg ruling (discri = 2 above): a double atan2 rounded once,
+ * <= 3 ulp from glibc's atan2f, so with |d| < 8 a payload int16 equals the reference's or differs by 1 modulo 2^16.
+ * Any feed length is valid (0 included); NCO phase, resampler window and distance, both moving averages, the squelch
+ * counters, m_m1Sample, the Bandpass ring and the running sample count carry across feeds.
+ * A fresh handle is the constructed object after applySettings(settings, true), applyChannelSettings(in_rate, offset, true)
+ * and start():
+ *   - m_sampleDistanceRemain starts at in_rate / output_sample_rate (a float quotient, also the step), NOT at 0 as in the
+ *     demodulators: the first output appears after floor(step) inputs
+ *   - the squelch starts closed with both counters 0; m_squelchGate = m_squelchRelease = (int)((output_sample_rate *
+ *     squelch_gate) / 100) in float arithmetic; above = !squelch_enabled || m_inMagsq > pow(10.0, squelch_db / 10.0);
+ *     gate 0 is stateless (open = above)
+ *   - m_inMovingAverage has (int)(rate * 0.01) entries, m_amMovingAverage (int)(rate * 0.005), both filled with 1e-10 and
+ *     a sum of size * 1e-10 (MovingAverage<double>::resize)
+ *   - m_m1Sample starts at 0 (start() resets it); the discriminator runs on OPEN samples only, so m_m1Sample is the last
+ *     open sample; m_phaseDiscri.setFMScaling(rate / (2.0f * fm_deviation))
+ *   - m_amMovingAverage and m_bandpass (Bandpass<double>, 301 Real taps, 300 Hz .. rf_bandwidth / 2 at the output rate) are
+ *     fed on open samples only; m_interpolator.create(16, in_rate, rf_bandwidth / 2.0)
+ *   - the payload conversions are what x86-64 gives: float -> qint16 is cvttss2si and the low 16 bits, double -> int16_t
+ *     cvttsd2si and the low 16 bits; outside the int32 range, and for NaN, both give 0
+ *   - left out: the SSB formats 4 .. 7 (SDRX_EINVAL).  They run fftfilt(0, bw / 2 / rate, 512), and the 512-point g_fft
+ *     network (bitrevR2, one radix-4 stage, two radix-8 stages) is not among the device's (1024 and 2048 only); they also
+ *     multiply ci by the AGC factor in front of the filter, which splits the front.  The follow-up.
+ *   - agc != 0 with formats 8 .. 10: agcFactor = m_agc.feedAndGetValue(ci) on EVERY sample, open or not, and inMagSq = getMagSq(),
+ *     the same (double)(re*re + im*im).  MagAGC (sdrbase/dsp/agc.cpp:98-182) as UDPSrc sets it up: (9600, 16384.0f, 1e-6), clampMax
+ *     2^30 with clamping on, m_squared false, the threshold enabled; resize((int)(rate / 5), (int)(rate / 20), 16384) leaves the
+ *     history 0 with sum 0, m_stepUpCounter 0, m_stepDownCounter = the step length; setStepDownDelay((int)((rate * (squelch_gate ==
+ *     0 ? 1 : squelch_gate)) / 100)); setGate((int)(rate * 0.05)); setThreshold(powerFromdB(squelch_db) * (1 << 23)) -- 2^23 in the
+ *     16-bit build too, reproduced.  The factor multiplies the AM payload in double in front of the gain.  Zero input gives
+ *     m_u0 = inf and a NaN amplitude, whose (qint16) is x86-64's 0, as in sdrx_ssb_*.  The history is as long as the rate makes it.
+ *     Formats 0 .. 3 never feed the AGC; they accept and ignore the flag as the reference does
+ *   - left out: m_outMovingAverage / m_magsq (GUI only), the audio return socket and AudioFifo, sockets of any kind (the
+ *     caller cuts the stream into datagrams of 512 / element-size samples; sdrx_udpsrc_total gives the running count), the
+ *     interpolating branch and mid-stream retune or settings change -- a channel is configured at creation
+ * SDRX_EINVAL also for output_sample_rate outside 1000 .. min(in_rate, 1e7), rf_bandwidth outside (0, 1e7] (format 10: above
+ * 600), fm_deviation <= 0, squelch_gate outside 0 .. 1000, squelch_db outside -300 .. 300, a non-finite gain.  (output_sample_rate >= 1000 keeps every window at 5 entries or more.)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_udpsrc sdrx_udpsrc_t;
+typedef struct sdrx_udpsrc_cfg {
+    int32_t in_rate;              /* channelizer output rate (m_inputSampleRate) */
+    int32_t nco_freq;             /* m_nco.setFreq(nco_freq, in_rate): UDPSrc passes -frequencyOffset */
+    float   output_sample_rate;   /* m_outputSampleRate, a float in the reference; 1000 <= rate <= in_rate */
+    int32_t sample_format;        /* UDPSrcSettings::SampleFormat, the reference's values: 0, 1, 2, 3, 8, 9, 10 */
+    float   rf_bandwidth;         /* m_rfBandwidth */
+    int32_t fm_deviation;         /* m_fmDeviation, Hz; > 0 */
+    float   gain;                 /* m_gain */
+    int32_t squelch_db;           /* m_squelchdB, power dB */
+    int32_t squelch_gate;         /* m_squelchGate, 1/100 s; 0 .. 1000 */
+    int32_t squelch_enabled;      /* m_squelchEnabled */
+    int32_t agc;                  /* m_agc: MagAGC for formats 8 .. 10; ignored by formats 0 .. 3 */
+} sdrx_udpsrc_cfg;
+int sdrx_udpsrc_create(sdrx_udpsrc_t** out, int device, int32_t n_ch, const sdrx_udpsrc_cfg* cfg);
+int sdrx_udpsrc_destroy(sdrx_udpsrc_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_udpsrc_reset(sdrx_udpsrc_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to UDPSrc::feed) */
+int sdrx_udpsrc_feed(sdrx_udpsrc_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_udpsrc_feed_dev(sdrx_udpsrc_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_udpsrc_feed_bank(sdrx_udpsrc_t* h, sdrx_chan_bank_t* bank);
+/* bytes of one payload sample of channel ch: 4, 8, 4, 2, 2, 2, 2 for formats 0, 1, 2, 3, 8, 9, 10 (<0: error) */
+int32_t sdrx_udpsrc_sample_bytes(sdrx_udpsrc_t* h, int32_t ch);
+/* raw payload bytes of the last feed for channel ch; returns the number of SAMPLES written (<0: error) */
+int64_t sdrx_udpsrc_read(sdrx_udpsrc_t* h, int32_t ch, void* payload, int64_t cap_samples);
+/* device-side view of the same (valid until the next feed): pointer and number of samples */
+int sdrx_udpsrc_last_dev(sdrx_udpsrc_t* h, int32_t ch, const void** d_payload, int64_t* n_samples);
+/* the Samples {re, im} the last feed handed to the spectrum sink (m_sampleBuffer), one per payload sample */
+int64_t sdrx_udpsrc_read_spectrum(sdrx_udpsrc_t* h, int32_t ch, int16_t* samples_iq, int64_t cap_samples);
+int sdrx_udpsrc_spectrum_last_dev(sdrx_udpsrc_t* h, int32_t ch, const int16_t** d_samples_iq, int64_t* n_samples);
+/* m_squelchOpen after the last feed: 1 / 0 (<0: error); m_squelchOpenCount and m_squelchCloseCount */
+int sdrx_udpsrc_squelch_open(sdrx_udpsrc_t* h, int32_t ch);
+int sdrx_udpsrc_squelch_counts(sdrx_udpsrc_t* h, int32_t ch, int32_t* open_count, int32_t* close_count);
+/* m_inMagsq after the last feed, exact (0 until the first output sample, as the constructor leaves it) */
+int sdrx_udpsrc_in_magsq(sdrx_udpsrc_t* h, int32_t ch, double* in_magsq);
+/* payload samples since creation or reset (<0: error): datagram k of the stream holds samples [k * M, (k + 1) * M), M = 512 / element size */
+int64_t sdrx_udpsrc_total(sdrx_udpsrc_t* h, int32_t ch);
+/* design products, for inspection: polyphase taps [16][ntaps] and the 151 folded Bandpass taps (Reals, widened), NCO increment,
+ * windows[3] = entries of m_inMovingAverage, m_amMovingAverage, m_outMovingAverage, gate and release in samples, m_squelch,
+ * the discriminator's scaling, the distance step, agc_ints[4] = MagAGC's history length, step length, step-down delay and gate in
+ * samples, and its threshold powerFromdB(squelch_db) * 2^23 */
+int sdrx_udpsrc_get_design(sdrx_udpsrc_t* h, int32_t ch, int32_t* ntaps_per_phase, double* taps, int32_t taps_cap, double* bandpass_taps,
+                           int32_t* nco_inc, int32_t* windows, int32_t* squelch_gate, int32_t* squelch_release, double* squelch_level,
+                           float* fm_scaling, float* distance_step, int32_t* agc_ints, double* agc_threshold);
+int sdrx_udpsrc_sync(sdrx_udpsrc_t* h);
+int sdrx_udpsrc_set_stream(sdrx_udpsrc_t* h, void* hip_stream);
+int sdrx_udpsrc_get_stream(sdrx_udpsrc_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_udpsrc_set_timing(sdrx_udpsrc_t* h, int enabled);
+int sdrx_udpsrc_get_timing(sdrx_udpsrc_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the output kernel of the last feed (discriminator, averages, Bandpass, gain, conversion): udp_out_kernel, its grid, block and LDS bytes */
+int sdrx_udpsrc_last_launch(const sdrx_udpsrc_t* h, char* kernel_name, int name_cap,
+                            int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

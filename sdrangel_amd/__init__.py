@@ -196,6 +196,23 @@ def lib() -> C.CDLL:
         "sdrx_ssb_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_ssb_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
                                           C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+        "sdrx_udpsrc_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_udpsrc_destroy": (C.c_int, [vp]),
+        "sdrx_udpsrc_reset": (C.c_int, [vp]),
+        "sdrx_udpsrc_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_udpsrc_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_udpsrc_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_udpsrc_sample_bytes": (i32, [vp, i32]),
+        "sdrx_udpsrc_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_udpsrc_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_udpsrc_read_spectrum": (i64, [vp, i32, vp, i64]),
+        "sdrx_udpsrc_spectrum_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_udpsrc_squelch_open": (C.c_int, [vp, i32]),
+        "sdrx_udpsrc_squelch_counts": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "sdrx_udpsrc_in_magsq": (C.c_int, [vp, i32, C.POINTER(C.c_double)]),
+        "sdrx_udpsrc_total": (i64, [vp, i32]),
+        "sdrx_udpsrc_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(i32),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), vp, C.POINTER(C.c_double)]),
         "sdrx_fdecim_state_bytes": (i64, [vp]),
         "sdrx_fdecim_get_state": (C.c_int, [vp, vp]),
         "sdrx_fdecim_set_state": (C.c_int, [vp, vp]),
@@ -245,7 +262,7 @@ def lib() -> C.CDLL:
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
                 "wfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
-                "ssb": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
         for name in names:
@@ -1031,6 +1048,132 @@ class SsbDemodBank(_DemodBank):
         self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc), C.byref(hn), C.byref(gate),
                    C.byref(thr), C.byref(vol))
         return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value, hn.value, gate.value, thr.value, vol.value
+
+
+class UdpSrcCfg(C.Structure):
+    """sdrx_udpsrc_cfg: one UDPSrc (in_rate, nco_freq = -frequencyOffset, UDPSrcSettings with the reference's SampleFormat values)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("output_sample_rate", C.c_float), ("sample_format", C.c_int32),
+                ("rf_bandwidth", C.c_float), ("fm_deviation", C.c_int32), ("gain", C.c_float), ("squelch_db", C.c_int32),
+                ("squelch_gate", C.c_int32), ("squelch_enabled", C.c_int32), ("agc", C.c_int32)]
+
+
+#: numpy dtype of one payload sample per UDPSrcSettings::SampleFormat: Sample16, Sample24 (two int32), Sample16, int16 ...
+UDPSRC_PAYLOAD_DTYPES = {0: np.dtype((np.int16, 2)), 1: np.dtype((np.int32, 2)), 2: np.dtype((np.int16, 2)), 3: np.dtype(np.int16),
+                         8: np.dtype(np.int16), 9: np.dtype(np.int16), 10: np.dtype(np.int16)}
+#: UDPSrc::udpBlockSize: bytes of one datagram
+UDPSRC_BLOCK_BYTES = 512
+
+
+class UdpPayloadCutter:
+    """UDPSink<T>::write on the host: the running payload stream of one channel cut into the reference's datagrams, exactly
+    samples [k * M, (k + 1) * M) with M = 512 / sizeof(T) (128, 256 or 64 samples); the remainder waits for the next feed."""
+
+    def __init__(self, sample_bytes: int):
+        self.sample_bytes = int(sample_bytes)
+        self.per_datagram = UDPSRC_BLOCK_BYTES // self.sample_bytes
+        self._rest = b""
+        self.sent = 0                     # samples handed out in datagrams so far
+
+    def push(self, raw: bytes) -> list:
+        data = self._rest + bytes(raw)
+        k = len(data) // UDPSRC_BLOCK_BYTES
+        self._rest = data[k * UDPSRC_BLOCK_BYTES:]
+        self.sent += k * self.per_datagram
+        return [data[i * UDPSRC_BLOCK_BYTES: (i + 1) * UDPSRC_BLOCK_BYTES] for i in range(k)]
+
+    @property
+    def pending(self) -> int:
+        """samples waiting for a full datagram"""
+        return len(self._rest) // self.sample_bytes
+
+
+class UdpSrcBank(_DemodBank):
+    """N UDPSrc channels (UDPSrc::feed; formats IQ16, IQ24, NFM, NFMMono, AMMono, AMNoDCMono, AMBPFMono): int16 I/Q at the
+    channelizer's output rate in (MagAGC for the AM formats when agc is set), the datagram payload samples and the spectrum Samples out.  No socket is opened anywhere:
+    payloads(ch) returns the bytes of the datagrams the reference would send."""
+    _prefix, _cfg = "udpsrc", UdpSrcCfg
+
+    def __init__(self, cfgs, device: int = 0):
+        super().__init__(cfgs, device)
+        self._cutters = [UdpPayloadCutter(self.sample_bytes(c)) for c in range(self.n_ch)]
+
+    def reset(self):
+        super().reset()
+        self._cutters = [UdpPayloadCutter(self.sample_bytes(c)) for c in range(self.n_ch)]
+
+    def sample_bytes(self, ch: int) -> int:
+        n = self._fn("sample_bytes")(self._h, ch)
+        if n < 0:
+            raise SdrxError(f"sdrx_udpsrc_sample_bytes rc={n}: {lib().sdrx_last_error().decode()}")
+        return n
+
+    def read_raw(self, ch: int) -> bytes:
+        """the last feed's payload samples as bytes"""
+        cap, size = self.last_dev(ch)[1], self._cutters[ch].sample_bytes
+        out = np.empty(max(cap, 1) * size, np.uint8)
+        n = self._fn("read")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_udpsrc_read rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[: n * size].tobytes()
+
+    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
+        """the last feed's payload samples: [n, 2] int16 (formats 0, 2), [n, 2] int32 (format 1) or [n] int16"""
+        dt = UDPSRC_PAYLOAD_DTYPES[self.cfgs[ch].sample_format]
+        a = np.frombuffer(self.read_raw(ch), dt.base).reshape((-1,) + dt.shape)
+        return (a if cap is None else a[:cap]).copy()
+
+    def payloads(self, ch: int) -> list:
+        """the datagrams (512 bytes each) that the last feed completes for channel ch.  Call it after every feed: the handle keeps
+        the last feed's samples only.  A second call for the same feed returns nothing, and a call after a feed whose samples were
+        never collected raises, because the datagram stream would go on with a hole in it."""
+        cut = self._cutters[ch]
+        new = self.total(ch) - (cut.sent + cut.pending)     # samples the cutter has not been given yet
+        if new == 0:
+            return []
+        if new != self.last_dev(ch)[1]:
+            raise SdrxError(f"UdpSrcBank.payloads({ch}): {new} samples are outstanding but the last feed holds {self.last_dev(ch)[1]}: "
+                            "payloads() was not called after an earlier feed")
+        return cut.push(self.read_raw(ch))
+
+    def spectrum_last_dev(self, ch: int):
+        p, n = C.c_void_p(), C.c_int64()
+        self._call("spectrum_last_dev", ch, C.byref(p), C.byref(n))
+        return p.value or 0, n.value
+
+    def read_spectrum(self, ch: int) -> np.ndarray:
+        """the Samples the last feed handed to the spectrum sink, as an [n, 2] array of (re, im)"""
+        cap = self.spectrum_last_dev(ch)[1]
+        out = np.empty((max(cap, 1), 2), np.int16)
+        n = self._fn("read_spectrum")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_udpsrc_read_spectrum rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def squelch_counts(self, ch: int):
+        """(m_squelchOpenCount, m_squelchCloseCount)"""
+        a, b = C.c_int32(), C.c_int32()
+        self._call("squelch_counts", ch, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def in_magsq(self, ch: int) -> float:
+        v = C.c_double()
+        self._call("in_magsq", ch, C.byref(v))
+        return v.value
+
+    def total(self, ch: int) -> int:
+        n = self._fn("total")(self._h, ch)
+        if n < 0:
+            raise SdrxError(f"sdrx_udpsrc_total rc={n}: {lib().sdrx_last_error().decode()}")
+        return n
+
+    def design(self, ch: int) -> dict:
+        nt, inc, gate, rel, lvl, fms, step = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_float(), C.c_float()
+        taps, bp, win, agc = np.zeros(16 * 128, np.float64), np.zeros(151, np.float64), np.zeros(3, np.int32), np.zeros(4, np.int32)
+        thr = C.c_double()
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, bp.ctypes.data, C.byref(inc), win.ctypes.data, C.byref(gate),
+                   C.byref(rel), C.byref(lvl), C.byref(fms), C.byref(step), agc.ctypes.data, C.byref(thr))
+        return {"agc": agc.tolist(), "agc_threshold": thr.value, "ntaps": nt.value, "taps": taps[: 16 * nt.value].copy(), "bandpass": bp, "nco_inc": inc.value, "windows": win.tolist(),
+                "gate": gate.value, "release": rel.value, "level": lvl.value, "fm_scaling": fms.value, "step": step.value}
 
 
 class AudioTailCfg(C.Structure):

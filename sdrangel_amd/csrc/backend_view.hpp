@@ -12,5 +12,8 @@ struct BackendView {
 int backend_view(sdrx_backend_t* b, int32_t ch, BackendView* v);
 // hip_stream == nullptr: back to the back-end's own stream.  Waits for the work queued so far.
 int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream);
+// A back-end that has not been fed yet: channel ch resamples with this distance step (UDPSrc divides by a float rate) and its
+// m_sampleDistanceRemain starts at `distance` instead of 0 (UDPSrc starts at one step).  step >= 1, distance >= 0.
+int backend_start_at(sdrx_backend_t* b, int32_t ch, float step, float distance);
 
 } // namespace sdrx

@@ -85,6 +85,18 @@ static int ensure_capacity(sdrx_backend* b, int c, int64_t n_in)
     return SDRX_OK;
 }
 
+// the distance step and, where step * 2^q is an integer, the closed-form schedule's constants
+static void set_step(BeChan& s, float step)
+{
+    s.step = step;
+    s.dy_q = -1; s.dy_S = 0;
+    if (s.step >= 1.0f && !getenv("SDRX_BE_SERIAL_SCHEDULE"))
+        for (int q = 0; q <= 10; q++) {
+            const float v = s.step * (float)(1 << q);                                  // exact (power of two)
+            if (v == std::floor(v) && v < (float)(1 << 20)) { s.dy_q = q; s.dy_S = (int)v; break; }
+        }
+}
+
 extern "C" {
 
 int sdrx_backend_destroy(sdrx_backend_t* b)
@@ -218,13 +230,7 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
         BeChan& s = b->h_chan[(size_t)c];
         std::memset(&s, 0, sizeof s);
         s.nco_inc = (int)(((float)k.nco_freq * BE_NCO_N) / (float)k.in_rate);          // NCO::setFreq (float math, truncation)
-        s.step = (float)k.in_rate / (float)k.out_rate;
-        s.dy_q = -1; s.dy_S = 0;
-        if (s.step >= 1.0f && !getenv("SDRX_BE_SERIAL_SCHEDULE"))
-            for (int q = 0; q <= 10; q++) {
-                const float v = s.step * (float)(1 << q);                                  // exact (power of two)
-                if (v == std::floor(v) && v < (float)(1 << 20)) { s.dy_q = q; s.dy_S = (int)v; break; }
-            }
+        set_step(s, (float)k.in_rate / (float)k.out_rate);
         s.ntaps = nt; s.phase_steps = 16;
         s.taps_off = b->taps_off[(size_t)c]; s.filt_mode = k.filt_mode; s.filt_off = b->filt_off[(size_t)c];
         s.discri = k.discri; s.fm_scaling = k.fm_scaling;
@@ -434,6 +440,23 @@ int backend_view(sdrx_backend_t* b, int32_t c, BackendView* v)
 int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream)
 {
     return b ? b->core.set_stream(hip_stream) : SDRX_EINVAL;
+}
+
+int backend_start_at(sdrx_backend_t* b, int32_t c, float step, float distance)
+{
+    if (!b || c < 0 || c >= b->n_ch || !(step >= 1.0f) || !(distance >= 0.0f)) { set_error("backend_start_at: bad argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
+    BeChan& s = b->h_chan[(size_t)c];                       // the config part and a fresh state
+    set_step(s, step);
+    b->any_dyadic = false;                                  // recomputed: the channel may have left the closed form
+    for (const BeChan& k : b->h_chan) b->any_dyadic = b->any_dyadic || k.dy_q >= 0;
+    // h_chan keeps distance 0 (it mirrors the configuration; nothing uploads it again after create): the start lives on the
+    // device only, and a caller that wants a fresh stream makes a fresh back-end and calls this again (sdrx_udpsrc_reset)
+    BeChan fresh = s;
+    fresh.distance = distance;
+    SDRX_HIP(hipMemcpy(b->d_chan + c, &fresh, sizeof fresh, hipMemcpyHostToDevice));
+    return SDRX_OK;
 }
 
 } // namespace sdrx
