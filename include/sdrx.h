@@ -407,7 +407,9 @@ int sdrx_sdriq_write_header(uint8_t* bytes24, const sdrx_sdriq_header* hdr);
  *   in_kind  0 float I/Q            1 int16 I/Q, scaled by decimation_scale<input_bits> (8|12|16) at the output
  *   out_kind 0 int16 Sample = (int16)(v * SDR_RX_SCALED), truncation (float input only)      1 float re, im
  * n_elems = the reference's nbIAndQ (floats or int16s); whole groups only, tail dropped; filter state carried.
- * Results are bit-identical to the reference built without -ffast-math (same operation order, no FMA). */
+ * Results are bit-identical to the reference built without -ffast-math (same operation order, no FMA).
+ * The out_kind 0 conversion is what x86-64 gives: cvttss2si / cvttsd2si and the low 16 bits, so a product outside the int32
+ * range, and NaN, give 0. */
 typedef struct sdrx_fdecim sdrx_fdecim_t;
 #define SDRX_FD_IN_F32  0
 #define SDRX_FD_IN_I16  1
@@ -460,7 +462,8 @@ int sdrx_dccorr_process_dev(sdrx_dccorr_t* h, const int16_t* d_iq, int16_t* d_ou
  * amplitude imbalance estimated by 128-deep float/double moving averages, in the reference's statement order.  The
  * recurrence is serial per stream, so ONE handle serves `n_streams` device streams side by side (one lane each).
  * Buffers are rewritten in place like the reference rewrites the FIFO span.  State carries across calls; reset = freshly
- * constructed engine members. */
+ * constructed engine members.  The float -> qint16 conversion of both outputs is what x86-64 gives: cvttss2si and the low
+ * 16 bits, so a product outside the int32 range, and NaN (the amplitude average after a negative residue), give 0. */
 typedef struct sdrx_iqimb sdrx_iqimb_t;
 int sdrx_iqimb_create(sdrx_iqimb_t** h, int device, int32_t n_streams);
 int sdrx_iqimb_destroy(sdrx_iqimb_t* h);

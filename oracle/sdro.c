@@ -507,6 +507,14 @@ static void mavg_i_put(mavg_i* m, int32_t v)
     else { m->total += v - m->s[m->idx]; m->s[m->idx] = v; m->idx = (m->idx + 1) % 1024; }
 }
 
+/* (qint16) of a float on x86-64: cvttss2si to int32 (0x80000000 when out of range or NaN: zq is NaN once avgAmp is), then
+ * the low 16 bits.  Written out because the plain C cast is undefined outside the int32 range. */
+static int16_t q16_f(float v)
+{
+    const int32_t i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : (int32_t)0x80000000u;
+    return (int16_t)i;
+}
+
 struct sdro_iqimb { mavg_i iBeta, qBeta; mavg_fd II, IQ, II2, QQ2; mavg_dd Phi, Amp; };
 
 sdro_iqimb* sdro_iqimb_new(void) { return (sdro_iqimb*)calloc(1, sizeof(sdro_iqimb)); }
@@ -524,7 +532,7 @@ void sdro_iqimb_process(sdro_iqimb* d, const int16_t* iq, int64_t n_cplx, int16_
         mavg_fd_put(&d->II2, xi * xi); mavg_fd_put(&d->QQ2, yq * yq);
         if (d->QQ2.total / 128 != 0) mavg_dd_put(&d->Amp, sqrt((d->II2.total / 128) / (d->QQ2.total / 128)));
         const float zq = (float)((d->Amp.total / 128) * (double)yq);
-        out[2 * n]     = (int16_t)(int32_t)(xi * 32768.0f);
-        out[2 * n + 1] = (int16_t)(int32_t)(zq * 32768.0f);
+        out[2 * n]     = q16_f(xi * 32768.0f);
+        out[2 * n + 1] = q16_f(zq * 32768.0f);
     }
 }

@@ -94,6 +94,19 @@ static float in_at(const sdro_fdecim* d, const void* in, long i)
     return d->in_kind == 0 ? ((const float*)in)[i] : (float)((const int16_t*)in)[i];
 }
 
+/* (qint16) of a float / a double on x86-64: cvttss2si / cvttsd2si to int32 (0x80000000 when out of range or NaN), then the
+ * low 16 bits.  Written out because the plain C cast is undefined outside the int32 range. */
+static int16_t q16_f(float v)
+{
+    const int32_t i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : (int32_t)0x80000000u;
+    return (int16_t)i;
+}
+static int16_t q16_d(double v)
+{
+    const int32_t i = (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : (int32_t)0x80000000u;
+    return (int16_t)i;
+}
+
 int32_t sdro_fdecim_process(sdro_fdecim* d, const void* in, int32_t n_elems, void* out)
 {
     const int grp = sdro_fdecim_group(d->log2, d->fcpos);
@@ -156,8 +169,8 @@ int32_t sdro_fdecim_process(sdro_fdecim* d, const void* in, int32_t n_elems, voi
         }
         if (d->out_kind == 0) {                 /* DecimatorsFI: setReal(v * SDR_RX_SCALED); decimate1 multiplies in float */
             int16_t* o = (int16_t*)out;
-            if (L == 0) { o[2*k] = (int16_t)(int32_t)(vI * 32768.0f); o[2*k+1] = (int16_t)(int32_t)(vQ * 32768.0f); }
-            else        { o[2*k] = (int16_t)(int32_t)(vI * 32768.0);  o[2*k+1] = (int16_t)(int32_t)(vQ * 32768.0); }
+            if (L == 0) { o[2*k] = q16_f(vI * 32768.0f); o[2*k+1] = q16_f(vQ * 32768.0f); }
+            else        { o[2*k] = q16_d(vI * 32768.0);  o[2*k+1] = q16_d(vQ * 32768.0); }
         } else { float* o = (float*)out; o[2*k] = vI; o[2*k+1] = vQ; }
     }
     free(bufI); free(bufQ); free(tI); free(tQ);

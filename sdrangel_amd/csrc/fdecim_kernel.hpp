@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "dsp_device.hpp"
 
 namespace sdrx {
 
@@ -103,12 +104,15 @@ template<int IN> __device__ __forceinline__ float2 fd_pre(const void* in, long p
     return fe == FD_FE_ID ? FdIn<IN>::sample(in, p) : FdIn<IN>::combo(in, p, fe);
 }
 
-// output conversion.  out_kind 0: DecimatorsFI, (int16)(v * 32768.0) -- the double product of a float and 2^15 is the
-// float product, conversion truncates; 1: float, times `scale` for DecimatorsIF (scale = 1 otherwise: exact)
+// output conversion.  out_kind 0: DecimatorsFI, (qint16)(v * 32768.0) (decimate1: v * 32768.0f) as x86-64 converts it:
+// truncation to int32, 0x80000000 out of that range and for NaN, then the low 16 bits (sdrx_to_q16).  The float product
+// stands for the double one: times 2^15 is exact in float up to overflow, and a product that overflows float is out of
+// the int32 range in double as well, so both convert to 0.  1: float, times `scale` for DecimatorsIF (scale = 1
+// otherwise: exact)
 __device__ __forceinline__ void fd_store(void* out, long k, float2 v, int out_kind, float scale)
 {
     if (out_kind == 0) {
-        const int re = (int)(v.x * 32768.0f), im = (int)(v.y * 32768.0f);
+        const int re = sdrx_to_q16(v.x * 32768.0f), im = sdrx_to_q16(v.y * 32768.0f);
         static_cast<uint32_t*>(out)[k] = ((uint32_t)re & 0xffffu) | ((uint32_t)im << 16);
     } else {
         static_cast<float2*>(out)[k] = make_float2(v.x * scale, v.y * scale);

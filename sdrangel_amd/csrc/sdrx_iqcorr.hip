@@ -10,6 +10,7 @@
 // cannot be spread along time bit-exactly.  sdrx_iqimb_* (end of this file) offers it the only exact way: one lane per
 // device stream walks its stream sample by sample (the reference's statement order, strict IEEE), many streams side by side.
 #include "sdrx_common.hpp"
+#include "dsp_device.hpp"
 #include <new>
 #include <vector>
 
@@ -238,7 +239,7 @@ void iqimb_kernel(IqImbState* __restrict__ states, const IqImbJob* __restrict__ 
                     else { st.tAmp += a - st.sAmp[st.idxAmp]; st.sAmp[st.idxAmp] = a; st.idxAmp = (st.idxAmp + 1) & 127; }
                 }
                 const float zq = (float)((st.tAmp / 128.0) * (double)yq);
-                const int yr = (int)(xi * 32768.0f), yi2 = (int)(zq * 32768.0f);        // float -> int (truncation), then the low 16 bits
+                const int yr = sdrx_to_q16(xi * 32768.0f), yi2 = sdrx_to_q16(zq * 32768.0f);   // float -> qint16 as x86-64: 0 when out of the int32 range or NaN
                 io[k] = ((uint32_t)yr & 0xffffu) | ((uint32_t)yi2 << 16);
             }
         }
