@@ -49,7 +49,7 @@ std::string lower_job(const TkMJob& j, int PI, int PO, TkLJob& r)
 }
 
 // the root arms: which kinds there are, and that they sit where the kernel's root fill and root history copy will look for them
-std::string lower_root(const TkSubtree& st, TkLRoot& r)
+std::string lower_root(const TkSubtree& st, const TkArray* arr, TkLRoot& r)
 {
     const int P = mx_pitch(0) / 4;                          // the tables count dwords
     r.base = 4 * st.rootE_I;
@@ -63,6 +63,49 @@ std::string lower_root(const TkSubtree& st, TkLRoot& r)
     if (r.kinds & MX_ROOT_O) { if (st.rootO_I != at || st.rootO_Q != at + P) return "lower: root odd arms not at 2 pitches"; at += 2 * P; }
     if (r.kinds & MX_ROOT_A) { if (st.rootA_I != at || st.rootA_Q != at + P) return "lower: root alternating arms not behind the others"; }
     if (st.root_arr_cnt != mx_root_arrays(r.kinds)) return "lower: unexpected root array count";
+    // the root histories: the first slots, in arm order
+    for (int k = 0; k < st.root_arr_cnt; k++)
+        if (arr[k].off != st.rootE_I + k * P || arr[k].len != P || arr[k].store != st.store_base + 16 * k) return "lower: root history slots not in arm order";
+    return {};
+}
+
+// The history copies of a level's tail jobs (chan_lower.hpp: MX_TAIL_BIT).  `jobs`: the level's lowered jobs.  Marks the last job
+// of every entry that has arrays and checks what the kernel relies on: the job's arrays are one run of the level's arrays, PO
+// bytes apart, their slots 16 dwords apart in the same order, and every array of the level belongs to exactly one tail job.
+std::string mark_tails(const TkSubtree& st, const TkLevel& lv, const TkArray* arr, int PO, std::vector<TkLJob>& jobs)
+{
+    if (lv.nout < 256 || lv.nout % 256) return "lower: a level with part of a job per entry";
+    if (lv.arr_cnt && (lv.arr_len * 4 != PO || lv.arr_len < 16 + 64)) return "lower: level arrays of another length";
+    std::vector<int> owner((size_t)lv.arr_cnt, 0);
+    // what the level reads and what it produces are two runs of arrays that do not meet: no job reads a head of this phase's arrays
+    const int rd0 = 4 * lv.prev_off, rd1 = rd0 + 4 * lv.prev_arr_cnt * lv.in_len, wr0 = 4 * lv.arr_off, wr1 = wr0 + lv.arr_cnt * PO;
+    if (lv.arr_cnt && rd0 < wr1 && wr0 < rd1) return "lower: a level that reads the arrays it produces";
+    for (TkLJob& r : jobs) {
+        const int f0 = mx_flags(r.meta, 0), f1 = mx_flags(r.meta, 1), n0 = mx_arm_arrays(f0), n = n0 + mx_arm_arrays(f1);
+        if (r.out0 < 0 || r.out0 > lv.nout - 256 || r.out0 % 256) return "lower: a job off the entry's job grid";
+        if (r.b < rd0 || r.b >= rd1 || r.c < rd0 || r.c >= rd1) return "lower: a job that reads outside the level's input arrays";
+        // a job's 64 dwords per array sit at out0 bytes behind the 16-dword head of an array of the level: only the entry's last job
+        // reaches the array's tail, and no job stores into a head
+        for (int k = 0; k < 2; k++) {
+            const int at = r.o[k] - 4 * (HIST / 2) - r.out0 - wr0;
+            if (mx_flags(r.meta, k) && (at < 0 || at % PO || at + mx_arm_arrays(mx_flags(r.meta, k)) * PO > wr1 - wr0)) return "lower: child arms off the level's array grid";
+        }
+        if (r.out0 != lv.nout - 256 || !n) continue;
+        // the window of the first array: the job's first block is entry HIST / 2 + out0 / 4 of it, and the job ends the window
+        const int head = (f0 ? r.o[0] : r.o[1]) + 256 - PO;
+        if (head != (f0 ? r.o[0] : r.o[1]) - 4 * (HIST / 2) - r.out0) return "lower: a tail job that does not end its arrays";
+        if (f0 && f1 && r.o[1] != r.o[0] + n0 * PO) return "lower: children of a pair not back to back";
+        if (head < 4 * lv.arr_off || (head - 4 * lv.arr_off) % PO) return "lower: child arms off the level's array grid";
+        const int k0 = (head - 4 * lv.arr_off) / PO, a0 = lv.arr_base + k0;
+        if (k0 + n > lv.arr_cnt || a0 > MX_SLOT_MASK) return "lower: child arms outside the level's arrays";
+        for (int k = k0; k < k0 + n; k++) {
+            const TkArray& a = arr[lv.arr_base + k];
+            if (a.off * 4 != head + (k - k0) * PO || a.len * 4 != PO || a.store != st.store_base + 16 * (lv.arr_base + k)) return "lower: history slots not in array order";
+            owner[(size_t)k]++;
+        }
+        r.meta |= MX_TAIL_BIT | (a0 << MX_SLOT_SHIFT) | (int)((uint32_t)n << MX_CNT_SHIFT);
+    }
+    for (int c : owner) if (c != 1) return "lower: an array without exactly one tail job";
     return {};
 }
 
@@ -70,6 +113,7 @@ std::string lower_root(const TkSubtree& st, TkLRoot& r)
 std::string lower_subtree(const BankPlan& plan, const TkSubtree& st, LoweredBank& out)
 {
     std::string err;
+    const TkArray* arr = plan.arrays.data() + st.array_base;
     for (int l = 0; l < st.n_levels; l++) {
         const TkLevel& lv = st.lv[l];
         const int PI = mx_pitch(l), PO = mx_pitch(l + 1);
@@ -82,6 +126,8 @@ std::string lower_subtree(const BankPlan& plan, const TkSubtree& st, LoweredBank
             if (!err.empty()) return err;
             order.emplace_back(mx_class(lowered[(size_t)q].meta), q);
         }
+        err = mark_tails(st, lv, arr, PO, lowered);
+        if (!err.empty()) return err;
         std::stable_sort(order.begin(), order.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
         for (int q = 0; q < lv.n_mjobs; q++) {
             out.jobs[(size_t)(lv.mjob_base + q)] = lowered[(size_t)order[(size_t)q].second];
@@ -108,7 +154,7 @@ std::string lower_bank(const BankPlan& plan, LoweredBank& out)
         const TkSubtree& st = plan.subtrees[s];
         if (!plan.mfma || !subtree_all_mx(st)) continue;
         TkLRoot root;
-        std::string err = lower_root(st, root);
+        std::string err = lower_root(st, plan.arrays.data() + st.array_base, root);
         if (err.empty()) err = lower_subtree(plan, st, out);
         if (err.empty()) out.roots[s] = root;
         if (err.empty()) sub_mx[s] = 1;

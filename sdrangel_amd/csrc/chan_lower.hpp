@@ -33,6 +33,14 @@ enum : int {
     MX_CLASSES = 3
 };
 constexpr int MX_LU_BIT = 1 << 16;
+// Array histories.  Every entry of a lean pass has >= 256 outputs per chunk, so the last 16 dwords of each arm array of a child
+// are written by ONE job, the entry's last of the chunk (the lanes with n16 >= 12), and that job's wave copies the histories of
+// the job's arrays: slot -> head, tail -> slot.  A job's children lie back to back (lower, then upper: alloc order), and so do
+// their slots: the job carries the first array's index in the subtree (slot = store_base + 16 * index) and the number of arrays.
+constexpr int MX_TAIL_BIT = 1 << 17;         // the job writes the tails of its children's arrays (and has at least one array)
+constexpr int MX_SLOT_SHIFT = 18, MX_SLOT_MASK = 1023;      // tail jobs: index of the first array of the first child with arms
+constexpr int MX_CNT_SHIFT = 28;             // tail jobs: arrays of both children together, 4 .. 12 (the top bits of the word)
+constexpr int mx_arm_arrays(int flags) { return flags == 7 ? 6 : flags ? 4 : 0; }
 
 struct TkLJob {
     int b;              // byte address of window entry 0 of the job's first block, odd arm feeding I; Q at +PI
@@ -43,7 +51,7 @@ struct TkLJob {
     int sink[2];        // heads of the children's sink lists (-1: none)
     int out0;           // first output of the job inside the chunk
     int meta;           // class | flags of child 0 << 4 | flags of child 1 << 8 (TkMOut::flags: 1 even, 2 plain odd, 4 alternating odd)
-                        //   | MX_LU_BIT for a lower/upper parent
+                        //   | MX_LU_BIT for a lower/upper parent | MX_TAIL_BIT, first array << MX_SLOT_SHIFT, arrays << MX_CNT_SHIFT for a tail job
 };
 static_assert(sizeof(TkLJob) == 32, "one s_load_dwordx8 per job");
 
@@ -60,6 +68,9 @@ constexpr int mx_root_arrays(int kinds) { return 2 + 2 * (kinds & 1) + (kinds & 
 
 inline int mx_class(int meta) { return meta & 15; }
 inline int mx_flags(int meta, int k) { return (meta >> (4 + 4 * k)) & 15; }
+inline bool mx_tail(int meta) { return (meta & MX_TAIL_BIT) != 0; }
+inline int mx_tail_first(int meta) { return (int)(((uint32_t)meta >> MX_SLOT_SHIFT) & MX_SLOT_MASK); }
+inline int mx_tail_count(int meta) { return (int)((uint32_t)meta >> MX_CNT_SHIFT); }
 
 struct LoweredBank {
     std::vector<TkLJob> jobs;        // parallel to BankPlan::mjobs: a level's jobs keep their index range (TkLevel::mjob_base, n_mjobs),

@@ -1,12 +1,15 @@
 // The bank's lean kernel: a pass whose every level runs on the matrix cores (the default plans, at most MX_MAX_LEVELS levels).
-// Same skeleton and the same arithmetic as tree_kernel<true> (tree_kernel.hpp: root fill, history walks, hb_mfma.hpp tiles,
+// Same skeleton and the same arithmetic as tree_kernel<true> (tree_kernel.hpp: root fill, array histories, hb_mfma.hpp tiles,
 // packed int16 epilogue), without the dot2 engine and its node / sink table copies, and with the jobs lowered by chan_lower.cpp:
 // one 8-dword descriptor per job, every LDS address a base plus a compile-time multiple of the level's pitch, so the lane adds its
 // share once per base and the ds_read / ds_write immediate offsets do the rest.  The level index is a template parameter (it
 // fixes the pitches), and so is the job's epilogue class: a wave's job pair runs a body with no branch it does not need.
-// What is the same for every lane of a chunk is decided on the scalar side or at compile time: the array lengths of the history
-// walks are constants of the level, the root arms hang off one lowered base (TkLRoot), and a job whose 256 outputs lie inside the
-// feed's range stores them without a per-lane compare.
+// What is the same for every lane of a chunk is decided on the scalar side or at compile time: the array lengths are constants of
+// the level, the root arms hang off one lowered base (TkLRoot), and a job whose 256 outputs lie inside the feed's range stores them
+// without a per-lane compare.
+// The 16-dword histories of the arrays (TkArray: slot -> head of the window, tail of the window -> slot, once per chunk) are not a
+// walk of the whole workgroup at the head of a level, as in tree_kernel.hpp: the wave that writes an array's tail copies both ways
+// itself, right behind its stores (hist below; chan_lower.cpp marks the jobs and names the slots).
 // Bit for bit what tree_kernel<true> computes: the biased odd arms and their zero history, the wrap-negated alternating copies,
 // the int16 stores, the sink ranges of ragged feeds are all the same code.
 #pragma once
@@ -20,17 +23,6 @@ namespace sdrx {
 __device__ __forceinline__ int mx_div_pow2_trunc(int v, int n)
 {
     return (v + ((v >> 31) & ((1 << n) - 1))) >> n;     // s.m_real /= (1 << n) (downchannelizer.cpp:80)
-}
-
-// q rows of the arrays `REL` levels below the root, in dwords.  The length is a constant of the level here (chan_lower.cpp refuses
-// a pass whose plan says otherwise), and the row index q is an array index inside one pass: below lds_dwords / LEN, a few hundred
-// at most with 160 KB of LDS, far inside the 24 bits __mul24 takes.  One full-rate 24-bit multiply (or a multiply-add with the
-// base) in place of the quarter-rate 32-bit multiplies that a length read from the level record costs.
-template<int REL> __device__ __forceinline__ int mx_rows(int q)
-{
-    constexpr int LEN = mx_pitch(REL) / 4;
-    static_assert(LEN > 0 && LEN < (1 << 16) && (160 * 1024 / 4) / LEN < (1 << 16), "24-bit multiply: length and row index both fit 16 bits");
-    return __mul24(q, LEN);
 }
 
 __global__ __launch_bounds__(TK_THREADS, 4)
@@ -107,9 +99,36 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
     auto psub = [](uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, (us2)(__builtin_bit_cast(us2, a) - __builtin_bit_cast(us2, b))); };
     auto pmul = [](uint32_t a, uint32_t m) { return __builtin_bit_cast(uint32_t, (us2)(__builtin_bit_cast(us2, a) * __builtin_bit_cast(us2, m))); };
 
+    // The histories of `n` arrays (4 .. 12) that lie back to back, P bytes each, the first at byte `head`, their slots from byte
+    // `slot` on, made by the one wave that has just stored their last 16 dwords: the slots (the previous chunk's tails) go in front
+    // of the windows, the new tails into the slots.  Lane = 16 * array + dword, four arrays per round, every further round an
+    // immediate offset.  The LDS serves one wave's operations in order: the tails read are the ones just stored, a slot is read
+    // before it is written, and neither needs a barrier.  Nobody else touches these heads before the barrier that ends the phase
+    // (their readers run one level down), nor these slots at all.
+    auto hist = [&](auto Pc, const int head, const int slot, const int n) {
+        constexpr int P = decltype(Pc)::value;
+        static_assert(9 * P < 65536, "ds_read / ds_write immediate offset");
+        int ln = threadIdx.x & 63;
+        asm volatile("" : "+v"(ln));                                   // opaque: no address of this leaves the branch it is in
+        const int g = ln >> 4;
+        char* w = ldsw + head + __mul24(g, P) + 4 * (ln & 15);
+        char* s = ldsw + slot + 4 * ln;
+        auto round = [&](auto Rc) {
+            constexpr int R = decltype(Rc)::value;
+            const uint32_t h = *reinterpret_cast<const uint32_t*>(s + 256 * R), t = *reinterpret_cast<const uint32_t*>(w + (4 * R + 1) * P - 64);
+            *reinterpret_cast<uint32_t*>(w + 4 * R * P) = h;
+            *reinterpret_cast<uint32_t*>(s + 256 * R) = t;
+        };
+        round(std::integral_constant<int, 0>{});
+        if (n > 4) {
+            if (g < n - 4) round(std::integral_constant<int, 1>{});
+            if (n > 8 && g < n - 8) round(std::integral_constant<int, 2>{});
+        }
+    };
+
     for (long chunk = first - st.warm; chunk <= last; ++chunk) {
-        // the thread index, opaque inside the chunk loop: the compiler would otherwise hoist every per-lane address of the root fill,
-        // the history walks and the boundary fetch out of the loop, and spill them
+        // the thread index, opaque inside the chunk loop: the compiler would otherwise hoist every per-lane address of the root fill
+        // and the boundary fetch out of the loop, and spill them
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         // ---- stream samples -> root arms (TkLRoot: E_I E_Q [O_I O_Q] [A_I A_Q], one pitch apart): one address per lane and
@@ -140,19 +159,20 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
             else if (root_kinds == MX_ROOT_O) fill(std::integral_constant<int, MX_ROOT_O>{});
             else fill(std::integral_constant<int, MX_ROOT_A>{});
         }
+        // the root arms' histories: the last wave's last stores above are the 16 tail dwords of every arm
+        static_assert(NT >= 64 && (LPT - 1) * NT + NT - 16 == C / 4 - 16, "the tail of a root arm is stored by the last 16 lanes of the fill");
         {
-            const uint32_t* slots = lds + store_base;
-            uint32_t* win = reinterpret_cast<uint32_t*>(ldsw + root_base);
-            const int root_cnt16 = 16 * mx_root_arrays(root_kinds);
-            for (int i = tid; i < root_cnt16; i += NT)
-                win[mx_rows<0>(i >> 4) + (i & 15)] = slots[i];
+            // opaque: hoisted out of the chunk loop, the wave test and the array count become lane masks held across it (spills)
+            int w = wv, kinds = root_kinds;
+            asm volatile("" : "+s"(w), "+s"(kinds));
+            if (w == NT / 64 - 1) hist(std::integral_constant<int, mx_pitch(0)>{}, root_base, 4 * store_base, mx_root_arrays(kinds));
         }
         if (chunk < last) fetch(chunk + 1, tid);
         __syncthreads();
 
         const bool live = chunk >= first;
         // the level records, opaque to the compiler inside the chunk loop: with the level index a template parameter it would hoist
-        // all four records and the history walks' per-lane addresses out of the loop, and hold them across it (spills)
+        // all four records out of the loop, and hold them across it (spills)
         int lv0 = 0;
         asm volatile("" : "+s"(lv0), "+s"(n_levels));
         // ---- one level, L = its index in the pass (compile time: the pitches of what it reads and writes)
@@ -160,18 +180,8 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
             constexpr int L = decltype(Lc)::value;
             constexpr int PI = mx_pitch(L), PO = mx_pitch(L + 1);
             const s16i rec = *(const s16i __attribute__((address_space(4)))*)reinterpret_cast<const int*>(&st.lv[L + lv0]);
-            const int nout = rec[3], arr_base = rec[4], arr_cnt = rec[5], mjob_base = rec[9], n_mjobs = rec[10];
+            const int nout = rec[3], mjob_base = rec[9], n_mjobs = rec[10];
             const uint32_t xm = (uint32_t)rec[11];
-            const int prev_off = rec[12], prev_arr_cnt = rec[13], arr_off = rec[14];
-            {   // history walk (tree_kernel.hpp), its two ranges as two loops: restore the history in front of the arrays this level
-                // produces, save the tails of the arrays it reads.  The lengths are PO / 4 and PI / 4 (mx_rows).
-                const int n_restore = arr_cnt * 16, n_save = prev_arr_cnt * 16;
-                const int slot0 = store_base + 16 * arr_base;
-                for (int i = tid; i < n_restore; i += NT)
-                    lds[arr_off + mx_rows<L + 1>(i >> 4) + (i & 15)] = lds[slot0 + i];
-                for (int k = tid; k < n_save; k += NT)
-                    lds[slot0 - n_save + k] = lds[prev_off + PI / 4 - 16 + mx_rows<L>(k >> 4) + (k & 15)];
-            }
             struct JobIn { v4i bI0, bI1, bQ0, bQ1; uint2 cI01, cQ01; uint32_t cI2, cQ2; };
             // the job's operands: two bases, everything else immediate offsets (the centre taps of a lower/upper parent come from
             // the OTHER component's even arm: E[1] feeds I)
@@ -307,6 +317,13 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
                 const v4i SI0 = taps.tile(r0.bI0, r0.bI1, bias), SQ0 = taps.tile(r0.bQ0, r0.bQ1, bias);
                 finish(Cc, r0, SI0, SQ0, d0);
             };
+            // a tail job (MX_TAIL_BIT) has just completed its children's arrays for this chunk: their histories, by this wave
+            auto tail = [&](const s8i d) {
+                const uint32_t meta = (uint32_t)d[7];
+                if (meta & MX_TAIL_BIT)
+                    hist(std::integral_constant<int, PO>{}, ((meta & 0xf0) ? d[2] : d[3]) + 256 - PO, 4 * store_base + 64 * (int)((meta >> MX_SLOT_SHIFT) & MX_SLOT_MASK),
+                         (int)(meta >> MX_CNT_SHIFT));
+            };
             typedef std::integral_constant<int, MX_FAST> KF;
             typedef std::integral_constant<int, MX_ARMS> KA;
             typedef std::integral_constant<int, MX_SINK> KS;
@@ -322,6 +339,7 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
                         if (c0 == MX_FAST) pair(KF{}, d0, d1);
                         else if (c0 == MX_ARMS) pair(KA{}, d0, d1);
                         else pair(KS{}, d0, d1);
+                        tail(d0); tail(d1);
                         tt += 2;
                         continue;
                     }
@@ -329,6 +347,7 @@ void tree_mx_kernel(const TkSubtree* __restrict__ subtrees, const TkArray* __res
                 if (c0 == MX_FAST) single(KF{}, d0);
                 else if (c0 == MX_ARMS) single(KA{}, d0);
                 else single(KS{}, d0);
+                tail(d0);
                 tt += 1;
             }
             __syncthreads();
