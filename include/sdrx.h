@@ -875,8 +875,12 @@ int sdrx_ssb_last_launch(const sdrx_ssb_t* h, char* kernel_name, int name_cap,
  *      10 FormatAMBPFMono    int16           open: (qint16)(Real)(m_bandpass.filter(sqrt(inMagSq)) / 301.0 * agcFactor * gain);  closed: 0
  * The payload element is 4, 8, 4, 2, 2, 2, 2 bytes for formats 0, 1, 2, 3, 8, 9, 10 (sdrx_udpsrc_sample_bytes).
  * Formats 0, 1, 8, 9, 10, the spectrum Samples, m_inMagsq and the squelch state are bit-identical to the strict-IEEE scalar
- * reference build.  Formats 2 and 3 inherit the back-end's std::arg ruling (discri = 2 above): a double atan2 rounded once,
- * <= 3 ulp from glibc's atan2f, so with |d| < 8 a payload int16 equals the reference's or differs by 1 modulo 2^16.
+ * reference build.  Formats 2 and 3 multiply std::arg = atan2f by fm_scaling * gain * 32768 / pi, up to several hundred times
+ * 32768 at a small fm_deviation, where one ulp of the angle is more than a unit of the int16: an ulp bound against the host's libm
+ * (the back-end's discri = 2 ruling) is no bound on the payload.  The device therefore evaluates the fdlibm float routines that
+ * glibc's atan2f was up to 2.40, operation for operation: against a reference built on such a libm formats 2 and 3 are
+ * bit-identical too; against a libm with another atan2f the angle is within 2 ulp, i.e. with |d| < 8 a payload int16 equals the
+ * reference's or differs by 1 modulo 2^16.
  * Any feed length is valid (0 included); NCO phase, resampler window and distance, both moving averages, the squelch
  * counters, m_m1Sample, the Bandpass ring and the running sample count carry across feeds.
  * A fresh handle is the constructed object after applySettings(settings, true), applyChannelSettings(in_rate, offset, true)

@@ -4,9 +4,9 @@
 //     inMagSq = |ci|^2;  m_inMovingAverage.feed(inMagSq / 2^30);  m_inMagsq = average();  spectrum Sample(ci)
 //     agcFactor = m_agc.feedAndGetValue(ci) (AM formats with m_agc on: every sample, open or not), else 1.0
 //     calculateSquelch(m_inMagsq);  the format's payload sample, 0 while the squelch is closed
-// Payloads are bit-identical to the strict-IEEE scalar reference build for every format but NFM / NFMMono, whose std::arg is a
-// double atan2 rounded once (as the back-end's discri = 2): every float and double expression keeps the reference's operand
-// order and the file is compiled with -ffp-contract=off.  udpsrc_scan.hpp has the cut of the recurrences; DESIGN.md 4.14 the
+// Payloads are bit-identical to the strict-IEEE scalar reference build; for NFM / NFMMono that holds where the reference's libm
+// has the fdlibm atan2f that udp_atan2f restates (udpsrc_scan.hpp).  Every float and double expression keeps the reference's
+// operand order and the file is compiled with -ffp-contract=off.  udpsrc_scan.hpp has the cut of the recurrences; DESIGN.md 4.14 the
 // kernel table.  The only loop that is serial along time is psum_rows' (demod_psum.hpp).  A channel's format is uniform over a
 // block (blockIdx.y is the channel), so the format branches diverge per block, not per lane.
 #pragma once
@@ -380,7 +380,7 @@ void udp_out_kernel(const UdpChan* __restrict__ ch, const UdpBufs* __restrict__ 
         if (a >= 0) {
             float2 m1; if (a == 0) { m1.x = s.m1r; m1.y = s.m1i; } else m1 = reinterpret_cast<const float2*>(b.x)[a - 1];
             const float dr = m1.x * v.x - (-m1.y) * v.y, di = m1.x * v.y + (-m1.y) * v.x;    // conj(m_m1Sample) * ci
-            const float ang = (float)atan2((double)di, (double)dr);                          // std::arg: as the back-end's discri = 2
+            const float ang = udp_atan2f(di, dr);                                            // std::arg = atan2f, the host libm's bits (udpsrc_scan.hpp)
             d = (float)(((double)ang / 3.14159265358979323846) * (double)s.fm_scaling) * gain;
         }
         const int q = udp_q16d((double)d * 32768.0);

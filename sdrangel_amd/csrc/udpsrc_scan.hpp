@@ -117,6 +117,67 @@ AM_HD int udp_q16d(double v)
     return (int)(short)i;
 }
 
+// ---- std::arg(Complex) = atan2f for formats 2 and 3.  The payload is (int16)(arg / pi * fm_scaling * gain * 32768): at
+// fm_scaling * gain = 720 one ulp of the angle near pi is two units of the int16, so "within a few ulp of the host's libm" is
+// not enough there.  This is the evaluation of the fdlibm float routines (e_atan2f.c, s_atanf.c: argument reduction to four
+// intervals, an odd polynomial of degree 23 in two interleaved halves, hi + lo constants), which glibc's atan2f was up to 2.40,
+// operation for operation in float; with -ffp-contract=off and IEEE division it returns that libm's bits on the host and on the
+// device (tests/udpsrc_scan_check.cpp compares it with the host's atan2f).  NaN and infinite arguments follow the same routine.
+AM_HD int udp_f2i(float v) { int i; __builtin_memcpy(&i, &v, 4); return i; }
+AM_HD float udp_atanf(float x)
+{
+    const float hi[4] = { 4.6364760399e-01f, 7.8539812565e-01f, 9.8279368877e-01f, 1.5707962513e+00f };     // atan(0.5), atan(1), atan(1.5), atan(inf)
+    const float lo[4] = { 5.0121582440e-09f, 3.7748947079e-08f, 3.4473217170e-08f, 7.5497894159e-08f };
+    const float t0 = 3.3333334327e-01f, t1 = -2.0000000298e-01f, t2 = 1.4285714924e-01f, t3 = -1.1111110449e-01f, t4 = 9.0908870101e-02f,
+                t5 = -7.6918758452e-02f, t6 = 6.6610731184e-02f, t7 = -5.8335702866e-02f, t8 = 4.9768779427e-02f, t9 = -3.6531571299e-02f,
+                t10 = 1.6285819933e-02f;
+    const int hx = udp_f2i(x), ix = hx & 0x7fffffff;
+    int id = -1;
+    if (ix >= 0x4c000000) {                                 // |x| >= 2^25
+        if (ix > 0x7f800000) return x + x;
+        return hx > 0 ? hi[3] + lo[3] : -hi[3] - lo[3];
+    }
+    if (ix < 0x3ee00000) {                                  // |x| < 0.4375
+        if (ix < 0x31000000) return x;                      // |x| < 2^-29
+    } else {
+        x = __builtin_fabsf(x);
+        if (ix < 0x3f980000) {                              // |x| < 1.1875
+            if (ix < 0x3f300000) { id = 0; x = (2.0f * x - 1.0f) / (2.0f + x); }
+            else { id = 1; x = (x - 1.0f) / (x + 1.0f); }
+        } else {
+            if (ix < 0x401c0000) { id = 2; x = (x - 1.5f) / (1.0f + 1.5f * x); }     // |x| < 2.4375
+            else { id = 3; x = -1.0f / x; }
+        }
+    }
+    const float z = x * x, w = z * z;
+    const float s1 = z * (t0 + w * (t2 + w * (t4 + w * (t6 + w * (t8 + w * t10)))));
+    const float s2 = w * (t1 + w * (t3 + w * (t5 + w * (t7 + w * t9))));
+    if (id < 0) return x - x * (s1 + s2);
+    const float r = hi[id] - ((x * (s1 + s2) - lo[id]) - x);
+    return hx < 0 ? -r : r;
+}
+AM_HD float udp_atan2f(float y, float x)
+{
+    const float tiny = 1.0e-30f, pi_o_4 = 7.8539818525e-01f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f, pi_lo = -8.7422776573e-08f;
+    const int hx = udp_f2i(x), ix = hx & 0x7fffffff, hy = udp_f2i(y), iy = hy & 0x7fffffff;
+    if (ix > 0x7f800000 || iy > 0x7f800000) return x + y;   // NaN
+    if (hx == 0x3f800000) return udp_atanf(y);              // x = 1
+    const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);      // 2 * sign(x) + sign(y)
+    if (iy == 0) return m < 2 ? y : (m == 2 ? pi + tiny : -pi - tiny);
+    if (ix == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    if (ix == 0x7f800000) {
+        if (iy == 0x7f800000) return m == 0 ? pi_o_4 + tiny : (m == 1 ? -pi_o_4 - tiny : (m == 2 ? 3.0f * pi_o_4 + tiny : -3.0f * pi_o_4 - tiny));
+        return m == 0 ? 0.0f : (m == 1 ? -0.0f : (m == 2 ? pi + tiny : -pi - tiny));
+    }
+    if (iy == 0x7f800000) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int k = (iy - ix) >> 23;
+    float z;
+    if (k > 60) z = pi_o_2 + 0.5f * pi_lo;                  // |y / x| > 2^60
+    else if (hx < 0 && k < -60) z = 0.0f;                   // |y| / x < -2^60
+    else z = udp_atanf(__builtin_fabsf(y / x));
+    return m == 0 ? z : (m == 1 ? -z : (m == 2 ? pi - (z - pi_lo) : (z - pi_lo) - pi));
+}
+
 #if defined(__HIPCC__)
 __device__ __forceinline__ UdpSq udp_sq_shfl_up(UdpSq m, int o)
 {

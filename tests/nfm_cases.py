@@ -212,3 +212,40 @@ def run_oracle(L: C.CDLL, case: dict, splits=None) -> dict:
     res = {"feeds": feeds, "magsq": m, "sum": s, "peak": p, "count": n, "open": o.squelch_open(), "state": o.squelch_count(), "probe": o.probe()}
     o.close()
     return res
+
+
+# ---------------------------------------------------------------- random cases
+def random_case(rng, i) -> dict:
+    """one random configuration, signal and split list; the order of the rng calls is part of the case set"""
+    rates = [(60000, 48000), (62500, 48000), (48000, 48000), (96000, 44100), (120000, 48000), (75000, 48000), (48000, 8000), (50000, 44100),
+             (48000, 32000), (16000, 1000)]
+    in_rate, audio = rates[int(rng.integers(len(rates)))]
+    kind = str(rng.choice(["nfm", "burst", "noise_full", "zero", "nfm", "gap"]))
+    f0 = float(rng.integers(-in_rate // 8, in_rate // 8))
+    sig = {"kind": "nfm" if kind in ("burst", "gap") else kind, "f0": f0, "dev": float(rng.choice([500.0, 2000.0, 4000.0])), "fa": float(rng.integers(100, 3000)),
+           "amp": float(rng.integers(50, 20000)), "noise": float(rng.integers(0, 50))}
+    if kind == "burst":
+        sig["runs"] = [int(v) for v in rng.integers(1, in_rate // 4, size=8)]
+        sig["amps"] = [float(rng.integers(3000, 16000)), float(rng.integers(1, 200))]
+    n = int(rng.integers(2000, 60000))
+    if kind == "gap":
+        sig["noise"] = 0.0
+        sig["zero_at"] = (int(rng.integers(0, n)), int(rng.integers(1, 400)))
+    cfg = (in_rate, -int(f0), audio, float(rng.choice([5000.0, 8330.0, 12500.0, 25000.0])), float(rng.choice([3000.0, 2400.0, 301.0, 6000.0])),
+           int(rng.choice([2000, 5000, 10, 1234])), float(rng.choice([0.5, 2.0, 10.0])), float(rng.choice([-1000.0, -600.0, -400.0, -255.5, -100.0])),
+           int(rng.choice([0, 1, 1, 2, 5, 5, 17, 60])), int(rng.random() < 0.1))
+    splits, left = [], n
+    while left > 0:
+        m = min(left, int(rng.choice([0, 1, 2, 32, 33, int(rng.integers(1, 3000)), int(rng.integers(1, 30000))])))
+        splits.append(m); left -= m
+    return {"name": f"random{i}", "cfg": cfg, "sig": sig, "n": n, "seed": 1000 + i, "splits": splits}
+
+
+#: the seed of random_cases(): the cases the `ref` test of tests/test_nfm_oracle.py proves against the reference
+RANDOM_SEED = 20261017
+
+
+def random_cases(count: int = 100) -> list[dict]:
+    """the first `count` random cases, drawn in order from one generator"""
+    rng = np.random.default_rng(RANDOM_SEED)
+    return [random_case(rng, i) for i in range(count)]

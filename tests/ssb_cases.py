@@ -231,3 +231,46 @@ def run_oracle(L: C.CDLL, case: dict, splits=None) -> dict:
            "active": o.audio_active(), "state": o.state(), "probe": o.probe(), "design": o.design()}
     o.close()
     return res
+
+
+# ---------------------------------------------------------------- random cases
+def random_case(rng, i) -> dict:
+    """one random configuration, signal and split list; the order of the rng calls is part of the case set"""
+    rates = [(60000, 48000), (62500, 48000), (48000, 48000), (96000, 44100), (120000, 48000), (48000, 8000), (50000, 44100), (48000, 32000),
+             (16000, 1000), (192000, 192000)]
+    in_rate, audio = rates[int(rng.integers(len(rates)))]
+    kind = str(rng.choice(["tone", "burst", "noise_full", "zero", "tone", "burst"]))
+    band = float(rng.choice([3000.0, 2400.0, 1500.0, 50.0, 5000.0])) * (audio / 48000.0 if audio < 16000 else 1.0)
+    lsb = rng.random() < 0.3
+    f0 = float(rng.integers(-in_rate // 8, in_rate // 8))
+    sig = {"kind": "tone" if kind == "burst" else kind, "f0": f0 + (-1.0 if lsb else 1.0) * band / 3, "amp": float(rng.integers(50, 20000)),
+           "noise": float(rng.integers(0, 50))}
+    time_log2 = int(rng.choice([0, 1, 3, 5, 7, 7, 9]))
+    hn = (audio // 1000) << time_log2
+    if hn < 2:
+        time_log2 = 1
+    if kind == "burst":
+        hn = (audio // 1000) << time_log2
+        sig["runs"] = [int(v) for v in rng.integers(1, max(2, min(3 * hn * in_rate // audio, in_rate // 3)), size=8)]
+        sig["amps"] = [float(rng.integers(3000, 16000)), float(rng.integers(1, 200))]
+    n = int(rng.integers(2000, 60000))
+    cfg = _cfg(in_rate, audio, nco_freq=-int(f0), rf_bandwidth=-band if lsb else band, low_cutoff=(-1.0 if lsb else 1.0) * float(rng.choice([300.0, 0.0, 100.0])),
+                  volume=float(rng.choice([0.5, 3.0, 10.0])), span_log2=int(rng.integers(1, 9)), audio_binaural=int(rng.random() < 0.3),
+                  audio_flip=int(rng.random() < 0.5), dsb=int(rng.random() < 0.2), audio_mute=int(rng.random() < 0.1), agc=int(rng.random() < 0.85),
+                  agc_clamping=int(rng.random() < 0.4), agc_time_log2=time_log2, agc_power_threshold=int(rng.choice([-40, -40, -20, -60, -100, 100, 0])),
+                  agc_threshold_gate=int(rng.choice([0, 1, 4, 4, 20])))
+    splits, left = [], n
+    while left > 0:
+        m = min(left, int(rng.choice([0, 1, 2, 511, 513, int(rng.integers(1, 3000)), int(rng.integers(1, 30000))])))
+        splits.append(m); left -= m
+    return {"name": f"random{i}", "cfg": cfg, "sig": sig, "n": n, "seed": 1000 + i, "splits": splits, "reach": []}
+
+
+#: the seed of random_cases(): the cases the `ref` test of tests/test_ssb_oracle.py proves against the reference
+RANDOM_SEED = 20261017
+
+
+def random_cases(count: int = 100) -> list[dict]:
+    """the first `count` random cases, drawn in order from one generator"""
+    rng = np.random.default_rng(RANDOM_SEED)
+    return [random_case(rng, i) for i in range(count)]

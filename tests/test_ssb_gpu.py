@@ -9,6 +9,7 @@ import sdrangel_amd as sa
 from tests import oracle_py as orc
 from tests import ssb_cases as sc
 from tests import synth
+from tests.demod_mixed import feed_rounds
 
 pytestmark = pytest.mark.gpu
 BY = {c["name"]: c for c in sc.CASES}
@@ -104,25 +105,18 @@ def test_random_splits_equal_one_feed(oracle, name):
     check_levels(bank, 0, want, name)
 
 
+def read_both(bank, ch):
+    return bank.read(ch), bank.read_spectrum(ch)
+
+
 def _mixed(names, wants):
     cases = [BY[n] for n in names]
     bank = sa.SsbDemodBank([gcfg(c["cfg"]) for c in cases])
-    cuts = [sc.cut(sc.inputs(c), c["splits"]) for c in cases]
-    rounds = max(len(x) for x in cuts)
-    empty = np.zeros(0, np.int16)
-    audio, spec = [[] for _ in cases], [[] for _ in cases]
-    for r in range(rounds):
-        bank.feed([x[r] if r < len(x) else empty for x in cuts])
-        for c, x in enumerate(cuts):
-            a, s = bank.read(c), bank.read_spectrum(c)
-            if r < len(x):
-                audio[c].append(a); spec[c].append(s)
-            else:
-                assert a.shape[0] == 0 and s.shape[0] == 0, (c, r)      # an empty feed: nothing out, state untouched
+    got = feed_rounds(bank, [sc.cut(sc.inputs(c), c["splits"]) for c in cases], read_both)
     for c, case in enumerate(cases):
         want = wants[case["name"]]
-        assert_feeds_equal(audio[c], want["audio"], case["name"] + " audio")
-        assert_feeds_equal(spec[c], want["spec"], case["name"] + " spectrum")
+        assert_feeds_equal([g[0] for g in got[c]], want["audio"], case["name"] + " audio")
+        assert_feeds_equal([g[1] for g in got[c]], want["spec"], case["name"] + " spectrum")
         check_levels(bank, c, want, case["name"])
 
 

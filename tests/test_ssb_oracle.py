@@ -179,35 +179,16 @@ def test_mono_audio_equals_the_audio_tail_restatement(oracle, runs):
     assert checked >= 12
 
 
-def _random_case(rng, i):
-    rates = [(60000, 48000), (62500, 48000), (48000, 48000), (96000, 44100), (120000, 48000), (48000, 8000), (50000, 44100), (48000, 32000),
-             (16000, 1000), (192000, 192000)]
-    in_rate, audio = rates[int(rng.integers(len(rates)))]
-    kind = str(rng.choice(["tone", "burst", "noise_full", "zero", "tone", "burst"]))
-    band = float(rng.choice([3000.0, 2400.0, 1500.0, 50.0, 5000.0])) * (audio / 48000.0 if audio < 16000 else 1.0)
-    lsb = rng.random() < 0.3
-    f0 = float(rng.integers(-in_rate // 8, in_rate // 8))
-    sig = {"kind": "tone" if kind == "burst" else kind, "f0": f0 + (-1.0 if lsb else 1.0) * band / 3, "amp": float(rng.integers(50, 20000)),
-           "noise": float(rng.integers(0, 50))}
-    time_log2 = int(rng.choice([0, 1, 3, 5, 7, 7, 9]))
-    hn = (audio // 1000) << time_log2
-    if hn < 2:
-        time_log2 = 1
-    if kind == "burst":
-        hn = (audio // 1000) << time_log2
-        sig["runs"] = [int(v) for v in rng.integers(1, max(2, min(3 * hn * in_rate // audio, in_rate // 3)), size=8)]
-        sig["amps"] = [float(rng.integers(3000, 16000)), float(rng.integers(1, 200))]
-    n = int(rng.integers(2000, 60000))
-    cfg = sc._cfg(in_rate, audio, nco_freq=-int(f0), rf_bandwidth=-band if lsb else band, low_cutoff=(-1.0 if lsb else 1.0) * float(rng.choice([300.0, 0.0, 100.0])),
-                  volume=float(rng.choice([0.5, 3.0, 10.0])), span_log2=int(rng.integers(1, 9)), audio_binaural=int(rng.random() < 0.3),
-                  audio_flip=int(rng.random() < 0.5), dsb=int(rng.random() < 0.2), audio_mute=int(rng.random() < 0.1), agc=int(rng.random() < 0.85),
-                  agc_clamping=int(rng.random() < 0.4), agc_time_log2=time_log2, agc_power_threshold=int(rng.choice([-40, -40, -20, -60, -100, 100, 0])),
-                  agc_threshold_gate=int(rng.choice([0, 1, 4, 4, 20])))
-    splits, left = [], n
-    while left > 0:
-        m = min(left, int(rng.choice([0, 1, 2, 511, 513, int(rng.integers(1, 3000)), int(rng.integers(1, 30000))])))
-        splits.append(m); left -= m
-    return {"name": f"random{i}", "cfg": cfg, "sig": sig, "n": n, "seed": 1000 + i, "splits": splits, "reach": []}
+def test_random_cases_cover_the_branches(oracle):
+    """the 100 random cases (the GPU banks of tests/test_demod_random_gpu.py run them too) through the oracle: floors on how
+    many carry audio and how many send the AGC from up to down.  With the generator and seed of tests/ssb_cases.py 46 are
+    audible, 40 go up_to_down, 17 down_to_up, 21 clamp, 35 fill the gate; none wraps the delay line, so `dl_wraps` stays with
+    the named case long_history"""
+    runs = [sc.run_oracle(oracle, case) for case in sc.random_cases()]
+    loud = sum(bool(_cat(r["audio"]).any()) for r in runs)
+    moved = sum(r["probe"]["up_to_down"] > 0 for r in runs)
+    print("audible", loud, {k: sum(r["probe"][k] > 0 for r in runs) for k in ("up_to_down", "down_to_up", "clamped", "gate_full", "dl_wraps")})
+    assert loud >= 40 and moved >= 10, (loud, moved)
 
 
 @pytest.mark.ref
@@ -219,10 +200,9 @@ def test_oracle_vs_rebuilt_recorder_random(oracle):
     if not mg.available(REF):
         pytest.skip("Qt headers not available")
     exe = mg.build_recorder(REF)
-    rng = np.random.default_rng(20261017)
-    loud, moved = 0, 0
-    for i in range(100):
-        case = _random_case(rng, i)
+    cases = sc.random_cases()
+    assert len(cases) == 100
+    for case in cases:
         want = mg.record(exe, case["cfg"], sc.inputs(case), case["splits"])
         got = sc.run_oracle(oracle, case)
         for key in ("audio", "spec"):
@@ -233,6 +213,3 @@ def test_oracle_vs_rebuilt_recorder_random(oracle):
                (want["magsq"], want["sum"], want["peak"], want["count"], want["active"], want["usc"]), case
         a, w = _agc_state(got), want["agc"]
         assert a[1:] == w[1:] and (a[0] == w[0] or (np.isnan(a[0]) and np.isnan(w[0]))), case
-        loud += bool(_cat(got["audio"]).any())
-        moved += got["probe"]["up_to_down"] > 0
-    assert loud >= 40 and moved >= 10, (loud, moved)

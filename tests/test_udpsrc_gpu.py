@@ -1,9 +1,10 @@
 """GPU: the UDPSrc bank (sdrx_udpsrc_*) against the oracle (tests/udpsrc_oracle.c): every payload sample, spectrum Sample,
 m_inMagsq, the squelch flag and counters and the running total, bit for bit for formats 0, 1, 8, 9 and 10.  Formats 2 and 3
-inherit the back-end's std::arg ruling (a double atan2 rounded once, <= 3 ulp from glibc's atan2f, include/sdrx.h at discri = 2):
-with |d * gain| < 8 the float's ulp is at most 2^-21, four ulp times 32768 is 2^-4 of an LSB, so each int16 equals the oracle's
-or differs by exactly 1 modulo 2^16, in at most 1/16 of the samples by expectation; the tests allow no difference above 1, at
-most 1/4 of a case's open samples differing, and demand exact zeros on closed samples.  The named cases of
+scale std::arg = atan2f, which the device evaluates as the fdlibm float routines do (udp_atan2f, include/sdrx.h): the same bits
+as the oracle's where the host's libm is a glibc up to 2.40, within 2 ulp of any other.  The rule below dates from a device
+atan2 that was a few ulp from the host's -- with |d * gain| < 8 the float's ulp is at most 2^-21, four ulp times 32768 is 2^-4
+of an LSB, so each int16 equals the oracle's or differs by exactly 1 modulo 2^16 -- and stays as the bound: the tests allow no
+difference above 1, at most 1/4 of a case's open samples differing, and demand exact zeros on closed samples.  The named cases of
 tests/udpsrc_cases.py (the AM formats with MagAGC off and on, the power crossing its threshold both ways), random splits, banks of
 1, 3 and 17 mixed channels, reset, the device hand-over from the channelizer
 bank, the design products, the accessors, and -- independent of that oracle -- format 0 against sdrx_backend_*."""
@@ -14,6 +15,7 @@ import sdrangel_amd as sa
 from tests import oracle_py as orc
 from tests import synth
 from tests import udpsrc_cases as uc
+from tests.demod_mixed import feed_rounds
 
 pytestmark = pytest.mark.gpu
 BY = {c["name"]: c for c in uc.CASES}
@@ -124,6 +126,10 @@ def test_random_splits_equal_one_feed(oracle, name):
         check_state(bank, 0, want, f"{name} trial {trial}")
 
 
+def read_both(bank, ch):
+    return bank.read(ch), bank.read_spectrum(ch)
+
+
 #: seventeen channels: all seven formats, every gate setting, four rates, the three AM formats with the AGC off and on
 MIX17 = ["iq16_burst_gate5", "iq24_burst", "nfm_burst", "nfmmono_burst_gate5", "am_burst", "amnodc_burst", "ambpf_burst", "iq16_burst_gate0",
          "iq16_release_boundary", "amnodc_small_feeds", "ambpf_small_feeds", "nfm_float_rate", "am_nondyadic_62500", "ambpf_r96k_to_44k1",
@@ -138,20 +144,10 @@ def test_mixed_channels_in_one_handle(wants, names):
         assert {(c["cfg"][3], c["cfg"][10]) for c in cases} >= {(8, 0), (8, 1), (9, 0), (9, 1), (10, 0), (10, 1)}
     # formats 0 .. 3 never feed the AGC: the flag is accepted and changes nothing there
     bank = sa.UdpSrcBank([gcfg(c["cfg"], agc=1 if c["cfg"][3] < 8 and i % 2 == 0 else None) for i, c in enumerate(cases)])
-    cuts = [uc.cut(uc.inputs(c), c["splits"]) for c in cases]
-    rounds = max(len(x) for x in cuts)
-    empty = np.zeros(0, np.int16)
-    got = [([], []) for _ in cases]
-    for r in range(rounds):
-        bank.feed([x[r] if r < len(x) else empty for x in cuts])
-        for c, x in enumerate(cuts):
-            if r < len(x):
-                got[c][0].append(bank.read(c)); got[c][1].append(bank.read_spectrum(c))
-            else:
-                assert bank.last_dev(c)[1] == 0, (c, r)     # an empty feed: no samples, state untouched
+    got = feed_rounds(bank, [uc.cut(uc.inputs(c), c["splits"]) for c in cases], read_both, idle=lambda bank, c: bank.last_dev(c)[1])
     for c, case in enumerate(cases):
         want = wants[case["name"]]
-        assert_streams(case, got[c][0], got[c][1], want, case["name"])
+        assert_streams(case, [g[0] for g in got[c]], [g[1] for g in got[c]], want, case["name"])
         check_state(bank, c, want, case["name"])
 
 

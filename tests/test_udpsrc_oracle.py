@@ -168,30 +168,17 @@ def test_discriminator_runs_on_open_samples_only(oracle):
     assert np.array_equal(gated[inside], free[inside])
 
 
-def _random_case(rng, i):
-    rates = [(48000, 8000.0), (48000, 48000.0), (62500, 48000.0), (96000, 44100.0), (48000, 11025.5), (60000, 48000.0), (50000, 44100.0),
-             (48000, 32000.0), (16000, 1000.0), (48000, 7999.25)]
-    in_rate, rate = rates[int(rng.integers(len(rates)))]
-    fmt = int(rng.choice(uc.FORMATS))
-    kind = str(rng.choice(["nfm", "am", "burst", "noise_full", "zero", "burst"]))
-    f0 = float(rng.integers(-in_rate // 8, in_rate // 8))
-    base = "am" if (kind in ("am", "burst") and fmt >= 8) else ("nfm" if kind in ("nfm", "am", "burst") else kind)
-    sig = {"kind": base, "f0": f0, "dev": float(rng.choice([500.0, 2000.0])), "fa": float(rng.integers(100, 3000)),
-           "amp": float(rng.integers(2, 20000)), "noise": float(rng.integers(0, 50))}
-    if kind == "burst":
-        sig["runs"] = [int(v) for v in rng.integers(1, in_rate // 8, size=8)]
-        sig["amps"] = [float(rng.integers(300, 16000)), float(rng.integers(1, 30))]
-    n = int(rng.integers(500, 20000))
-    cfg = (in_rate, -int(f0), rate, fmt, float(rng.choice([1300.0, 5000.0, 12500.0])), int(rng.choice([2500, 5000, 100])),
-           float(rng.choice([0.5, 1.0, 7.0, -3.0])), int(rng.choice([-100, -60, -40, -20])), int(rng.choice([0, 0, 1, 2, 5, 17])), int(rng.random() < 0.8), int(rng.random() < 0.5))
-    if cfg[10] and fmt >= 8 and kind == "burst":             # the raw power on both sides of the AGC threshold (amplitude 290 at -20 dB)
-        cfg = cfg[:7] + (int(rng.choice([-20, -10])),) + cfg[8:]
-        sig["amps"] = [float(rng.integers(3000, 16000)), float(rng.integers(1, 100))]
-    splits, left = [], n
-    while left > 0:
-        m = min(left, int(rng.choice([0, 1, 2, 32, 33, int(rng.integers(1, 300)), int(rng.integers(1, 8000))])))
-        splits.append(m); left -= m
-    return {"name": f"random{i}", "cfg": cfg, "sig": sig, "n": n, "seed": 2000 + i, "splits": splits}
+def test_random_cases_cover_the_branches(oracle):
+    """the 100 random cases (the GPU banks of tests/test_demod_random_gpu.py run them too) through the oracle: floors on how
+    many open the squelch and how many flip the AGC's mode, and every format.  With the generator and seed of
+    tests/udpsrc_cases.py 77 open, 10 change the AGC mode, 5 use up the release, 44 wrap a conversion"""
+    cases = uc.random_cases()
+    probes = [uc.run_oracle(oracle, case)["probe"] for case in cases]
+    opened = sum(p["open"] > 0 for p in probes)
+    agc_moved = sum(p["agc_mode_changes"] > 0 for p in probes)
+    formats = {case["cfg"][3] for case in cases}
+    print("open", opened, "agc_mode_changes", agc_moved, {k: sum(p[k] > 0 for p in probes) for k in ("release_hits", "conv_wraps")})
+    assert opened >= 30 and formats == set(uc.FORMATS) and agc_moved >= 8, (opened, formats, agc_moved)
 
 
 @pytest.mark.ref
@@ -203,10 +190,9 @@ def test_oracle_vs_rebuilt_recorder_random(oracle):
     if not mg.available(REF):
         pytest.skip("Qt headers not available")
     exe = mg.build_recorder(REF)
-    rng = np.random.default_rng(20261018)
-    opened, formats, agc_moved = 0, set(), 0
-    for i in range(100):
-        case = _random_case(rng, i)
+    cases = uc.random_cases()
+    assert len(cases) == 100
+    for case in cases:
         want = mg.record(exe, case["cfg"], uc.inputs(case), case["splits"])
         got = uc.run_oracle(oracle, case)
         assert [f.shape[0] for f in got["feeds"]] == [f.shape[0] for f in want["feeds"]], case
@@ -214,7 +200,3 @@ def test_oracle_vs_rebuilt_recorder_random(oracle):
             assert np.array_equal(g, w) and np.array_equal(gs, ws), case
         assert (got["in_magsq"], got["open"], got["open_count"], got["close_count"]) == \
                (want["in_magsq"], want["open"], want["open_count"], want["close_count"]), case
-        opened += got["probe"]["open"] > 0
-        formats.add(case["cfg"][3])
-        agc_moved += got["probe"]["agc_mode_changes"] > 0
-    assert opened >= 30 and formats == set(uc.FORMATS) and agc_moved >= 8, (opened, formats, agc_moved)

@@ -41,3 +41,19 @@ def test_agc_counter_scans_with_independent_gate_delay_and_step(check, seed):
     out = subprocess.run([check, "agc", str(seed), "300"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
     assert int(out.stdout.split()[1]) > 100000
+
+
+@pytest.mark.parametrize("seed", [1, 20261019])
+def test_arg_of_the_discriminator_is_the_host_libm_atan2f(check, seed):
+    """udp_atan2f (formats 2 and 3) restates the fdlibm float routines that glibc's atan2f was up to 2.40: never more than 2 ulp
+    from the host's atan2f, which is also what tests/udpsrc_oracle.c calls, and its very bits where the libm is such a glibc
+    (checked against 2.35)"""
+    import platform
+    out = subprocess.run([check, "arg", str(seed), "30000000"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
+    n, differ, worst = (int(v) for v in out.stdout.split()[1:4])
+    print(platform.libc_ver(), n, differ, worst)
+    assert n == 30000000 and worst <= 2, out.stdout
+    name, ver = platform.libc_ver()
+    if name == "glibc" and tuple(int(v) for v in ver.split(".")[:2]) <= (2, 35):
+        assert differ == 0, out.stdout

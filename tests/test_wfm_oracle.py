@@ -93,25 +93,11 @@ def test_wrap_case_wraps(oracle):
     assert np.abs(np.diff(a)).max() > 40000             # jumps across the int16 range: the conversion wrapped
 
 
-def _random_case(rng, i):
-    rates = [(240000, 48000), (120000, 48000), (48000, 48000), (250000, 48000), (384000, 44100), (384000, 48000), (96000, 8000),
-             (200000, 44100), (48000, 32000)]
-    in_rate, audio = rates[int(rng.integers(len(rates)))]
-    rf = float(rng.choice([12500.0, 12345.0, 40000.0, 80000.0, 80005.0, 120000.0, 250000.0]))
-    rf = min(rf, in_rate * 0.9)
-    kind = str(rng.choice(["fm", "burst", "noise_full", "zero", "fm"]))
-    f0 = float(rng.integers(-in_rate // 8, in_rate // 8))
-    sig = {"kind": kind, "f0": f0, "dev": rf * 0.4, "fa": float(rng.integers(100, 5000)), "amp": float(rng.integers(50, 20000)),
-           "hi": 12000.0, "lo": float(rng.integers(1, 200)), "noise": float(rng.integers(0, 50)),
-           "runs": [int(v) for v in rng.integers(1, int(rf / 5), size=8)]}
-    cfg = (in_rate, -int(f0), audio, rf, float(rng.choice([3000.0, 15000.0, 20000.0])), float(rng.choice([0.5, 2.0, 10.0])),
-           float(rng.choice([-60.0, -30.0, -25.5, -10.0])), int(rng.random() < 0.1))
-    n = int(rng.integers(2000, 60000))
-    splits, left = [], n
-    while left > 0:
-        m = min(left, int(rng.choice([1, 511, 512, 513, int(rng.integers(1, 3000)), int(rng.integers(1, 30000))])))
-        splits.append(m); left -= m
-    return {"name": f"random{i}", "cfg": cfg, "sig": sig, "n": n, "seed": 1000 + i, "splits": splits}
+def test_random_cases_cover_the_branches(oracle):
+    """the 100 random cases (the GPU banks of tests/test_demod_random_gpu.py run them too) through the oracle: a floor on how
+    many carry audio.  57 do with the generator and seed of tests/wfm_cases.py; the floor is a condition on the inputs"""
+    audible = sum(bool(np.concatenate(wc.run_oracle(oracle, case)["feeds"]).any()) for case in wc.random_cases())
+    assert audible >= 40, audible
 
 
 @pytest.mark.ref
@@ -123,9 +109,9 @@ def test_oracle_vs_rebuilt_recorder_random(oracle):
     if not mg.available(REF):
         pytest.skip("Qt headers not available")
     exe = mg.build_recorder(REF)
-    rng = np.random.default_rng(20261017)
-    for i in range(100):
-        case = _random_case(rng, i)
+    cases = wc.random_cases()
+    assert len(cases) == 100
+    for case in cases:
         want = mg.record(exe, case["cfg"], wc.inputs(case), case["splits"])
         got = wc.run_oracle(oracle, case)
         assert [f.size for f in got["feeds"]] == [f.size for f in want["feeds"]], case

@@ -244,3 +244,41 @@ def run_oracle(L: C.CDLL, case: dict, splits=None) -> dict:
     res = dict(o.state(), feeds=feeds, specs=specs, opens=opens, masks=masks, probe=o.probe())
     o.close()
     return res
+
+
+# ---------------------------------------------------------------- random cases
+def random_case(rng, i) -> dict:
+    """one random configuration, signal and split list; the order of the rng calls is part of the case set"""
+    rates = [(48000, 8000.0), (48000, 48000.0), (62500, 48000.0), (96000, 44100.0), (48000, 11025.5), (60000, 48000.0), (50000, 44100.0),
+             (48000, 32000.0), (16000, 1000.0), (48000, 7999.25)]
+    in_rate, rate = rates[int(rng.integers(len(rates)))]
+    fmt = int(rng.choice(FORMATS))
+    kind = str(rng.choice(["nfm", "am", "burst", "noise_full", "zero", "burst"]))
+    f0 = float(rng.integers(-in_rate // 8, in_rate // 8))
+    base = "am" if (kind in ("am", "burst") and fmt >= 8) else ("nfm" if kind in ("nfm", "am", "burst") else kind)
+    sig = {"kind": base, "f0": f0, "dev": float(rng.choice([500.0, 2000.0])), "fa": float(rng.integers(100, 3000)),
+           "amp": float(rng.integers(2, 20000)), "noise": float(rng.integers(0, 50))}
+    if kind == "burst":
+        sig["runs"] = [int(v) for v in rng.integers(1, in_rate // 8, size=8)]
+        sig["amps"] = [float(rng.integers(300, 16000)), float(rng.integers(1, 30))]
+    n = int(rng.integers(500, 20000))
+    cfg = (in_rate, -int(f0), rate, fmt, float(rng.choice([1300.0, 5000.0, 12500.0])), int(rng.choice([2500, 5000, 100])),
+           float(rng.choice([0.5, 1.0, 7.0, -3.0])), int(rng.choice([-100, -60, -40, -20])), int(rng.choice([0, 0, 1, 2, 5, 17])), int(rng.random() < 0.8), int(rng.random() < 0.5))
+    if cfg[10] and fmt >= 8 and kind == "burst":             # the raw power on both sides of the AGC threshold (amplitude 290 at -20 dB)
+        cfg = cfg[:7] + (int(rng.choice([-20, -10])),) + cfg[8:]
+        sig["amps"] = [float(rng.integers(3000, 16000)), float(rng.integers(1, 100))]
+    splits, left = [], n
+    while left > 0:
+        m = min(left, int(rng.choice([0, 1, 2, 32, 33, int(rng.integers(1, 300)), int(rng.integers(1, 8000))])))
+        splits.append(m); left -= m
+    return {"name": f"random{i}", "cfg": cfg, "sig": sig, "n": n, "seed": 2000 + i, "splits": splits}
+
+
+#: the seed of random_cases(): the cases the `ref` test of tests/test_udpsrc_oracle.py proves against the reference
+RANDOM_SEED = 20261018
+
+
+def random_cases(count: int = 100) -> list[dict]:
+    """the first `count` random cases, drawn in order from one generator"""
+    rng = np.random.default_rng(RANDOM_SEED)
+    return [random_case(rng, i) for i in range(count)]

@@ -10,6 +10,7 @@
 //                                           (maps composed over random chunks in random association, applied to the carried
 //                                           state) against the counters written with the reference's ifs
 // prints "ok <checked>" or the first mismatch, exit status 0 / 1
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -226,11 +227,40 @@ static int agc_counters(int rounds)
     return 0;
 }
 
+// udp_atan2f against the host's atan2f: products of two int16-sized factors as the discriminator forms them, fixed-point pairs
+// and arbitrary bit patterns (zeros, subnormals, infinities, NaN).  Prints the count, how many differ and the largest distance in ulp.
+static int arg_check(long rounds)
+{
+    long differ = 0, worst = 0;
+    for (long i = 0; i < rounds; i++) {
+        const uint64_t r = rnd();
+        float y, x;
+        if (i % 3 == 0) { const uint32_t a = (uint32_t)r, b = (uint32_t)(r >> 32); memcpy(&y, &a, 4); memcpy(&x, &b, 4); }
+        else if (i % 3 == 1) { y = (float)(int32_t)(r & 0xffffffffu) * (1.0f / 65536.0f); x = (float)(int32_t)(r >> 32) * (1.0f / 65536.0f); }
+        else {
+            y = (float)((int)(r & 0xffff) - 32768) * (float)((int)((r >> 16) & 0xffff) - 32768);
+            x = (float)((int)((r >> 32) & 0xffff) - 32768) * (float)((int)(r >> 48) - 32768) + y * 0.001f;
+        }
+        const float want = atan2f(y, x), got = udp_atan2f(y, x);
+        if (want != want && got != got) continue;
+        int32_t a, b; memcpy(&a, &want, 4); memcpy(&b, &got, 4);
+        if (a == b) continue;
+        differ++;
+        if (a < 0) a = (int32_t)0x80000000u - a;
+        if (b < 0) b = (int32_t)0x80000000u - b;
+        const long d = labs((long)a - (long)b);
+        if (want != want || got != got || d > worst) worst = (want != want || got != got) ? 1L << 40 : d;
+    }
+    printf("ok %ld %ld %ld\n", rounds, differ, worst);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc > 3 && !strcmp(argv[1], "arg")) { g_s = strtoull(argv[2], nullptr, 10); return arg_check(atol(argv[3])); }
     if (argc > 1 && !strcmp(argv[1], "exhaustive")) return exhaustive();
     if (argc > 3 && !strcmp(argv[1], "random")) { g_s = strtoull(argv[2], nullptr, 10); return random_long(atoi(argv[3])); }
     if (argc > 3 && !strcmp(argv[1], "agc")) { g_s = strtoull(argv[2], nullptr, 10); return agc_counters(atoi(argv[3])); }
-    fprintf(stderr, "usage: udpsrc_scan_check exhaustive | random <seed> <rounds> | agc <seed> <rounds>\n");
+    fprintf(stderr, "usage: udpsrc_scan_check exhaustive | random <seed> <rounds> | agc <seed> <rounds> | arg <seed> <rounds>\n");
     return 2;
 }

@@ -255,3 +255,36 @@ def run_oracle(L: C.CDLL, case: dict, splits=None) -> dict:
     res = {"feeds": feeds, "sum": s, "peak": p, "count": n, "open": o.squelch_open(), "state": o.squelch_state(), "ge": o.count_ge()}
     o.close()
     return res
+
+
+# ---------------------------------------------------------------- random cases
+def random_case(rng, i) -> dict:
+    """one random configuration, signal and split list; the order of the rng calls is part of the case set"""
+    rates = [(240000, 48000), (120000, 48000), (48000, 48000), (250000, 48000), (384000, 44100), (384000, 48000), (96000, 8000),
+             (200000, 44100), (48000, 32000)]
+    in_rate, audio = rates[int(rng.integers(len(rates)))]
+    rf = float(rng.choice([12500.0, 12345.0, 40000.0, 80000.0, 80005.0, 120000.0, 250000.0]))
+    rf = min(rf, in_rate * 0.9)
+    kind = str(rng.choice(["fm", "burst", "noise_full", "zero", "fm"]))
+    f0 = float(rng.integers(-in_rate // 8, in_rate // 8))
+    sig = {"kind": kind, "f0": f0, "dev": rf * 0.4, "fa": float(rng.integers(100, 5000)), "amp": float(rng.integers(50, 20000)),
+           "hi": 12000.0, "lo": float(rng.integers(1, 200)), "noise": float(rng.integers(0, 50)),
+           "runs": [int(v) for v in rng.integers(1, int(rf / 5), size=8)]}
+    cfg = (in_rate, -int(f0), audio, rf, float(rng.choice([3000.0, 15000.0, 20000.0])), float(rng.choice([0.5, 2.0, 10.0])),
+           float(rng.choice([-60.0, -30.0, -25.5, -10.0])), int(rng.random() < 0.1))
+    n = int(rng.integers(2000, 60000))
+    splits, left = [], n
+    while left > 0:
+        m = min(left, int(rng.choice([1, 511, 512, 513, int(rng.integers(1, 3000)), int(rng.integers(1, 30000))])))
+        splits.append(m); left -= m
+    return {"name": f"random{i}", "cfg": cfg, "sig": sig, "n": n, "seed": 1000 + i, "splits": splits}
+
+
+#: the seed of random_cases(): the cases the `ref` test of tests/test_wfm_oracle.py proves against the reference
+RANDOM_SEED = 20261017
+
+
+def random_cases(count: int = 100) -> list[dict]:
+    """the first `count` random cases, drawn in order from one generator"""
+    rng = np.random.default_rng(RANDOM_SEED)
+    return [random_case(rng, i) for i in range(count)]
