@@ -1,5 +1,6 @@
-// host code the demodulator banks share (sdrx_wfm.hip, sdrx_am.hip, sdrx_nfm.hip): input staging and checks, the hand-over
-// from a channelizer bank, one channel's device state, the per-feed pointer table, the Bandpass design.  `who` is the entry point named in the error text.
+// host code the demodulator banks share (sdrx_wfm.hip directly; sdrx_am.hip, sdrx_nfm.hip, sdrx_ssb.hip and sdrx_udpsrc.hip
+// through demod_bank.hpp): input staging and checks, the hand-over from a channelizer bank, one channel's device state, the
+// per-feed pointer table, the Bandpass design.  `who` is the entry point named in the error text.
 #pragma once
 #include "sdrx_common.hpp"
 #include <algorithm>

@@ -2,334 +2,135 @@
 // plugins/channelrx/demodam/amdemod.cpp:101-276) on one device: int16 I/Q at the channelizer's output rate in, mono qint16
 // audio out.  The front (NCO, Interpolator) is a channel back-end the handle owns and launches on its own stream; the tail's
 // kernels are in am_kernels.hpp.  Host side: the design products as applyChannelSettings / applyAudioSampleRate /
-// applySettings derive them (amdemod.cpp:360-475), launches, buffer bookkeeping.
+// applySettings derive them (amdemod.cpp:360-475), the two layouts and the launches; the rest is demod_bank.hpp's.
 #include "sdrx_common.hpp"
 #include "am_kernels.hpp"
-#include "backend_view.hpp"
-#include "demod_common.hpp"
+#include "demod_bank.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using namespace sdrx;
 
-namespace {
+struct AmFamily : DemodDefaults {
+    using Handle = sdrx_am;
+    using Cfg = sdrx_am_cfg;
+    using Chan = AmChan;
+    using Bufs = AmBufs;
+    static constexpr const char* name = "sdrx_am";
+    static constexpr const float2* AmBufs::* input = &AmBufs::ci;
+    static constexpr int bp_taps = AM_BP_H + 1;
 
-struct AmHost {
-    DevBuf work, stage_in;
-    char* hist = nullptr;             // two sets of [16 magsq | D roots | H fed values | 300 demods]
-    size_t hist_set = 0;              // bytes of one set
-    int cur = 0;
-    int64_t cap_in = 0;
-};
-
-constexpr size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
-} // namespace
-
-struct sdrx_am {
-    HandleCore core;
-    int n_ch = 0;
-    std::vector<sdrx_am_cfg> cfg;
-    std::vector<sdrx_backend_cfg> be_cfg;
-    sdrx_backend_t* front = nullptr;
-    std::vector<AmHost> ch;
-    std::vector<AmChan> h_chan;   // configuration and the state of a fresh handle
-    AmChan* d_chan = nullptr;
-    AmBufs* d_bufs = nullptr;
-    AmBufs* h_bufs = nullptr;     // pinned: the per-feed table goes to the device in one async copy
-    hipEvent_t bufs_ev = nullptr;
-    float* d_bp = nullptr;
-    std::vector<float> bp_all;
-};
-
-static int validate(int32_t n_ch, const sdrx_am_cfg* cfg)
-{
-    if (n_ch <= 0 || !cfg) { set_error("sdrx_am_create: bad argument"); return SDRX_EINVAL; }
-    for (int c = 0; c < n_ch; c++) {
-        const sdrx_am_cfg& k = cfg[c];
-        if (k.in_rate <= 0 || k.audio_rate < 1000 || k.audio_rate > k.in_rate) {
-            set_error("sdrx_am_create: bad channel configuration (need 1000 <= audio_rate <= in_rate; the interpolating branch is left out)");
-            return SDRX_EINVAL;
+    static int validate(int32_t n_ch, const sdrx_am_cfg* cfg)
+    {
+        if (n_ch <= 0 || !cfg) { set_error("sdrx_am_create: bad argument"); return SDRX_EINVAL; }
+        for (int c = 0; c < n_ch; c++) {
+            const sdrx_am_cfg& k = cfg[c];
+            if (k.in_rate <= 0 || k.audio_rate < 1000 || k.audio_rate > k.in_rate) {
+                set_error("sdrx_am_create: bad channel configuration (need 1000 <= audio_rate <= in_rate; the interpolating branch is left out)");
+                return SDRX_EINVAL;
+            }
+            if (!(k.rf_bandwidth > 0.0f) || !(k.rf_bandwidth <= 1.0e7f)) {
+                set_error("sdrx_am_create: bad channel configuration (need 0 < rf_bandwidth <= 1e7)"); return SDRX_EINVAL;
+            }
+            if (!std::isfinite(k.volume) || !std::isfinite(k.squelch_db)) {
+                set_error("sdrx_am_create: bad channel configuration (volume and squelch_db must be finite)"); return SDRX_EINVAL;
+            }
         }
-        if (!(k.rf_bandwidth > 0.0f) || !(k.rf_bandwidth <= 1.0e7f)) {
-            set_error("sdrx_am_create: bad channel configuration (need 0 < rf_bandwidth <= 1e7)"); return SDRX_EINVAL;
-        }
-        if (!std::isfinite(k.volume) || !std::isfinite(k.squelch_db)) {
-            set_error("sdrx_am_create: bad channel configuration (volume and squelch_db must be finite)"); return SDRX_EINVAL;
-        }
+        return SDRX_OK;
     }
-    return SDRX_OK;
-}
 
-static int ensure_capacity(sdrx_am* b, int c, int64_t n_in)
-{
-    AmHost& h = b->ch[(size_t)c];
-    if (n_in <= h.cap_in) return SDRX_OK;
-    int64_t cap = h.cap_in ? h.cap_in : 4096;
-    while (cap < n_in) cap *= 2;
-    // every audio sample consumes at least one input (step >= 1): at most `cap` samples per feed; nothing here carries state
-    const size_t n = (size_t)cap + 16, nblk = n / 256 + 1;
-    const size_t bytes = 4 * al(n * 4) + al(n * 4) + 5 * al(n * 8) + al(n * 4) + al(n * 2) + al(nblk * 8) + al(nblk * 4);
-    SDRX_HIP(hipStreamSynchronize(b->core.stream));
-    int rc = h.work.reserve(bytes); if (rc) return rc;
-    h.cap_in = cap;
-    return SDRX_OK;
-}
-
-static int upload_fresh_state(sdrx_am* b)
-{
-    SDRX_HIP(hipMemcpyAsync(b->d_chan, b->h_chan.data(), (size_t)b->n_ch * sizeof(AmChan), hipMemcpyHostToDevice, b->core.stream));
-    std::vector<char> img;
-    for (int c = 0; c < b->n_ch; c++) {
-        AmHost& h = b->ch[(size_t)c];
-        const AmChan& s = b->h_chan[(size_t)c];
-        img.assign(h.hist_set, 0);
-        // MovingAverage<double>(rate / 10, 0.003): every entry (double) 0.003f; everything else starts at 0 (the delay line too:
-        // DoubleBufferFIFO does not clear its array, see sdrx.h)
-        double* v = reinterpret_cast<double*>(img.data() + al(AM_MA * 4) + al((size_t)s.D * 4));
-        for (int i = 0; i < s.H; i++) v[i] = am_agc_initial();
-        SDRX_HIP(hipMemcpyAsync(h.hist, img.data(), h.hist_set, hipMemcpyHostToDevice, b->core.stream));
-        SDRX_HIP(hipStreamSynchronize(b->core.stream));        // img is reused
-        h.cur = 0;
-    }
-    return SDRX_OK;
-}
-
-static int make_front(sdrx_am* b)
-{
-    int rc = sdrx_backend_create(&b->front, b->core.device, b->n_ch, b->be_cfg.data()); if (rc) return rc;
-    return backend_set_stream(b->front, b->core.stream);
-}
-
-extern "C" {
-
-int sdrx_am_destroy(sdrx_am_t* b)
-{
-    if (!b) return SDRX_OK;
-    (void)hipSetDevice(b->core.device);
-    if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
-    if (b->front) (void)sdrx_backend_destroy(b->front);
-    for (auto& h : b->ch) {
-        h.work.release(); h.stage_in.release();
-        if (h.hist) (void)hipFree(h.hist);
-    }
-    if (b->d_chan) (void)hipFree(b->d_chan);
-    if (b->d_bufs) (void)hipFree(b->d_bufs);
-    if (b->h_bufs) (void)hipHostFree(b->h_bufs);
-    if (b->bufs_ev) (void)hipEventDestroy(b->bufs_ev);
-    if (b->d_bp) (void)hipFree(b->d_bp);
-    b->core.close();
-    delete b;
-    return SDRX_OK;
-}
-
-int sdrx_am_create(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg* cfg)
-{
-    if (!out) { set_error("sdrx_am_create: null out"); return SDRX_EINVAL; }
-    *out = nullptr;
-    int rc = validate(n_ch, cfg); if (rc) return rc;
-    sdrx_am* b = new (std::nothrow) sdrx_am;
-    if (!b) return SDRX_ENOMEM;
-    rc = b->core.open(device);
-    if (rc) { delete b; return rc; }
-    b->n_ch = n_ch;
-    b->cfg.assign(cfg, cfg + n_ch);
-    b->ch.resize((size_t)n_ch); b->h_chan.resize((size_t)n_ch); b->be_cfg.resize((size_t)n_ch);
-    b->bp_all.assign((size_t)n_ch * (AM_BP_H + 1), 0.0f);
-
-    for (int c = 0; c < n_ch; c++) {
-        const sdrx_am_cfg& k = cfg[c];
-        sdrx_backend_cfg& f = b->be_cfg[(size_t)c];
-        std::memset(&f, 0, sizeof f);
+    static void design(int c, const sdrx_am_cfg& k, sdrx_backend_cfg& f, AmChan& s, float* bp)
+    {
         f.in_rate = k.in_rate; f.nco_freq = k.nco_freq; f.out_rate = k.audio_rate;
         f.interp_cutoff = k.rf_bandwidth / 2.2f;            // m_interpolator.create(16, inputSampleRate, rfBandwidth / 2.2f)
         f.taps_per_phase = 4.5f;
-        AmChan& s = b->h_chan[(size_t)c];
-        std::memset(&s, 0, sizeof s);
         s.rate = k.audio_rate; s.D = k.audio_rate / 20; s.H = k.audio_rate / 10;
         s.level = (float)std::pow(10.0, (double)k.squelch_db / 10.0);      // CalcDb::powerFromdB
         s.volume = k.volume;
         s.att = 0.05f * (float)(uint32_t)k.audio_rate;
         s.gain = (float)(uint32_t)(k.audio_rate / 24);
         s.mute = k.audio_mute ? 1 : 0; s.bandpass = k.bandpass_enable ? 1 : 0;
-        s.bp_off = c * (AM_BP_H + 1);
+        s.bp_off = c * bp_taps;
         s.agc_sum = (double)s.H * am_agc_initial();         // m_sum = (Type) m_history.size() * initial
         // m_bandpass.create(301, audioSampleRate, 300.0, rfBandwidth / 2.0f)
-        demod_bandpass_design((double)k.audio_rate, 300.0, (double)(k.rf_bandwidth / 2.0f), &b->bp_all[(size_t)s.bp_off]);
-        AmHost& h = b->ch[(size_t)c];
-        h.hist_set = al(AM_MA * 4) + al((size_t)s.D * 4) + al((size_t)s.H * 8) + al(AM_BP_HIST * 4);
-        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.hist), 2 * h.hist_set), sdrx_am_destroy(b));
+        demod_bandpass_design((double)k.audio_rate, 300.0, (double)(k.rf_bandwidth / 2.0f), bp);
     }
-    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bp), b->bp_all.size() * 4), sdrx_am_destroy(b));
-    SDRX_HIP_ELSE(hipMemcpy(b->d_bp, b->bp_all.data(), b->bp_all.size() * 4, hipMemcpyHostToDevice), sdrx_am_destroy(b));
-    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(AmChan)), sdrx_am_destroy(b));
-    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(AmBufs)), sdrx_am_destroy(b));
-    SDRX_HIP_ELSE(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(AmBufs), hipHostMallocDefault), sdrx_am_destroy(b));
-    SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->bufs_ev, hipEventDisableTiming), sdrx_am_destroy(b));
-    SDRX_HIP_ELSE(hipEventRecord(b->bufs_ev, b->core.stream), sdrx_am_destroy(b));
-    rc = make_front(b);
-    if (!rc) rc = upload_fresh_state(b);
-    if (rc) { sdrx_am_destroy(b); return rc; }
-    *out = b;
-    return SDRX_OK;
-}
 
-int sdrx_am_reset(sdrx_am_t* b)
-{
-    if (!b) { set_error("sdrx_am_reset: null handle"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->core.device));
-    SDRX_HIP(hipStreamSynchronize(b->core.stream));
-    // the front has no reset of its own: a fresh one with the same design
-    if (b->front) { (void)sdrx_backend_destroy(b->front); b->front = nullptr; }
-    int rc = make_front(b); if (rc) return rc;
-    return upload_fresh_state(b);
-}
-
-// the tail behind a front feed that has just been queued on the handle's stream
-static int tail_common(sdrx_am* b, const int64_t* n_per_ch)
-{
-    int64_t bound = 0;
-    for (int c = 0; c < b->n_ch; c++) {
-        int rc = ensure_capacity(b, c, std::max<int64_t>(n_per_ch[c], 1)); if (rc) return rc;
-        // every audio sample after the first two of a stream consumes >= floor(step) inputs
-        const int64_t per_out = std::max<int64_t>(1, b->cfg[(size_t)c].in_rate / b->cfg[(size_t)c].audio_rate);
-        bound = std::max(bound, std::min<int64_t>(n_per_ch[c], n_per_ch[c] / per_out + 4));
+    // one history set: [16 magsq | D roots | H fed values | 300 demods]
+    static void hist(HistCarver& k, const AmChan& s, AmBufs& u)
+    {
+        k.pair(u.mhist, u.mhist_next, AM_MA);
+        k.pair(u.rhist, u.rhist_next, (size_t)s.D);
+        k.pair(u.vhist, u.vhist_next, (size_t)s.H);
+        k.pair(u.dhist, u.dhist_next, AM_BP_HIST);
     }
-    SDRX_HIP(hipEventSynchronize(b->bufs_ev));            // previous feed's copy has read the table
-    for (int c = 0; c < b->n_ch; c++) {
-        AmHost& h = b->ch[(size_t)c];
-        const AmChan& s = b->h_chan[(size_t)c];
-        AmBufs& u = b->h_bufs[c];
-        BackendView v;
-        int rc = backend_view(b->front, c, &v); if (rc) return rc;
-        u.ci = static_cast<const float2*>(v.out); u.n_ptr = v.n_out;
-        char* set[2] = { h.hist + (size_t)h.cur * h.hist_set, h.hist + (size_t)(h.cur ^ 1) * h.hist_set };
-        size_t o = 0;
-        u.mhist = reinterpret_cast<const float*>(set[0] + o); u.mhist_next = reinterpret_cast<float*>(set[1] + o); o += al(AM_MA * 4);
-        u.rhist = reinterpret_cast<const float*>(set[0] + o); u.rhist_next = reinterpret_cast<float*>(set[1] + o); o += al((size_t)s.D * 4);
-        u.vhist = reinterpret_cast<const double*>(set[0] + o); u.vhist_next = reinterpret_cast<double*>(set[1] + o); o += al((size_t)s.H * 8);
-        u.dhist = reinterpret_cast<const float*>(set[0] + o); u.dhist_next = reinterpret_cast<float*>(set[1] + o);
-        const size_t n = (size_t)h.cap_in + 16, nblk = n / 256 + 1;
-        char* p = static_cast<char*>(h.work.p);
-        auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return r; };
-        u.msq = reinterpret_cast<float*>(take(n * 4)); u.root = reinterpret_cast<float*>(take(n * 4));
-        u.cnt = reinterpret_cast<int*>(take(n * 4)); u.aidx = reinterpret_cast<int*>(take(n * 4)); u.fcnt = reinterpret_cast<int*>(take(n * 4));
-        u.dterm = reinterpret_cast<double*>(take(n * 8)); u.tot = reinterpret_cast<double*>(take(n * 8));
-        u.vnew = reinterpret_cast<double*>(take(n * 8)); u.uterm = reinterpret_cast<double*>(take(n * 8)); u.agc = reinterpret_cast<double*>(take(n * 8));
-        u.dem = reinterpret_cast<float*>(take(n * 4));
-        u.audio = reinterpret_cast<int16_t*>(take(n * 2));
-        u.blk_sum = reinterpret_cast<double*>(take(nblk * 8)); u.blk_peak = reinterpret_cast<float*>(take(nblk * 4));
+
+    // MovingAverage<double>(rate / 10, 0.003): every entry (double) 0.003f; everything else starts at 0 (the delay line too:
+    // DoubleBufferFIFO does not clear its array, see sdrx.h)
+    static void fresh(const AmChan& s, AmBufs& u) { for (int i = 0; i < s.H; i++) u.vhist_next[i] = am_agc_initial(); }
+
+    static void work(Carver& k, size_t n, AmBufs& u)
+    {
+        const size_t nblk = n / 256 + 1;
+        u.msq = k.take<float>(n); u.root = k.take<float>(n);
+        u.cnt = k.take<int>(n); u.aidx = k.take<int>(n); u.fcnt = k.take<int>(n);
+        u.dterm = k.take<double>(n); u.tot = k.take<double>(n);
+        u.vnew = k.take<double>(n); u.uterm = k.take<double>(n); u.agc = k.take<double>(n);
+        u.dem = k.take<float>(n);
+        u.audio = k.take<int16_t>(n);
+        u.blk_sum = k.take<double>(nblk); u.blk_peak = k.take<float>(nblk);
     }
-    int rc = demod_upload_bufs(b->d_bufs, b->h_bufs, b->n_ch, b->bufs_ev, b->core.stream); if (rc) return rc;
-    const unsigned nc = (unsigned)b->n_ch, gp = (nc + AM_PS_CH - 1) / AM_PS_CH, gx = (unsigned)std::max<int64_t>(1, (bound + 255) / 256);
-    hipLaunchKernelGGL(am_level_kernel, dim3(gx, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
-    SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch, 0);
-    SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_gate_kernel, dim3(nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
-    SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch, 1);
-    SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_demod_kernel, dim3(gx, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
-    SDRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(am_out_kernel, dim3(gx, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_bp);
-    SDRX_HIP(hipGetLastError());
-    b->core.note_launch("am_out_kernel", (int)(gx * nc), 256, (int)((AM_BP_H + 1) * sizeof(float)));
-    hipLaunchKernelGGL(am_carry_kernel, dim3(nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
-    SDRX_HIP(hipGetLastError());
-    for (auto& h : b->ch) h.cur ^= 1;
-    return SDRX_OK;
-}
 
-int sdrx_am_feed_dev(sdrx_am_t* b, const int16_t* const* d_iq, const int64_t* n_per_ch)
-{
-    if (!b || !d_iq || !n_per_ch) { set_error("sdrx_am_feed_dev: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->core.device));
-    int rc = demod_check_lengths(b->n_ch, n_per_ch, "sdrx_am_feed_dev"); if (rc) return rc;
-    rc = demod_check_dev_pointers(b->n_ch, d_iq, n_per_ch, "sdrx_am_feed_dev"); if (rc) return rc;
-    rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
-    rc = sdrx_backend_feed_dev(b->front, d_iq, n_per_ch); if (rc) return rc;
-    rc = tail_common(b, n_per_ch); if (rc) return rc;
-    return b->core.timer.end(b->core.stream);
-}
+    static int64_t outputs_bound(const sdrx_am_cfg& k, int64_t n_in) { return demod_outputs_bound(k.in_rate / k.audio_rate, n_in); }
 
-int sdrx_am_feed_bank(sdrx_am_t* b, sdrx_chan_bank_t* bank)
-{
-    if (!b || !bank) { set_error("sdrx_am_feed_bank: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->core.device));
-    std::vector<const int16_t*> d;                          // the front takes them from the bank itself
-    std::vector<int64_t> n;
-    int rc = demod_gather_bank(bank, b->n_ch, "sdrx_am_feed_bank", d, n); if (rc) return rc;
-    rc = demod_check_lengths(b->n_ch, n.data(), "sdrx_am_feed_bank"); if (rc) return rc;
-    rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
-    // the front orders its readers against the bank's stream (sdrx_backend_feed_bank); the tail reads the front's output only
-    rc = sdrx_backend_feed_bank(b->front, bank); if (rc) return rc;
-    rc = tail_common(b, n.data()); if (rc) return rc;
-    return b->core.timer.end(b->core.stream);
-}
+    static int launch(DemodBank<AmFamily>& b, unsigned nc, unsigned gx)
+    {
+        const unsigned gp = (nc + AM_PS_CH - 1) / AM_PS_CH;
+        hipLaunchKernelGGL(am_level_kernel, dim3(gx, nc), dim3(256), 0, b.core.stream, b.d_chan, b.d_bufs);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b.core.stream, b.d_chan, b.d_bufs, b.n_ch, 0);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(am_gate_kernel, dim3(nc), dim3(256), 0, b.core.stream, b.d_chan, b.d_bufs);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(am_psum_kernel, dim3(gp), dim3(64), 0, b.core.stream, b.d_chan, b.d_bufs, b.n_ch, 1);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(am_demod_kernel, dim3(gx, nc), dim3(256), 0, b.core.stream, b.d_chan, b.d_bufs);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(am_out_kernel, dim3(gx, nc), dim3(256), 0, b.core.stream, b.d_chan, b.d_bufs, b.d_bp);
+        SDRX_HIP(hipGetLastError());
+        b.core.note_launch("am_out_kernel", (int)(gx * nc), 256, (int)((AM_BP_H + 1) * sizeof(float)));
+        hipLaunchKernelGGL(am_carry_kernel, dim3(nc), dim3(256), 0, b.core.stream, b.d_chan, b.d_bufs);
+        SDRX_HIP(hipGetLastError());
+        return SDRX_OK;
+    }
 
-int sdrx_am_feed(sdrx_am_t* b, const int16_t* const* iq, const int64_t* n_per_ch)
-{
-    if (!b || !iq || !n_per_ch) { set_error("sdrx_am_feed: null argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->core.device));
-    std::vector<const int16_t*> d;
-    int rc = demod_stage_inputs(b->ch, b->core.stream, iq, n_per_ch, "sdrx_am_feed", d); if (rc) return rc;
-    rc = sdrx_am_feed_dev(b, d.data(), n_per_ch); if (rc) return rc;
-    SDRX_HIP(hipStreamSynchronize(b->core.stream));            // the caller's buffers are free again on return
-    return SDRX_OK;
-}
+    static double magsq(const AmChan& s) { return s.magsq; }
+};
 
-int64_t sdrx_am_read(sdrx_am_t* b, int32_t c, int16_t* audio, int64_t cap)
-{
-    if (!b || c < 0 || c >= b->n_ch || cap < 0 || (cap > 0 && !audio)) { set_error("sdrx_am_read: bad argument"); return SDRX_EINVAL; }
-    AmChan s;
-    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
-    const int64_t n = std::min<int64_t>(s.n, cap);
-    if (n == 0) return 0;
-    SDRX_HIP(hipMemcpy(audio, b->h_bufs[c].audio, (size_t)n * 2, hipMemcpyDeviceToHost));
-    return n;
-}
+struct sdrx_am : DemodBank<AmFamily> {};
+using Bank = DemodBank<AmFamily>;
 
-int sdrx_am_last_dev(sdrx_am_t* b, int32_t c, const int16_t** d_audio, int64_t* n)
-{
-    if (!b || c < 0 || c >= b->n_ch || !d_audio || !n) { set_error("sdrx_am_last_dev: bad argument"); return SDRX_EINVAL; }
-    AmChan s;
-    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
-    *d_audio = s.n > 0 ? b->h_bufs[c].audio : static_cast<const int16_t*>(b->ch[(size_t)c].work.p);
-    *n = s.n;
-    return SDRX_OK;
-}
+extern "C" {
 
-int sdrx_am_squelch_open(sdrx_am_t* b, int32_t c)
-{
-    if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_am_squelch_open: bad argument"); return SDRX_EINVAL; }
-    AmChan s;
-    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
-    return s.sq_open;
-}
-
-int sdrx_am_levels(sdrx_am_t* b, int32_t c, double* magsq, double* sum, double* peak, int64_t* count, int reset)
-{
-    if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_am_levels: bad argument"); return SDRX_EINVAL; }
-    AmChan s;
-    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
-    if (magsq) *magsq = s.magsq;
-    if (sum) *sum = s.magsq_sum;
-    if (peak) *peak = s.magsq_peak;
-    if (count) *count = s.magsq_count;
-    if (!reset) return SDRX_OK;                           // getMagSqLevels: sum, peak and count back to 0; m_magsq stays
-    return demod_zero_levels(b->core, b->d_chan + c, offsetof(AmChan, magsq_sum), offsetof(AmChan, magsq_peak), offsetof(AmChan, magsq_count));
-}
+int sdrx_am_create(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg* cfg) { return Bank::create(out, device, n_ch, cfg); }
+int sdrx_am_destroy(sdrx_am_t* b) { return Bank::destroy(b); }
+int sdrx_am_reset(sdrx_am_t* b) { return Bank::reset(b); }
+int sdrx_am_feed_dev(sdrx_am_t* b, const int16_t* const* d_iq, const int64_t* n_per_ch) { return Bank::feed_dev(b, d_iq, n_per_ch); }
+int sdrx_am_feed_bank(sdrx_am_t* b, sdrx_chan_bank_t* bank) { return Bank::feed_bank(b, bank); }
+int sdrx_am_feed(sdrx_am_t* b, const int16_t* const* iq, const int64_t* n_per_ch) { return Bank::feed(b, iq, n_per_ch); }
+int64_t sdrx_am_read(sdrx_am_t* b, int32_t c, int16_t* audio, int64_t cap) { return Bank::read(b, "read", c, audio, cap, &AmBufs::audio, &AmChan::n, 2); }
+int sdrx_am_last_dev(sdrx_am_t* b, int32_t c, const int16_t** d_audio, int64_t* n) { return Bank::last_dev(b, "last_dev", c, d_audio, n, &AmBufs::audio, &AmChan::n); }
+int sdrx_am_squelch_open(sdrx_am_t* b, int32_t c) { return Bank::flag(b, "squelch_open", c, &AmChan::sq_open); }
+int sdrx_am_levels(sdrx_am_t* b, int32_t c, double* magsq, double* sum, double* peak, int64_t* count, int reset) { return Bank::levels(b, c, magsq, sum, peak, count, reset); }
 
 int sdrx_am_get_design(sdrx_am_t* b, int32_t c, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
                        float* bandpass_taps, int32_t* nco_inc, float* squelch_level)
 {
-    if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_am_get_design: bad channel"); return SDRX_EINVAL; }
+    if (!Bank::in_range(b, c)) return Bank::fail("get_design", ": bad channel");
     int rc = sdrx_backend_get_design(b->front, c, ntaps_per_phase, taps_cap > 0 ? taps : nullptr, taps_cap, nullptr, nco_inc); if (rc) return rc;
     if (bandpass_taps) std::memcpy(bandpass_taps, &b->bp_all[(size_t)b->h_chan[(size_t)c].bp_off], (AM_BP_H + 1) * 4);
     if (squelch_level) *squelch_level = b->h_chan[(size_t)c].level;
@@ -337,20 +138,10 @@ int sdrx_am_get_design(sdrx_am_t* b, int32_t c, int32_t* ntaps_per_phase, float*
 }
 
 int sdrx_am_sync(sdrx_am_t* b) { return b ? b->core.sync() : SDRX_EINVAL; }
-
-int sdrx_am_set_stream(sdrx_am_t* b, void* hip_stream)
-{
-    if (!b) return SDRX_EINVAL;
-    int rc = b->core.set_stream(hip_stream); if (rc) return rc;
-    return backend_set_stream(b->front, b->core.stream);      // the front launches on the same stream
-}
-
+int sdrx_am_set_stream(sdrx_am_t* b, void* hip_stream) { return Bank::set_stream(b, hip_stream); }
 int sdrx_am_get_stream(sdrx_am_t* b, void** hip_stream) { return b ? b->core.get_stream(hip_stream) : SDRX_EINVAL; }
-
 int sdrx_am_set_timing(sdrx_am_t* b, int enabled) { return b ? b->core.set_timing(enabled) : SDRX_EINVAL; }
-
 int sdrx_am_get_timing(sdrx_am_t* b, double* total_ms, int64_t* feeds, int reset) { return b ? b->core.get_timing(total_ms, feeds, reset) : SDRX_EINVAL; }
-
 int sdrx_am_last_launch(const sdrx_am_t* b, char* kernel_name, int name_cap, int* grid, int* block, int* lds_bytes) { return b ? b->core.last_launch(kernel_name, name_cap, grid, block, lds_bytes) : SDRX_EINVAL; }
 
 } // extern "C"
