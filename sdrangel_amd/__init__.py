@@ -505,6 +505,12 @@ class DecimatorsU(Decimators):
         _check(lib().sdrx_decim_process_u8(self._h, buf.ctypes.data, buf.size, out.ctypes.data, C.byref(n)), "sdrx_decim_process_u8")
         return out[: 2 * n.value]
 
+    def decimate_dev(self, d_in_ptr: int, n_uint8: int, d_out_ptr: int) -> int:
+        """device pointers (d_in 8-byte aligned); asynchronous on the handle's stream; returns #complex outputs"""
+        n = C.c_int64()
+        _check(lib().sdrx_decim_process_dev_u8(self._h, d_in_ptr, n_uint8, d_out_ptr, C.byref(n)), "sdrx_decim_process_dev_u8")
+        return n.value
+
 
 class Fanout(_Handle):
     """One staged source stream copied to several GPUs point-to-point (sdrx_fanout_*; xGMI peer copies on a multi-GPU node)."""
@@ -1184,7 +1190,7 @@ class AudioTailCfg(C.Structure):
                 ("agc_clamping", C.c_int32), ("agc_threshold", C.c_double)]
 
 
-class AudioTail(_Handle):
+class AudioTail(_Handle, _Sync):
     """audio-rate tail of the NFM / SSB demods (squelch / MagAGC / delay line / Bandpass -> qint16) for N channels"""
     _prefix = "audiotail"
 
@@ -1204,6 +1210,13 @@ class AudioTail(_Handle):
         ns = (C.c_int64 * self.n_ch)(*[x.size // 2 for x in ins])
         self._call("feed", pi, ns, po)
         return [o[: x.size // 2] for o, x in zip(outs, ins)]
+
+    def feed_dev(self, in_ptrs, counts, out_ptrs):
+        """device pointers per channel: counts[c] complex floats in, counts[c] qint16 out; asynchronous, sync() waits"""
+        pi = (C.c_void_p * self.n_ch)(*in_ptrs)
+        ns = (C.c_int64 * self.n_ch)(*counts)
+        po = (C.c_void_p * self.n_ch)(*out_ptrs)
+        self._call("feed_dev", pi, ns, po)
 
 
 class IirCfg(C.Structure):
@@ -1304,7 +1317,7 @@ class ChannelizerBank24(_Handle, _Sync):
         return outs
 
 
-class IqImbalance(_Handle):
+class IqImbalance(_Handle, _Sync, _SetStream):
     """DSPDeviceSourceEngine::iqCorrections(begin, end, true) (DC + I/Q imbalance, float flavour) for N device streams."""
     _prefix = "iqimb"
 
@@ -1322,6 +1335,14 @@ class IqImbalance(_Handle):
         ns = (C.c_int64 * self.n)(*[b.size // 2 for b in bufs])
         self._call("process", ptrs, ns)
         return bufs
+
+    def process_dev(self, in_ptrs, out_ptrs, counts):
+        """device pointers (4-byte aligned) and complex sample counts per stream; out may equal in; asynchronous on the
+        handle's stream"""
+        pi = (C.c_void_p * self.n)(*in_ptrs)
+        po = (C.c_void_p * self.n)(*out_ptrs)
+        ns = (C.c_int64 * self.n)(*counts)
+        self._call("process_dev", pi, po, ns)
 
 
 class SampleSinkFifo(_Handle):
