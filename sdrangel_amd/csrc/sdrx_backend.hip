@@ -139,6 +139,11 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
             set_error("sdrx_backend_create: bad channel configuration (need out_rate <= in_rate, taps_per_phase*16 <= 256)");
             return SDRX_EINVAL;
         }
+        // Interpolator::create takes (int)(taps_per_phase * 16) taps per phase: none at all leaves an empty tap vector
+        if ((int)((double)k.taps_per_phase * 16) < 1) {
+            set_error("sdrx_backend_create: taps_per_phase too small (need (int)(taps_per_phase * 16) >= 1)");
+            return SDRX_EINVAL;
+        }
     }
     sdrx_backend* b = new (std::nothrow) sdrx_backend;
     if (!b) return SDRX_ENOMEM;

@@ -126,6 +126,24 @@ def test_round2_entry_points_refuse_bad_arguments_and_take_empty_calls():
         h.close()
 
 
+def test_backend_refuses_a_design_without_taps():
+    """(int)(taps_per_phase * 16) == 0: Interpolator::create would leave an empty tap vector and the design a zero sum"""
+    L = sa.lib()
+    p = C.c_void_p()
+    good = dict(in_rate=60000, nco_freq=100, out_rate=48000, interp_cutoff=5000.0, taps_per_phase=0.0625, filt_mode=0, f1=0.0, f2=0.0,
+                discri=0, fm_scaling=1.0)
+    for tpp in (0.05, 0.0624, 1e-30):
+        bad = (sa.BackendCfg * 2)(sa.BackendCfg(**good), sa.BackendCfg(**dict(good, taps_per_phase=tpp)))
+        assert L.sdrx_backend_create(C.byref(p), 0, 2, bad) == -1 and not p.value, tpp      # SDRX_EINVAL
+        assert b"taps_per_phase" in L.sdrx_last_error(), tpp
+    for tpp in (0.0, -1.0, 16.01):
+        bad = (sa.BackendCfg * 1)(sa.BackendCfg(**dict(good, taps_per_phase=tpp)))
+        assert L.sdrx_backend_create(C.byref(p), 0, 1, bad) == -1 and b"taps_per_phase" in L.sdrx_last_error(), tpp
+    b = sa.BackendBank([sa.BackendCfg(**good)])               # one tap, made two: the smallest design there is
+    assert b.design(0)[0] == 2
+    b.close()
+
+
 def test_checkpoints_of_bank_and_float_decimators():
     """get_state / set_state: a fresh object that is given the state continues exactly where the first one was"""
     L = sa.lib()
