@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "am_scan.hpp"
 #include "demod_psum.hpp"
+#include "demod_wg.hpp"
 #include "dsp_device.hpp"
 
 namespace sdrx {
@@ -79,12 +80,7 @@ void am_level_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
         b.root[i] = sqrtf(m);                           // the correctly rounded expansion (IEEE sqrt is the build default)
         b.dterm[i] = am_ma_term(m, old);
     }
-    sums[tid] = (double)m; peaks[tid] = m;
-    __syncthreads();
-    for (int st = 128; st; st >>= 1) {
-        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmaxf(peaks[tid], peaks[tid + st]); }
-        __syncthreads();
-    }
+    wg_level_reduce(sums, peaks, tid, (double)m, m);
     if (tid == 0) { b.blk_sum[blockIdx.x] = sums[0]; b.blk_peak[blockIdx.x] = peaks[0]; }
 }
 
@@ -94,6 +90,8 @@ constexpr int AM_PS_CH = PS_CH;
 __global__ __launch_bounds__(64)
 void am_psum_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs, int n_ch, int which)
 {
+    // psum_rows called directly, not through psum_channels as in the other families: with the wrapper this kernel ran 3 % longer
+    // (2.13 against 2.07 ms per launch) and the AM feed 1.8 % over the parent's slowest run, though its loop kept its instructions (experiments/README.md)
     const int lane = threadIdx.x, c = blockIdx.x * AM_PS_CH + lane;
     const bool chain = lane < AM_PS_CH && c < n_ch;
     const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(256)
 void am_gate_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
 {
     __shared__ WfmClamp wmap[4];
-    __shared__ int wact[4], wfed[4];
+    __shared__ int2 wcnt[4];                                // open, fed
     __shared__ double sums[256];
     __shared__ float peaks[256];
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -122,28 +120,18 @@ void am_gate_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
     const int n = s.n, cap = s.H, D = s.D, rate = s.rate;
     const float level = s.level;
     const bool mute = s.mute != 0;
+    const WfmClampOps sq{cap};
     int carry = s.count, nact = 0, nfed = 0;
     for (int base = 0; base < n; base += 1024) {
         const int i0 = base + tid * 4;
         bool up[4];
-        WfmClamp m = wfm_identity(cap);
+        WfmClamp m = sq.identity();
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             up[k] = false;
             if (i0 + k < n) { up[k] = am_up(b.tot[i0 + k], level); m = wfm_compose(m, wfm_step(up[k], cap)); }
         }
-        WfmClamp incl = m;                                  // wfm_wave_scan, written out: the call compiles to other code here
-        for (int o = 1; o < 64; o *= 2) {
-            const WfmClamp t = wfm_shfl_up(incl, o);
-            if (lane >= o) incl = wfm_compose(t, incl);
-        }
-        if (lane == 63) wmap[w] = incl;
-        __syncthreads();
-        WfmClamp pre = wfm_identity(cap);
-        for (int q = 0; q < w; q++) pre = wfm_compose(pre, wmap[q]);
-        WfmClamp ex = wfm_shfl_up(incl, 1);
-        if (lane == 0) ex = wfm_identity(cap);
-        int st = wfm_apply(wfm_compose(pre, ex), carry);
+        int st = wfm_apply(wg_scan(sq, m, lane, w, wmap), carry);
         int stv[4]; bool act[4], fed[4]; float rr[4];
         int a_loc = 0, f_loc = 0;
 #pragma unroll
@@ -159,15 +147,8 @@ void am_gate_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
                 a_loc += act[k]; f_loc += fed[k];
             }
         }
-        int a_inc = a_loc, f_inc = f_loc;
-        for (int o = 1; o < 64; o *= 2) {
-            const int ta = __shfl_up(a_inc, o, 64), tf = __shfl_up(f_inc, o, 64);
-            if (lane >= o) { a_inc += ta; f_inc += tf; }
-        }
-        if (lane == 63) { wact[w] = a_inc; wfed[w] = f_inc; }
-        __syncthreads();
-        int a_ex = nact + a_inc - a_loc, f_ex = nfed + f_inc - f_loc;
-        for (int q = 0; q < w; q++) { a_ex += wact[q]; f_ex += wfed[q]; }
+        const int2 incl = wg_scan_incl(WgCount2{}, make_int2(a_loc, f_loc), lane, w, wcnt);
+        int a_ex = nact + incl.x - a_loc, f_ex = nfed + incl.y - f_loc;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if (i0 + k < n) {
@@ -177,22 +158,14 @@ void am_gate_kernel(AmChan* __restrict__ ch, const AmBufs* __restrict__ bufs)
                 b.fcnt[i0 + k] = f_ex;
             }
         }
-        WfmClamp all = wmap[0];
-        for (int q = 1; q < 4; q++) all = wfm_compose(all, wmap[q]);
-        carry = wfm_apply(all, carry);
-        for (int q = 0; q < 4; q++) { nact += wact[q]; nfed += wfed[q]; }
-        __syncthreads();                                    // wmap / wact / wfed are rewritten by the next trip
+        carry = wfm_apply(wg_total(sq, wmap), carry);
+        const int2 all = wg_total(WgCount2{}, wcnt);
+        nact += all.x; nfed += all.y;
+        __syncthreads();                                    // wmap / wcnt are rewritten by the next trip
     }
     // level accumulators: the 256-sample partials of am_level_kernel, in a fixed order
-    const int nblk = (n + 255) / 256;
-    double ps = 0.0; float pk = 0.0f;
-    for (int j = tid; j < nblk; j += 256) { ps += b.blk_sum[j]; pk = fmaxf(pk, b.blk_peak[j]); }
-    sums[tid] = ps; peaks[tid] = pk;
-    __syncthreads();                                        // also: every vnew of this feed is written
-    for (int st = 128; st; st >>= 1) {
-        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmaxf(peaks[tid], peaks[tid + st]); }
-        __syncthreads();
-    }
+    // (its barriers also: every vnew of this feed is written)
+    wg_level_gather(sums, peaks, tid, (n + 255) / 256, b.blk_sum, b.blk_peak);
     const int H = s.H;
     for (int j = tid; j < nfed; j += 256) b.uterm[j] = am_agc_term(b.vnew[j], am_stream_at(b.vhist, H, (const double*)b.vnew, (long)j - H));
     if (tid == 0) {

@@ -58,4 +58,23 @@ __device__ __forceinline__ double psum_rows(int lane, bool chain, Row row)
     return acc;
 }
 
+// What a psum kernel is (one wave of 64 per PS_CH channels, grid = the channel count rounded up): for channel c, row_of(c) names
+// the terms, where the sums go, their number, the carried sum, and where the sum after the last term goes.  am_psum_kernel
+// spells this out instead; am_kernels.hpp says why.
+struct PsumRow { const double* term; double* out; int n; double sum; double* next; };
+template <class RowOf>
+__device__ __forceinline__ void psum_channels(int n_ch, RowOf row_of)
+{
+    const int lane = threadIdx.x, c = blockIdx.x * PS_CH + lane;
+    const bool chain = lane < PS_CH && c < n_ch;
+    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
+        // rows past the last channel: its pointers, no terms.  The count and the carried sum are loaded for those rows too (valid
+        // memory, the index is clamped) and dropped; the row is named again below for `next` alone
+        const PsumRow r = row_of(min(c, n_ch - 1));
+        term = r.term; out = r.out;
+        if (chain) { n_mine = r.n; sum = r.sum; }
+    });
+    if (chain) *row_of(c).next = acc;
+}
+
 } // namespace sdrx

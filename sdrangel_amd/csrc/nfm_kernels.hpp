@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "nfm_scan.hpp"
 #include "demod_psum.hpp"
+#include "demod_wg.hpp"
 #include "dsp_device.hpp"
 #include "gfft_kernel.hpp"              // atan2_approx2
 
@@ -79,12 +80,7 @@ void nfm_level_kernel(NfmChan* __restrict__ ch, const NfmBufs* __restrict__ bufs
         b.wraw[i] = nfm_demod(atan2_approx2(v.y, v.x), prev, s.fm_scaling) * s.comp;
         b.dterm[i] = am_ma_term(m, old);
     }
-    sums[tid] = (double)m; peaks[tid] = m;
-    __syncthreads();
-    for (int st = 128; st; st >>= 1) {
-        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmaxf(peaks[tid], peaks[tid + st]); }
-        __syncthreads();
-    }
+    wg_level_reduce(sums, peaks, tid, (double)m, m);
     if (tid == 0) { b.blk_sum[blockIdx.x] = sums[0]; b.blk_peak[blockIdx.x] = peaks[0]; }
 }
 
@@ -92,14 +88,7 @@ void nfm_level_kernel(NfmChan* __restrict__ ch, const NfmBufs* __restrict__ bufs
 __global__ __launch_bounds__(64)
 void nfm_psum_kernel(NfmChan* __restrict__ ch, const NfmBufs* __restrict__ bufs, int n_ch)
 {
-    const int lane = threadIdx.x, c = blockIdx.x * PS_CH + lane;
-    const bool chain = lane < PS_CH && c < n_ch;
-    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
-        const int cc = min(c, n_ch - 1);                    // rows past the last channel: its pointers, no terms
-        term = bufs[cc].dterm; out = bufs[cc].tot;
-        if (chain) { n_mine = ch[cc].n; sum = ch[cc].total; }
-    });
-    if (chain) ch[c].total_next = acc;
+    psum_channels(n_ch, [&](int c) { return PsumRow{bufs[c].dterm, bufs[c].tot, ch[c].n, ch[c].total, &ch[c].total_next}; });
 }
 
 // what the delay line holds for stream index j of this feed (j < 0: the carried history)
@@ -124,11 +113,12 @@ void nfm_gate_kernel(NfmChan* __restrict__ ch, const NfmBufs* __restrict__ bufs)
     const int n = s.n, gate = s.gate, cap = 2 * s.gate, D = s.D;
     const float level = s.level;
     const bool mute = s.mute != 0;
+    const WfmClampOps sq{cap};
     int carry = s.count, nact = 0;
     for (int base = 0; base < n; base += 1024) {
         const int i0 = base + tid * 4;
         bool up[4];
-        WfmClamp m = wfm_identity(cap);
+        WfmClamp m = sq.identity();
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             up[k] = false;
@@ -138,18 +128,7 @@ void nfm_gate_kernel(NfmChan* __restrict__ ch, const NfmBufs* __restrict__ bufs)
                 b.w[i0 + k] = up[k] ? b.wraw[i0 + k] : 0.0f;
             }
         }
-        WfmClamp incl = m;
-        for (int o = 1; o < 64; o *= 2) {
-            const WfmClamp t = wfm_shfl_up(incl, o);
-            if (lane >= o) incl = wfm_compose(t, incl);
-        }
-        if (lane == 63) wmap[w] = incl;
-        __syncthreads();
-        WfmClamp pre = wfm_identity(cap);
-        for (int q = 0; q < w; q++) pre = wfm_compose(pre, wmap[q]);
-        WfmClamp ex = wfm_shfl_up(incl, 1);
-        if (lane == 0) ex = wfm_identity(cap);
-        int st = wfm_apply(wfm_compose(pre, ex), carry);
+        int st = wfm_apply(wg_scan(sq, m, lane, w, wmap), carry);
         bool act[4];
         int a_loc = 0;
 #pragma unroll
@@ -161,15 +140,7 @@ void nfm_gate_kernel(NfmChan* __restrict__ ch, const NfmBufs* __restrict__ bufs)
                 a_loc += act[k];
             }
         }
-        int a_inc = a_loc;
-        for (int o = 1; o < 64; o *= 2) {
-            const int ta = __shfl_up(a_inc, o, 64);
-            if (lane >= o) a_inc += ta;
-        }
-        if (lane == 63) wact[w] = a_inc;
-        __syncthreads();
-        int a_ex = nact + a_inc - a_loc;
-        for (int q = 0; q < w; q++) a_ex += wact[q];
+        int a_ex = nact + wg_scan_incl(WgCount{}, a_loc, lane, w, wact) - a_loc;
         if (lane == 0 && i0 < n) b.blk_a[i0 >> 8] = a_ex;   // i0 is a multiple of 256 here
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -178,22 +149,12 @@ void nfm_gate_kernel(NfmChan* __restrict__ ch, const NfmBufs* __restrict__ bufs)
                 if (act[k]) b.x[a_ex++] = nfm_w_at(b, D, level, (long)(i0 + k) - D);
             }
         }
-        WfmClamp all = wmap[0];
-        for (int q = 1; q < 4; q++) all = wfm_compose(all, wmap[q]);
-        carry = wfm_apply(all, carry);
-        for (int q = 0; q < 4; q++) nact += wact[q];
+        carry = wfm_apply(wg_total(sq, wmap), carry);
+        nact += wg_total(WgCount{}, wact);
         __syncthreads();                                    // wmap / wact are rewritten by the next trip
     }
     // level accumulators: the 256-sample partials of nfm_level_kernel, in a fixed order
-    const int nblk = (n + 255) / 256;
-    double ps = 0.0; float pk = 0.0f;
-    for (int j = tid; j < nblk; j += 256) { ps += b.blk_sum[j]; pk = fmaxf(pk, b.blk_peak[j]); }
-    sums[tid] = ps; peaks[tid] = pk;
-    __syncthreads();
-    for (int st = 128; st; st >>= 1) {
-        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmaxf(peaks[tid], peaks[tid + st]); }
-        __syncthreads();
-    }
+    wg_level_gather(sums, peaks, tid, (n + 255) / 256, b.blk_sum, b.blk_peak);
     if (tid == 0) {
         s.n_act = nact;
         if (n > 0) {

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "ssb_scan.hpp"
 #include "demod_psum.hpp"
+#include "demod_wg.hpp"
 #include "dsp_device.hpp"
 
 namespace sdrx {
@@ -91,12 +92,7 @@ void ssb_level_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs
         reinterpret_cast<short2*>(b.spec)[i] = make_short2((short)re, (short)im);
         if (i == ncl - 1) s.magsq = m;
     }
-    sums[tid] = m; peaks[tid] = m;
-    __syncthreads();
-    for (int st = 128; st; st >>= 1) {
-        if (tid < st) { sums[tid] += sums[tid + st]; peaks[tid] = fmax(peaks[tid], peaks[tid + st]); }
-        __syncthreads();
-    }
+    wg_level_reduce(sums, peaks, tid, m, m);
     if (tid == 0) { b.blk_sum[blockIdx.x] = sums[0]; b.blk_peak[blockIdx.x] = peaks[0]; }
 }
 
@@ -104,24 +100,16 @@ void ssb_level_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs
 __global__ __launch_bounds__(64)
 void ssb_psum_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs, int n_ch)
 {
-    const int lane = threadIdx.x, c = blockIdx.x * PS_CH + lane;
-    const bool chain = lane < PS_CH && c < n_ch;
-    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
-        const int cc = min(c, n_ch - 1);                    // rows past the last channel: its pointers, no terms
-        term = bufs[cc].dterm; out = bufs[cc].tot;
-        if (chain) { n_mine = ch[cc].agc ? ch[cc].n : 0; sum = ch[cc].total; }
-    });
-    if (chain) ch[c].total_next = acc;
+    psum_channels(n_ch, [&](int c) { return PsumRow{bufs[c].dterm, bufs[c].tot, ch[c].agc ? ch[c].n : 0, ch[c].total, &ch[c].total_next}; });
 }
 
-// ---- 3. one workgroup per channel, 1024 samples per trip, four consecutive samples per lane: m_u0, the gate counter, m_count
-// and the step pair as three scans in a row (wave scan by shuffles, the four wave totals through LDS), the factor, the
-// delay-line write and getStepValue() per sample; then the level accumulators
+// ---- 3. one workgroup per channel, 1024 samples per trip, four consecutive samples per lane: the gate counter, m_count and the
+// step pair (magagc_trip, ssb_scan.hpp), m_u0, the factor, the delay-line write and getStepValue() per sample; then the level
+// accumulators
 __global__ __launch_bounds__(256)
 void ssb_gate_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs)
 {
-    __shared__ WfmClamp gmap[4], cmap[4];
-    __shared__ SsbPair pmap[4];
+    __shared__ MagAgcSlots slots;
     __shared__ double sums[256];
     __shared__ double peaks[256];
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -146,103 +134,21 @@ void ssb_gate_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs)
             b.sv[i] = svc;
         }
     } else {
-        for (int base = 0; base < n; base += 1024) {
-            const int i0 = base + tid * 4;
-            bool above[4], rst[4], up[4];
-            double magsq[4];
-            WfmClamp gm = wfm_identity(gate);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                above[k] = false; magsq[k] = 0.0;
-                if (i0 + k < n) {
-                    magsq[k] = (double)b.pw[i0 + k];
-                    above[k] = magsq[k] > thr;
-                    gm = wfm_compose(gm, ssb_gate_step(above[k], gate));
-                }
-            }
-            // a. gate counter
-            WfmClamp gi = wfm_wave_scan(gm, lane);
-            if (lane == 63) gmap[w] = gi;
-            __syncthreads();
-            WfmClamp pre = wfm_identity(gate);
-            for (int q = 0; q < w; q++) pre = wfm_compose(pre, gmap[q]);
-            WfmClamp ex = wfm_shfl_up(gi, 1);
-            if (lane == 0) ex = wfm_identity(gate);
-            int g = wfm_apply(wfm_compose(pre, ex), st.g);
-            WfmClamp all = gmap[0];
-            for (int q = 1; q < 4; q++) all = wfm_compose(all, gmap[q]);
-            st.g = wfm_apply(all, st.g);
-            WfmClamp cm = wfm_identity(hn);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                rst[k] = false;
-                if (i0 + k < n) {
-                    rst[k] = ssb_reset(above[k], g, gate);
-                    g = wfm_apply(ssb_gate_step(above[k], gate), g);
-                    cm = wfm_compose(cm, ssb_count_step(rst[k], above[k], hn));
-                }
-            }
-            // b. m_count
-            WfmClamp ci = wfm_wave_scan(cm, lane);
-            if (lane == 63) cmap[w] = ci;
-            __syncthreads();
-            pre = wfm_identity(hn);
-            for (int q = 0; q < w; q++) pre = wfm_compose(pre, cmap[q]);
-            ex = wfm_shfl_up(ci, 1);
-            if (lane == 0) ex = wfm_identity(hn);
-            int cnt = wfm_apply(wfm_compose(pre, ex), st.count);
-            all = cmap[0];
-            for (int q = 1; q < 4; q++) all = wfm_compose(all, cmap[q]);
-            st.count = wfm_apply(all, st.count);
-            SsbPair pm = ssb_pair_identity(L);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                up[k] = false;
-                if (i0 + k < n) {
-                    cnt = wfm_apply(ssb_count_step(rst[k], above[k], hn), cnt);
-                    up[k] = ssb_up(cnt, hn);
-                    pm = ssb_pair_compose(pm, ssb_pair_step(up[k], L));
-                }
-            }
-            // c. the step pair
-            SsbPair pi = ssb_pair_wave_scan(pm, lane);
-            if (lane == 63) pmap[w] = pi;
-            __syncthreads();
-            SsbPair ppre = ssb_pair_identity(L);
-            for (int q = 0; q < w; q++) ppre = ssb_pair_compose(ppre, pmap[q]);
-            SsbPair pex = ssb_pair_shfl_up(pi, 1);
-            if (lane == 0) pex = ssb_pair_identity(L);
-            SsbUD ud = ssb_pair_apply(ssb_pair_compose(ppre, pex), st.ud);
-            SsbPair pall = pmap[0];
-            for (int q = 1; q < 4; q++) pall = ssb_pair_compose(pall, pmap[q]);
-            st.ud = ssb_pair_apply(pall, st.ud);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (i0 + k < n) {
-                    const SsbUD was = ud;
-                    ud = ssb_pair_apply(ssb_pair_step(up[k], L), ud);
-                    const double u0 = ssb_u0(magsq[k], b.tot[i0 + k], hn, clamping);
-                    const float a = (float)ssb_agc_value(up[k], was, ud, L, sd, u0);
-                    const float2 v = b.s[i0 + k];
-                    b.w[i0 + k] = make_float2(v.x * a, v.y * a);
-                    b.sv[i0 + k] = ssb_step_value(up[k], ud, sd);
-                    if (i0 + k == n - 1) s.u0 = u0;
-                }
-            }
-            // no barrier here: each of gmap, cmap and pmap is read between its own barrier and the next one, and two
-            // barriers lie between those reads and the next trip's write of the same array
-        }
+        for (int base = 0; base < n; base += 1024)
+            magagc_trip(st, slots, base + tid * 4, n, lane, w, gate, hn, L, thr,
+                [&](int i) { return (double)b.pw[i]; },
+                [&](int i, bool up, SsbUD was, SsbUD ud, double magsq) {
+                    const double u0 = ssb_u0(magsq, b.tot[i], hn, clamping);
+                    const float a = (float)ssb_agc_value(up, was, ud, L, sd, u0);
+                    const float2 v = b.s[i];
+                    b.w[i] = make_float2(v.x * a, v.y * a);
+                    b.sv[i] = ssb_step_value(up, ud, sd);
+                    if (i == n - 1) s.u0 = u0;
+                });
     }
     // level accumulators: the 256-group partials of ssb_level_kernel, in a fixed order
-    const int ncl = s.n_spec, nblk = (ncl + 255) / 256;
-    double ps = 0.0, pk = 0.0;
-    for (int j = tid; j < nblk; j += 256) { ps += b.blk_sum[j]; pk = fmax(pk, b.blk_peak[j]); }
-    sums[tid] = ps; peaks[tid] = pk;
-    __syncthreads();
-    for (int k = 128; k; k >>= 1) {
-        if (tid < k) { sums[tid] += sums[tid + k]; peaks[tid] = fmax(peaks[tid], peaks[tid + k]); }
-        __syncthreads();
-    }
+    const int ncl = s.n_spec;
+    wg_level_gather(sums, peaks, tid, (ncl + 255) / 256, b.blk_sum, b.blk_peak);
     if (tid == 0) {
         s.g = st.g; s.count = st.count; s.U = st.ud.U; s.Dn = st.ud.D;
         if (ncl > 0) {

@@ -31,6 +31,9 @@
 //    names is m_currentIndex itself: for hn >= 96000 x[j] = w[j - 1] (ssb_delay), as NFM's line does at its size.
 #pragma once
 #include "am_scan.hpp"
+#if defined(__HIPCC__)
+#include "demod_wg.hpp"                   // wg_scan, for magagc_trip at the end
+#endif
 
 namespace sdrx {
 
@@ -133,13 +136,76 @@ __device__ __forceinline__ SsbPair ssb_pair_shfl_up(SsbPair m, int o)
     SsbPair r; r.sel = __shfl_up(m.sel, o, 64); r.u = wfm_shfl_up(m.u, o); r.d = wfm_shfl_up(m.d, o);
     return r;
 }
-__device__ __forceinline__ SsbPair ssb_pair_wave_scan(SsbPair m, int lane)   // inclusive, in lane order
+struct SsbPairOps {                                         // for wg_scan (demod_wg.hpp)
+    using Map = SsbPair;
+    int L;
+    __device__ __forceinline__ SsbPair identity() const { return ssb_pair_identity(L); }
+    __device__ __forceinline__ SsbPair compose(SsbPair f, SsbPair g) const { return ssb_pair_compose(f, g); }
+    __device__ __forceinline__ SsbPair shfl_up(SsbPair m, int o) const { return ssb_pair_shfl_up(m, o); }
+};
+
+// ---- one 1024-sample trip of the three counter scans (4a-c) over a workgroup of 256 lanes, four consecutive samples per lane:
+// ssb_gate_kernel's and udp_agc_kernel's.  Three wg_scans in a row on three slot arrays, no barrier of its own (demod_wg.hpp).
+struct MagAgcSlots { WfmClamp g[4], c[4]; SsbPair p[4]; };  // __shared__, one per kernel
+
+// Samples i0 .. i0 + 3 of this lane (those below n), the workgroup's lanes in stream order.  cap: where m_count stops (the step-down
+// delay); magsq_at(i): m_magsq of sample i; sink(i, up, was, now, magsq): the pair before and after sample i's step.  st goes
+// from the counters before the trip's first sample to those after its last, in every lane.
+template <class Load, class Sink>
+__device__ __forceinline__ void magagc_trip(SsbCounters& st, MagAgcSlots& slots, int i0, int n, int lane, int w, int gate, int cap, int L,
+                                            double thr, Load magsq_at, Sink sink)
 {
-    for (int o = 1; o < 64; o *= 2) {
-        const SsbPair t = ssb_pair_shfl_up(m, o);
-        if (lane >= o) m = ssb_pair_compose(t, m);
+    const WfmClampOps gop{gate}, cop{cap};
+    const SsbPairOps pop{L};
+    bool above[4], rst[4], up[4];
+    double magsq[4];
+    WfmClamp gm = gop.identity();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        above[k] = false; magsq[k] = 0.0;
+        if (i0 + k < n) {
+            magsq[k] = magsq_at(i0 + k);
+            above[k] = magsq[k] > thr;
+            gm = wfm_compose(gm, ssb_gate_step(above[k], gate));
+        }
     }
-    return m;
+    // a. gate counter
+    int g = wfm_apply(wg_scan(gop, gm, lane, w, slots.g), st.g);
+    st.g = wfm_apply(wg_total(gop, slots.g), st.g);
+    WfmClamp cm = cop.identity();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        rst[k] = false;
+        if (i0 + k < n) {
+            rst[k] = ssb_reset(above[k], g, gate);
+            g = wfm_apply(ssb_gate_step(above[k], gate), g);
+            cm = wfm_compose(cm, ssb_count_step(rst[k], above[k], cap));
+        }
+    }
+    // b. m_count
+    int cnt = wfm_apply(wg_scan(cop, cm, lane, w, slots.c), st.count);
+    st.count = wfm_apply(wg_total(cop, slots.c), st.count);
+    SsbPair pm = pop.identity();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        up[k] = false;
+        if (i0 + k < n) {
+            cnt = wfm_apply(ssb_count_step(rst[k], above[k], cap), cnt);
+            up[k] = ssb_up(cnt, cap);
+            pm = ssb_pair_compose(pm, ssb_pair_step(up[k], L));
+        }
+    }
+    // c. the step pair
+    SsbUD ud = ssb_pair_apply(wg_scan(pop, pm, lane, w, slots.p), st.ud);
+    st.ud = ssb_pair_apply(wg_total(pop, slots.p), st.ud);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (i0 + k < n) {
+            const SsbUD was = ud;
+            ud = ssb_pair_apply(ssb_pair_step(up[k], L), ud);
+            sink(i0 + k, up[k], was, ud, magsq[k]);
+        }
+    }
 }
 #endif
 

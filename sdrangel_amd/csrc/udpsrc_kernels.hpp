@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include "udpsrc_scan.hpp"
 #include "demod_psum.hpp"
+#include "demod_wg.hpp"
 
 namespace sdrx {
 
@@ -97,38 +98,23 @@ void udp_level_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs
 __global__ __launch_bounds__(64)
 void udp_psum_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs, int n_ch)
 {
-    const int lane = threadIdx.x, c = blockIdx.x * PS_CH + lane;
-    const bool chain = lane < PS_CH && c < n_ch;
-    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
-        const int cc = min(c, n_ch - 1);                    // rows past the last channel: its pointers, no terms
-        term = bufs[cc].dterm; out = bufs[cc].tot;
-        if (chain) { n_mine = ch[cc].n; sum = ch[cc].in_sum; }
-    });
-    if (chain) ch[c].in_sum_next = acc;
+    psum_channels(n_ch, [&](int c) { return PsumRow{bufs[c].dterm, bufs[c].tot, ch[c].n, ch[c].in_sum, &ch[c].in_sum_next}; });
 }
 
 // ---- 2a. AGC on: the history's sum after every sample (psum_rows); the other channels have no terms
 __global__ __launch_bounds__(64)
 void udp_agcpsum_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs, int n_ch)
 {
-    const int lane = threadIdx.x, c = blockIdx.x * PS_CH + lane;
-    const bool chain = lane < PS_CH && c < n_ch;
-    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
-        const int cc = min(c, n_ch - 1);
-        term = bufs[cc].gterm; out = bufs[cc].gtot;
-        if (chain) { n_mine = ch[cc].agc ? ch[cc].n : 0; sum = ch[cc].agc_sum; }
-    });
-    if (chain) ch[c].agc_sum_next = acc;
+    psum_channels(n_ch, [&](int c) { return PsumRow{bufs[c].gterm, bufs[c].gtot, ch[c].agc ? ch[c].n : 0, ch[c].agc_sum, &ch[c].agc_sum_next}; });
 }
 
 // ---- 2b. AGC on: one workgroup per channel, 1024 samples per trip, four consecutive samples per lane: the gate counter, m_count
-// and the step pair as three scans in a row (ssb_scan.hpp's maps; wave scan by shuffles, the four wave totals through LDS), then
-// m_u0 and the factor feedAndGetValue returns, left in gterm
+// (capped at the step-down delay) and the step pair (magagc_trip, ssb_scan.hpp), then m_u0 and the factor feedAndGetValue
+// returns, left in gterm
 __global__ __launch_bounds__(256)
 void udp_agc_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs)
 {
-    __shared__ WfmClamp gmap[4], cmap[4];
-    __shared__ SsbPair pmap[4];
+    __shared__ MagAgcSlots slots;
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     UdpChan& s = ch[c];
     if (!s.agc) return;
@@ -136,89 +122,13 @@ void udp_agc_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs)
     const int n = s.n, hn = s.a_hn, L = s.a_L, sdd = s.a_sdd, gate = s.a_gate;
     const double thr = s.a_thr, sd = 1.0 / (double)L;
     SsbCounters st; st.g = s.a_g; st.count = s.a_count; st.ud.U = s.a_U; st.ud.D = s.a_D;
-    for (int base = 0; base < n; base += 1024) {
-        const int i0 = base + tid * 4;
-        bool above[4], rst[4], up[4];
-        double magsq[4];
-        WfmClamp gm = wfm_identity(gate);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            above[k] = false; magsq[k] = 0.0;
-            if (i0 + k < n) {
-                const float2 v = b.ci[i0 + k];
-                magsq[k] = (double)(v.x * v.x + v.y * v.y);
-                above[k] = magsq[k] > thr;
-                gm = wfm_compose(gm, ssb_gate_step(above[k], gate));
-            }
-        }
-        // a. gate counter
-        WfmClamp gi = wfm_wave_scan(gm, lane);
-        if (lane == 63) gmap[w] = gi;
-        __syncthreads();
-        WfmClamp pre = wfm_identity(gate);
-        for (int q = 0; q < w; q++) pre = wfm_compose(pre, gmap[q]);
-        WfmClamp ex = wfm_shfl_up(gi, 1);
-        if (lane == 0) ex = wfm_identity(gate);
-        int g = wfm_apply(wfm_compose(pre, ex), st.g);
-        WfmClamp all = gmap[0];
-        for (int q = 1; q < 4; q++) all = wfm_compose(all, gmap[q]);
-        st.g = wfm_apply(all, st.g);
-        WfmClamp cm = wfm_identity(sdd);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            rst[k] = false;
-            if (i0 + k < n) {
-                rst[k] = ssb_reset(above[k], g, gate);
-                g = wfm_apply(ssb_gate_step(above[k], gate), g);
-                cm = wfm_compose(cm, ssb_count_step(rst[k], above[k], sdd));
-            }
-        }
-        // b. m_count, capped at the step-down delay
-        WfmClamp ci = wfm_wave_scan(cm, lane);
-        if (lane == 63) cmap[w] = ci;
-        __syncthreads();
-        pre = wfm_identity(sdd);
-        for (int q = 0; q < w; q++) pre = wfm_compose(pre, cmap[q]);
-        ex = wfm_shfl_up(ci, 1);
-        if (lane == 0) ex = wfm_identity(sdd);
-        int cnt = wfm_apply(wfm_compose(pre, ex), st.count);
-        all = cmap[0];
-        for (int q = 1; q < 4; q++) all = wfm_compose(all, cmap[q]);
-        st.count = wfm_apply(all, st.count);
-        SsbPair pm = ssb_pair_identity(L);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            up[k] = false;
-            if (i0 + k < n) {
-                cnt = wfm_apply(ssb_count_step(rst[k], above[k], sdd), cnt);
-                up[k] = ssb_up(cnt, sdd);
-                pm = ssb_pair_compose(pm, ssb_pair_step(up[k], L));
-            }
-        }
-        // c. the step pair
-        SsbPair pi = ssb_pair_wave_scan(pm, lane);
-        if (lane == 63) pmap[w] = pi;
-        __syncthreads();
-        SsbPair ppre = ssb_pair_identity(L);
-        for (int q = 0; q < w; q++) ppre = ssb_pair_compose(ppre, pmap[q]);
-        SsbPair pex = ssb_pair_shfl_up(pi, 1);
-        if (lane == 0) pex = ssb_pair_identity(L);
-        SsbUD ud = ssb_pair_apply(ssb_pair_compose(ppre, pex), st.ud);
-        SsbPair pall = pmap[0];
-        for (int q = 1; q < 4; q++) pall = ssb_pair_compose(pall, pmap[q]);
-        st.ud = ssb_pair_apply(pall, st.ud);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (i0 + k < n) {
-                const SsbUD was = ud;
-                ud = ssb_pair_apply(ssb_pair_step(up[k], L), ud);
-                const double u0 = udp_agc_u0(magsq[k], b.gtot[i0 + k], hn);
-                b.gterm[i0 + k] = ssb_agc_value(up[k], was, ud, L, sd, u0);
-            }
-        }
-        // no barrier here: each of gmap, cmap and pmap is read between its own barrier and the next one, and two barriers lie
-        // between those reads and the next trip's write of the same array
-    }
+    for (int base = 0; base < n; base += 1024)
+        magagc_trip(st, slots, base + tid * 4, n, lane, w, gate, sdd, L, thr,
+            [&](int i) { const float2 v = b.ci[i]; return (double)(v.x * v.x + v.y * v.y); },
+            [&](int i, bool up, SsbUD was, SsbUD ud, double magsq) {
+                const double u0 = udp_agc_u0(magsq, b.gtot[i], hn);
+                b.gterm[i] = ssb_agc_value(up, was, ud, L, sd, u0);
+            });
     if (tid == 0) { s.a_g = st.g; s.a_count = st.count; s.a_U = st.ud.U; s.a_D = st.ud.D; }
 }
 
@@ -235,11 +145,12 @@ void udp_gate_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs)
     const int n = s.n, G = s.gate, top = s.top, win = s.w_in, fmt = s.fmt;
     const bool enabled = s.sq_enabled != 0, nfm = udp_fmt_nfm(fmt), amx = udp_fmt_amx(fmt);
     const double level = s.level;
+    const UdpSqOps sq{top};
     int carry = s.pos, nact = 0;
     for (int base = 0; base < n; base += 1024) {
         const int i0 = base + tid * 4;
         bool up[4];
-        UdpSq m = udp_sq_identity(top);
+        UdpSq m = sq.identity();
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             up[k] = false;
@@ -248,18 +159,7 @@ void udp_gate_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs)
                 m = udp_sq_compose(m, udp_sq_map(up[k], G, top), top);
             }
         }
-        UdpSq incl = m;
-        for (int o = 1; o < 64; o *= 2) {
-            const UdpSq t = udp_sq_shfl_up(incl, o);
-            if (lane >= o) incl = udp_sq_compose(t, incl, top);
-        }
-        if (lane == 63) wmap[w] = incl;
-        __syncthreads();
-        UdpSq pre = udp_sq_identity(top);
-        for (int q = 0; q < w; q++) pre = udp_sq_compose(pre, wmap[q], top);
-        UdpSq ex = udp_sq_shfl_up(incl, 1);
-        if (lane == 0) ex = udp_sq_identity(top);
-        int st = udp_sq_apply(udp_sq_compose(pre, ex, top), carry);
+        int st = udp_sq_apply(wg_scan(sq, m, lane, w, wmap), carry);
         bool act[4];
         int a_loc = 0;
 #pragma unroll
@@ -271,15 +171,7 @@ void udp_gate_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs)
                 a_loc += act[k];
             }
         }
-        int a_inc = a_loc;
-        for (int o = 1; o < 64; o *= 2) {
-            const int ta = __shfl_up(a_inc, o, 64);
-            if (lane >= o) a_inc += ta;
-        }
-        if (lane == 63) wact[w] = a_inc;
-        __syncthreads();
-        int a_ex = nact + a_inc - a_loc;
-        for (int q = 0; q < w; q++) a_ex += wact[q];
+        int a_ex = nact + wg_scan_incl(WgCount{}, a_loc, lane, w, wact) - a_loc;
         if (lane == 0 && i0 < n) b.blk_a[i0 >> 8] = a_ex;   // i0 is a multiple of 256 here
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -292,10 +184,8 @@ void udp_gate_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs)
                 }
             }
         }
-        UdpSq all = wmap[0];
-        for (int q = 1; q < 4; q++) all = udp_sq_compose(all, wmap[q], top);
-        carry = udp_sq_apply(all, carry);
-        for (int q = 0; q < 4; q++) nact += wact[q];
+        carry = udp_sq_apply(wg_total(sq, wmap), carry);
+        nact += wg_total(WgCount{}, wact);
         __syncthreads();                                    // wmap / wact are rewritten by the next trip
     }
     if (tid == 0) {
@@ -321,14 +211,9 @@ void udp_amterm_kernel(const UdpChan* __restrict__ ch, const UdpBufs* __restrict
 __global__ __launch_bounds__(64)
 void udp_ampsum_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs, int n_ch)
 {
-    const int lane = threadIdx.x, c = blockIdx.x * PS_CH + lane;
-    const bool chain = lane < PS_CH && c < n_ch;
-    const double acc = psum_rows(lane, chain, [&](const double*& term, double*& out, int& n_mine, double& sum) {
-        const int cc = min(c, n_ch - 1);
-        term = bufs[cc].dterm; out = bufs[cc].tot;
-        if (chain) { n_mine = ch[cc].fmt == UDP_AM_NODC_MONO ? ch[cc].n_act : 0; sum = ch[cc].am_sum; }
+    psum_channels(n_ch, [&](int c) {
+        return PsumRow{bufs[c].dterm, bufs[c].tot, ch[c].fmt == UDP_AM_NODC_MONO ? ch[c].n_act : 0, ch[c].am_sum, &ch[c].am_sum_next};
     });
-    if (chain) ch[c].am_sum_next = acc;
 }
 
 // ---- 5. per sample: the format's payload sample; closed samples are 0.  The open samples of a block are consecutive in the

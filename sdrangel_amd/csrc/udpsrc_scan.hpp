@@ -186,6 +186,13 @@ __device__ __forceinline__ UdpSq udp_sq_shfl_up(UdpSq m, int o)
     r.a = __shfl_up(m.a, o, 64);
     return r;
 }
+struct UdpSqOps {                                           // for wg_scan (demod_wg.hpp)
+    using Map = UdpSq;
+    int top;
+    __device__ __forceinline__ UdpSq identity() const { return udp_sq_identity(top); }
+    __device__ __forceinline__ UdpSq compose(UdpSq f, UdpSq g) const { return udp_sq_compose(f, g, top); }
+    __device__ __forceinline__ UdpSq shfl_up(UdpSq m, int o) const { return udp_sq_shfl_up(m, o); }
+};
 #endif
 
 } // namespace sdrx

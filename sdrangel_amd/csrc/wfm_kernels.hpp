@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include "gfft_kernel.hpp"
 #include "wfm_scan.hpp"
+#include "demod_wg.hpp"
 #include "dsp_device.hpp"
 
 namespace sdrx {
@@ -275,7 +276,7 @@ void wfm_blockscan_kernel(WfmChan* __restrict__ ch, const WfmBufs* __restrict__ 
     for (int b0 = 0; b0 < nb; b0 += 64) {
         const int blk = b0 + lane;
         const bool in = blk < nb;
-        const WfmClamp m = wfm_wave_scan(in ? b.blk_map[blk] : wfm_identity(cap), lane);
+        const WfmClamp m = wg_wave_scan(WfmClampOps{cap}, in ? b.blk_map[blk] : wfm_identity(cap), lane);
         const int after = wfm_apply(m, carry);
         int before = __shfl_up(after, 1, 64);
         if (lane == 0) before = carry;
@@ -320,14 +321,7 @@ void wfm_demod_kernel(const WfmChan* __restrict__ ch, const WfmBufs* __restrict_
     if (tid == 0) first = -1;
     const int cap = s.cap;
     const WfmClamp m0 = wfm_step(f2.x != 0, cap), m1 = wfm_step(f2.y != 0, cap);
-    const WfmClamp incl = wfm_wave_scan(wfm_compose(m0, m1), lane);
-    if (lane == 63) wmap[w] = incl;
-    __syncthreads();
-    WfmClamp pre = wfm_identity(cap);
-    for (int q = 0; q < w; q++) pre = wfm_compose(pre, wmap[q]);
-    WfmClamp ex = wfm_shfl_up(incl, 1);
-    if (lane == 0) ex = wfm_identity(cap);
-    const int before = wfm_apply(wfm_compose(pre, ex), b.blk_state[blk]);
+    const int before = wfm_apply(wg_scan(WfmClampOps{cap}, wfm_compose(m0, m1), lane, w, wmap), b.blk_state[blk]);
     const int st0 = wfm_apply(m0, before), st1 = wfm_apply(m1, st0);
     const bool live = !s.mute;
     const bool open0 = live && (float)st0 > s.open_f, open1 = live && (float)st1 > s.open_f;   // m_squelchOpen && !m_audioMute

@@ -1,6 +1,6 @@
 // The two recurrences of WFMDemod::feed's per-sample loop (plugins/channelrx/demodwfm/wfmdemod.cpp:121-140) as
-// associative scan operators.  Compiles for the host too (tests/wfm_scan_check.cpp), no HIP header needed; the wave-wide
-// scan at the end is there for hipcc only.
+// associative scan operators.  Compiles for the host too (tests/wfm_scan_check.cpp), no HIP header needed; the shuffle and the
+// ops struct at the end are there for hipcc only (the scans that use them: demod_wg.hpp).
 //
 // 1. Squelch counter.  `if (magsq >= level) { if (state < rfBW / 10) state++; } else { if (state > 0) state--; }` with an
 //    int state compared against a float.  With H = the smallest integer that is not below the float bound (wfm_counter_cap),
@@ -54,14 +54,13 @@ __device__ __forceinline__ WfmClamp wfm_shfl_up(WfmClamp m, int o)
     WfmClamp r; r.a = __shfl_up(m.a, o, 64); r.lo = __shfl_up(m.lo, o, 64); r.hi = __shfl_up(m.hi, o, 64);
     return r;
 }
-__device__ __forceinline__ WfmClamp wfm_wave_scan(WfmClamp m, int lane)     // inclusive, in lane order
-{
-    for (int o = 1; o < 64; o *= 2) {
-        const WfmClamp t = wfm_shfl_up(m, o);
-        if (lane >= o) m = wfm_compose(t, m);
-    }
-    return m;
-}
+struct WfmClampOps {                                        // what wg_wave_scan / wg_scan (demod_wg.hpp) ask of a map type
+    using Map = WfmClamp;
+    int cap;
+    __device__ __forceinline__ WfmClamp identity() const { return wfm_identity(cap); }
+    __device__ __forceinline__ WfmClamp compose(WfmClamp f, WfmClamp g) const { return wfm_compose(f, g); }
+    __device__ __forceinline__ WfmClamp shfl_up(WfmClamp m, int o) const { return wfm_shfl_up(m, o); }
+};
 #endif
 
 } // namespace sdrx
