@@ -174,3 +174,15 @@ def test_checkpoints_of_bank_and_float_decimators():
     assert L.sdrx_fdecim_get_state(f1._h, fs.ctypes.data) == 0 and L.sdrx_fdecim_set_state(f2._h, fs.ctypes.data) == 0
     assert np.array_equal(f1.decimate(xf[77_056:]), f2.decimate(xf[77_056:]))
     f1.close(); f2.close()
+
+
+def test_measured_read_ceiling_runs_and_refuses_bad_arguments():
+    """sdrx_measure_hbm_read (sdrx_stream_sum_kernel, the roofline denominator of bench.py): 24 MiB + 48 bytes puts lanes of the
+    narrowest grid in the four-load loop and in the tail loop, lanes of the widest in the tail loop alone.  The kernel has no output
+    to compare; the rate must be a finite positive number below what any memory system delivers."""
+    rate = sa.measure_hbm_read(0, (24 << 20) + 48, 1)
+    assert np.isfinite(rate) and 0 < rate < 1e6, rate
+    for bad in ((0, (1 << 20) - 1, 1), (0, 1 << 20, 0), (-1, 1 << 20, 1)):
+        with pytest.raises(sa.SdrxError):
+            sa.measure_hbm_read(*bad)
+    assert sa.lib().sdrx_measure_hbm_read(0, 1 << 20, 1, None) == -1

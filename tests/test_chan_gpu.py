@@ -195,10 +195,12 @@ def test_add_and_remove_channel_leave_the_others_alone(hb_engine):
     assert np.array_equal(bank.read(1), orc.Chain(ref[1][1]).feed(a))
 
 
-@pytest.mark.parametrize("levels,lds_kb", [(8, 80), (10, 150)])
+@pytest.mark.parametrize("levels,lds_kb", [(8, 80), (10, 150), (5, 80)])
 def test_deep_pass_plans_stay_exact(levels, lds_kb, monkeypatch, hb_engine):
     """SDRX_CHAN_MAX_LEVELS / SDRX_CHAN_LDS_KB (the experiment of DESIGN 4.3: deeper first pass, fewer node-stream bytes):
-    more than six levels per pass need several warm-up chunks and a longer stream history -- same samples"""
+    more than six levels per pass need several warm-up chunks and a longer stream history -- same samples.
+    (5, 80) cuts the ten levels into two passes of five: the second pass holds many subtrees whose fifth level is off the matrix
+    cores, so tree_kernel<true> runs with more than one stream (it takes the stream from blockIdx.y; the deeper plans give it one)"""
     monkeypatch.setenv("SDRX_CHAN_MAX_LEVELS", str(levels))
     monkeypatch.setenv("SDRX_CHAN_LDS_KB", str(lds_kb))
     rates, fcs = cfg3_channels(32)

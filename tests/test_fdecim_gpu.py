@@ -31,15 +31,45 @@ CASES = [(k, L, fc, bits) for k, bl in (("fi", (16,)), ("ff", (16,)), ("if", (8,
          for L in range(7) for fc in (sa.FC_INF, sa.FC_SUP, sa.FC_CEN) if not (L == 0 and fc != sa.FC_CEN)]
 
 
-@pytest.mark.parametrize("kind,L,fc,bits", CASES)
-def test_streaming_blocks_match_oracle(kind, L, fc, bits):
+# ragged device-thread blocks: tails are dropped, state is carried; one block shorter than the warm-up history
+BLOCKS = (2 * 40000 + 6, 2, 2 * 300, 2 * 70001, 0, 2 * 2048 * 5)
+
+
+def stages(L, fc):
+    """half-band stages of the cascade: _cen runs L of them, _inf / _sup a 4x front end and L - 2 (fdecim_kernel.hpp)"""
+    return L if fc == sa.FC_CEN else max(L - 2, 0)
+
+
+def _stream(kind, L, fc, bits, blocks, kernel=None):
     g = sa.FloatDecimators(kind, L, fc, bits)
     o = orc.FDecim(kind, L, fc, bits)
-    # ragged device-thread blocks: tails are dropped, state is carried; one block shorter than the warm-up history
-    for i, n in enumerate((2 * 40000 + 6, 2, 2 * 300, 2 * 70001, 0, 2 * 2048 * 5)):
+    for i, n in enumerate(blocks):
         x = _input(kind, n, 1000 * L + 10 * fc + i, bits)
         got, want = g.decimate(x), o.process(x)
         assert _same(got, want), (kind, L, fc, bits, i, n, got.size, want.size)
+        if kernel and want.size:
+            assert g.last_launch()["kernel"] == kernel, (kind, L, fc, bits, i, g.last_launch())
+
+
+@pytest.mark.parametrize("kind,L,fc,bits", CASES)
+def test_streaming_blocks_match_oracle(kind, L, fc, bits):
+    _stream(kind, L, fc, bits, BLOCKS)
+
+
+@pytest.mark.parametrize("kind,L,fc,bits", [c for c in CASES if stages(c[1], c[2]) > 3])
+def test_streaming_blocks_in_one_pass(kind, L, fc, bits, monkeypatch):
+    """SDRX_FDECIM_SPLIT=0: cascades of 4, 5 and 6 stages as ONE fdecim_chain_kernel<ns, in> instead of two passes of at most three
+    stages.  The 5-stage chain gets one more block, of 2048 * 3 + 64 pre-samples: its last chunk holds 64 of them, so the state dump
+    takes nearly all of every arm's 32 entries from the chunk before (1954 pre-samples back for stage 5), and the block behind it
+    starts from that dump."""
+    monkeypatch.setenv("SDRX_FDECIM_SPLIT", "0")
+    ns = stages(L, fc)
+    blocks = BLOCKS[:-1] + ((2 * (2048 * 3 + 64),) if ns == 5 else ()) + BLOCKS[-1:]
+    _stream(kind, L, fc, bits, blocks, kernel=f"fdecim_chain_kernel<{ns},{int(kind == 'if')}>")
+
+
+def test_one_pass_cases_cover_the_long_cascades():
+    assert sorted({(stages(c[1], c[2]), c[0]) for c in CASES if stages(c[1], c[2]) > 3}) == [(ns, k) for ns in (4, 5, 6) for k in ("ff", "fi", "if")]
 
 
 def test_golden_vectors_from_the_compiled_reference():

@@ -55,6 +55,17 @@ def test_case_bit_exact(oracle, case):
     check_levels(bank, 0, want, case["name"])
 
 
+@pytest.mark.parametrize("case", wc.DYADIC_CASES, ids=[c["name"] for c in wc.DYADIC_CASES])
+def test_case_bit_exact_on_the_forced_serial_schedule(oracle, case, monkeypatch):
+    """SDRX_WFM_SERIAL_SCHEDULE=1 (read by sdrx_wfm_create): wfm_sched_walk_kernel on the steps that wfm_prep_kernel and
+    wfm_sched_fill_kernel otherwise take in closed form -- walk and closed form against the same oracle on the same channel"""
+    monkeypatch.setenv("SDRX_WFM_SERIAL_SCHEDULE", "1")
+    want = wc.run_oracle(oracle, case)
+    bank, got = run_gpu(case)
+    assert_feeds_equal(got, want["feeds"], case["name"] + " serial")
+    check_levels(bank, 0, want, case["name"] + " serial")
+
+
 def test_design_products_equal_the_oracle(oracle):
     for case in wc.CASES[:6]:
         o = wc.OracleWfm(oracle, case["cfg"])

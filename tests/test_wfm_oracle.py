@@ -37,6 +37,11 @@ def test_cases_cover_what_they_claim():
         assert s in by["splits_edges"]["splits"]
     assert by["one_long_feed"]["splits"] == [by["one_long_feed"]["n"]]
     assert wc.required_bw(80000) == 120000 and wc.required_bw(12500) == 48000 and wc.required_bw(48000) == 48000
+    # steps 5, 2.5, 1 and 8 are dyadic, 250000 / 48000 and 384000 / 44100 are not: both schedules have their cases
+    dyadic = {c["name"] for c in wc.DYADIC_CASES}
+    assert len(dyadic) >= 3 and {"default_240k", "default_120k", "nbfm_48k_step1", "wide_rf250k_384k", "burst_240k_fraccap"} <= dyadic
+    assert not dyadic & {"nondyadic_250k", "r384k_to_44k1"}
+    assert len({c["cfg"][0] / c["cfg"][2] for c in wc.DYADIC_CASES}) >= 3
 
 
 @pytest.mark.parametrize("case", wc.CASES, ids=[c["name"] for c in wc.CASES])

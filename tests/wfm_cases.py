@@ -235,6 +235,17 @@ EDGE_IQ = (10077, 12971)
 CASES = make_cases()
 
 
+def dyadic_step(cfg) -> bool:
+    """whether sdrx_wfm_create gives the channel the closed-form resampler schedule: the float step in_rate / audio_rate times 2^q
+    is an integer below 2^20 for some q <= 10 (sdrangel_amd/csrc/sdrx_wfm.hip)"""
+    step = np.float32(cfg[0]) / np.float32(cfg[2])
+    return any(float(step) * (1 << q) == np.floor(float(step) * (1 << q)) < (1 << 20) for q in range(11))
+
+
+#: the named cases that SDRX_WFM_SERIAL_SCHEDULE=1 moves from the closed form to the serial walk
+DYADIC_CASES = [c for c in CASES if dyadic_step(c["cfg"])]
+
+
 def inputs(case: dict) -> np.ndarray:
     return signal(case["sig"], case["n"], case["cfg"][0], case["seed"])
 
