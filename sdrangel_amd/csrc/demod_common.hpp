@@ -1,8 +1,10 @@
-// host code the demodulator banks share (sdrx_wfm.hip directly; sdrx_am.hip, sdrx_nfm.hip, sdrx_ssb.hip and sdrx_udpsrc.hip
-// through demod_bank.hpp): input staging and checks, the hand-over from a channelizer bank, one channel's device state, the
-// per-feed pointer table, the Bandpass design.  `who` is the entry point named in the error text.
+// host code the demodulator banks and the channel back-end share (sdrx_wfm.hip and sdrx_backend.hip directly; sdrx_am.hip,
+// sdrx_nfm.hip, sdrx_ssb.hip and sdrx_udpsrc.hip through demod_bank.hpp): input staging and checks, the hand-over from a
+// channelizer bank and the ordering against its stream, one channel's device state, the per-feed pointer table, growth
+// and reset of a work arena with carried fronts, the Bandpass design.  `who` is the entry point named in the error text.
 #pragma once
 #include "sdrx_common.hpp"
+#include "demod_carve.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -43,13 +45,14 @@ int demod_stage_inputs(std::vector<Host>& ch, hipStream_t stream, const int16_t*
     return SDRX_OK;
 }
 
-// what the bank's last feed produced for its channels 0 .. n_ch-1
-inline int demod_gather_bank(sdrx_chan_bank_t* bank, int n_ch, const char* who, std::vector<const int16_t*>& d, std::vector<int64_t>& n)
+// what the bank's last feed produced for its channels 0 .. n_ch-1; `me` is what the error text calls the caller
+inline int demod_gather_bank(sdrx_chan_bank_t* bank, int n_ch, const char* who, std::vector<const int16_t*>& d, std::vector<int64_t>& n,
+                             const char* me = "the demodulator bank")
 {
     d.resize((size_t)n_ch); n.resize((size_t)n_ch);
     for (int c = 0; c < n_ch; c++) {
         int rc = sdrx_chan_bank_last_dev(bank, c, &d[(size_t)c], &n[(size_t)c]);
-        if (rc) { set_error(std::string(who) + ": the bank has fewer channels than the demodulator bank"); return rc; }
+        if (rc) { set_error(std::string(who) + ": the bank has fewer channels than " + me); return rc; }
     }
     return SDRX_OK;
 }
@@ -82,6 +85,62 @@ int demod_upload_bufs(Bufs* d_bufs, const Bufs* h_bufs, int n_ch, hipEvent_t ev,
 {
     SDRX_HIP(hipMemcpyAsync(d_bufs, h_bufs, (size_t)n_ch * sizeof(Bufs), hipMemcpyHostToDevice, stream));
     SDRX_HIP(hipEventRecord(ev, stream));
+    return SDRX_OK;
+}
+
+// A work arena whose layout marks carried fronts (Carver::take_kept): `lay(k, cap, bufs)` describes it for feeds of up to
+// `cap` samples.  demod_place: the pointers it hands out at `base`, all null for a null base.
+template <class Bufs, class Lay>
+Bufs demod_place(void* base, int64_t cap, Lay lay)
+{
+    Bufs u{};
+    Carver k{static_cast<char*>(base)};
+    lay(k, cap, u);
+    return u;
+}
+
+// Growth starts at 4096 samples and doubles until n_in fits.  The new arena is zeroed, takes each kept range from where the
+// old layout had it, and replaces the old arena after a single wait for the stream.
+template <class Bufs, class Lay>
+int demod_grow_arena(DevBuf& arena, int64_t& cap_in, int64_t n_in, hipStream_t stream, Lay lay)
+{
+    if (n_in <= cap_in) return SDRX_OK;
+    int64_t cap = cap_in ? cap_in : 4096;
+    while (cap < n_in) cap *= 2;
+    Carver was{nullptr}, now{nullptr};
+    Bufs u{};
+    lay(was, cap_in, u); lay(now, cap, u);
+    char* np = nullptr;
+    SDRX_HIP(hipMalloc(reinterpret_cast<void**>(&np), now.off));
+    hipError_t e = hipMemsetAsync(np, 0, now.off, stream);
+    for (int i = 0; arena.p && i < now.n_kept && e == hipSuccess; i++)
+        e = hipMemcpyAsync(np + now.kept[i].off, static_cast<const char*>(arena.p) + was.kept[i].off, now.kept[i].bytes, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { (void)hipFree(np); return hip_fail(e, "grow arena", __FILE__, __LINE__); }
+    arena.release();
+    arena.p = np; arena.cap = now.off; cap_in = cap;
+    return SDRX_OK;
+}
+
+// a fresh stream: the kept ranges of an arena laid out for cap_in samples back to zero, on the stream
+template <class Bufs, class Lay>
+int demod_clear_kept(const DevBuf& arena, int64_t cap_in, hipStream_t stream, Lay lay)
+{
+    Carver k{nullptr};
+    Bufs u{};
+    lay(k, cap_in, u);
+    for (int i = 0; arena.p && i < k.n_kept; i++) SDRX_HIP(hipMemsetAsync(static_cast<char*>(arena.p) + k.kept[i].off, 0, k.kept[i].bytes, stream));
+    return SDRX_OK;
+}
+
+// Device-side ordering of a feed against the stream that is still writing its input: `later` runs nothing queued from here on
+// until `earlier` has done what it holds now.  Once with (feed's stream, producer) in front of the kernels that read the
+// input, once with (producer, feed's stream) behind them; a no-op without a second stream.
+inline int demod_stream_after(hipStream_t later, hipStream_t earlier, hipEvent_t ev)
+{
+    if (!later || !earlier || later == earlier) return SDRX_OK;
+    SDRX_HIP(hipEventRecord(ev, earlier));
+    SDRX_HIP(hipStreamWaitEvent(later, ev, 0));
     return SDRX_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "backend_kernels.hpp"
 #include "backend_design.hpp"
 #include "backend_view.hpp"
+#include "demod_common.hpp"
 #include <cstddef>
 #include <vector>
 #include <cmath>
@@ -18,13 +19,30 @@ using namespace sdrx;
 
 namespace {
 
+// One channel's work arena for feeds of up to cap_in samples.  The fronts of res (the resampled samples waiting for a full
+// fftfilt block) and of tail (slot 0: ovlbuf) carry state from feed to feed.
+void work(Carver& k, int64_t cap_in, size_t half, BeBufs& u)
+{
+    // pending (<512) + at most one resampler output per input (distance step >= 1 by construction of decimate())
+    const size_t n_res_max = (size_t)cap_in + 1024;
+    const size_t n_blk_max = n_res_max / half + 2;
+    u.mixed = k.take<float2>((size_t)(BE_HIST + cap_in));
+    u.res = k.take_kept<float2>(n_res_max + BE_FFT, BE_FFT);
+    u.head = k.take<float2>(n_blk_max * half);
+    u.tail = k.take_kept<float2>((n_blk_max + 1) * half, half);
+    u.cplx_out = k.take<float2>(n_res_max);
+    u.real_out = k.take<float>(n_res_max);
+}
+
 struct ChanHost {
     sdrx_backend_cfg cfg;
-    DevBuf mixed, res, head, tail, cplx_out, real_out;
+    DevBuf arena;                 // work()'s layout for cap_in samples
     uint32_t* hist[2] = { nullptr, nullptr };
     int cur = 0;
     int64_t cap_in = 0;
     DevBuf stage_in;              // host-pointer feeds
+    auto lay() const { return [this](Carver& k, int64_t cap, BeBufs& u) { work(k, cap, cfg.filt_mode >= 4 ? BE_FFT : BE_FFT / 2, u); }; }
+    BeBufs placed() const { return demod_place<BeBufs>(arena.p, cap_in, lay()); }      // null pointers before the first feed
 };
 
 } // namespace
@@ -45,56 +63,17 @@ struct sdrx_backend {
     float* d_utbl = nullptr; float* d_utbl2 = nullptr;     // g_fft cosine tables for N = 1024 / 2048
     bool any1024 = false, any2048 = false;
     bool any_dyadic = false;      // some resampling ratio has a closed-form schedule
-    std::vector<float> taps_all; std::vector<float> filters_all;     // kept for inspection (tests)
-    std::vector<int> taps_off, filt_off, ntaps;
+    InterpTables taps; std::vector<float> filters_all;     // kept for inspection (tests)
     std::vector<int> perm, col_of;    // schedule column q holds channel perm[q]; col_of[c] is its inverse
     int* d_perm = nullptr;
     bool state_valid = false;     // d_chan state initialised
 };
 
-static int ensure_capacity(sdrx_backend* b, int c, int64_t n_in)
-{
-    ChanHost& h = b->ch[(size_t)c];
-    if (n_in <= h.cap_in) return SDRX_OK;
-    int64_t cap = h.cap_in ? h.cap_in : 4096;
-    while (cap < n_in) cap *= 2;
-    // pending (<512) + at most one resampler output per input (distance step >= 1 by construction of decimate())
-    const size_t n_res_max = (size_t)cap + 1024;
-    const size_t half = h.cfg.filt_mode >= 4 ? BE_FFT : BE_FFT / 2;
-    const size_t n_blk_max = n_res_max / half + 2;
-    // buffers that carry state (res: pending, tail: ovlbuf) must keep their content
-    auto grow_keep = [&](DevBuf& buf, size_t bytes, size_t keep) -> int {
-        if (bytes <= buf.cap) return SDRX_OK;
-        void* np = nullptr;
-        SDRX_HIP(hipMalloc(&np, bytes));
-        SDRX_HIP(hipMemsetAsync(np, 0, bytes, b->core.stream));
-        if (buf.p && keep) SDRX_HIP(hipMemcpyAsync(np, buf.p, keep, hipMemcpyDeviceToDevice, b->core.stream));
-        SDRX_HIP(hipStreamSynchronize(b->core.stream));
-        if (buf.p) (void)hipFree(buf.p);
-        buf.p = np; buf.cap = bytes;
-        return SDRX_OK;
-    };
-    int rc;
-    if ((rc = grow_keep(h.mixed, (size_t)(BE_HIST + cap) * 8, 0))) return rc;
-    if ((rc = grow_keep(h.res, (n_res_max + BE_FFT) * 8, BE_FFT * 8))) return rc;
-    if ((rc = grow_keep(h.head, n_blk_max * half * 8, 0))) return rc;
-    if ((rc = grow_keep(h.tail, (n_blk_max + 1) * half * 8, half * 8))) return rc;
-    if ((rc = grow_keep(h.cplx_out, n_res_max * 8, 0))) return rc;
-    if ((rc = grow_keep(h.real_out, n_res_max * 4, 0))) return rc;
-    h.cap_in = cap;
-    return SDRX_OK;
-}
-
 // the distance step and, where step * 2^q is an integer, the closed-form schedule's constants
 static void set_step(BeChan& s, float step)
 {
     s.step = step;
-    s.dy_q = -1; s.dy_S = 0;
-    if (s.step >= 1.0f && !getenv("SDRX_BE_SERIAL_SCHEDULE"))
-        for (int q = 0; q <= 10; q++) {
-            const float v = s.step * (float)(1 << q);                                  // exact (power of two)
-            if (v == std::floor(v) && v < (float)(1 << 20)) { s.dy_q = q; s.dy_S = (int)v; break; }
-        }
+    design_dyadic_step(s.step, "SDRX_BE_SERIAL_SCHEDULE", &s.dy_q, &s.dy_S);
 }
 
 extern "C" {
@@ -105,8 +84,7 @@ int sdrx_backend_destroy(sdrx_backend_t* b)
     (void)hipSetDevice(b->core.device);
     if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
     for (auto& h : b->ch) {
-        h.mixed.release(); h.res.release(); h.head.release(); h.tail.release();
-        h.cplx_out.release(); h.real_out.release(); h.stage_in.release();
+        h.arena.release(); h.stage_in.release();
         for (int i = 0; i < 2; i++) if (h.hist[i]) (void)hipFree(h.hist[i]);
     }
     b->sched.release();
@@ -151,22 +129,12 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
     if (rc) { delete b; return rc; }
     b->n_ch = n_ch;
     b->ch.resize((size_t)n_ch); b->h_chan.resize((size_t)n_ch);
-    b->taps_off.resize((size_t)n_ch); b->filt_off.resize((size_t)n_ch); b->ntaps.resize((size_t)n_ch);
 
-    // NCO table (nco.cpp:30-39) and g_fft cosine table (gfft.h:141-150)
-    std::vector<float> nco(BE_NCO_N);
-    for (int i = 0; i < BE_NCO_N; i++) nco[(size_t)i] = (float)std::cos((2.0 * PI_D * i) / BE_NCO_N);
-    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_nco), BE_NCO_N * 4), sdrx_backend_destroy(b));
-    SDRX_HIP_ELSE(hipMemcpy(b->d_nco, nco.data(), BE_NCO_N * 4, hipMemcpyHostToDevice), sdrx_backend_destroy(b));
-    for (int n : { BE_FFT, BE_FFT_MAX }) {
-        std::vector<float> utbl((size_t)n / 4 + 1);
-        utbl[0] = 1.0f;
-        for (int i = 1; i < n / 4; i++) utbl[(size_t)i] = (float)std::cos((2.0 * 3.141592653589793238462643383279502884197 * (float)i) / (float)n);
-        utbl[(size_t)n / 4] = 0.0f;
-        float*& dst = n == BE_FFT ? b->d_utbl : b->d_utbl2;
-        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&dst), ((size_t)n / 4 + 1) * 4), sdrx_backend_destroy(b));
-        SDRX_HIP_ELSE(hipMemcpy(dst, utbl.data(), ((size_t)n / 4 + 1) * 4, hipMemcpyHostToDevice), sdrx_backend_destroy(b));
-    }
+    // NCO table (nco.cpp:30-39) and g_fft cosine tables (gfft.h:141-150)
+    rc = design_upload(&b->d_nco, design_nco_table(BE_NCO_N));
+    if (!rc) rc = design_upload(&b->d_utbl, design_gfft_table(BE_FFT));
+    if (!rc) rc = design_upload(&b->d_utbl2, design_gfft_table(BE_FFT_MAX));
+    if (rc) { sdrx_backend_destroy(b); return rc; }
 
     // per channel design
     SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_filters), (size_t)n_ch * 2 * BE_FFT_MAX * 8), sdrx_backend_destroy(b));   // [filter | filterOpp] per channel
@@ -175,56 +143,17 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
         const sdrx_backend_cfg& k = cfg[c];
         ChanHost& h = b->ch[(size_t)c];
         h.cfg = k;
-        // channels with the same Interpolator::create arguments share one tap table
-        int same = -1;
-        for (int p = 0; p < c && same < 0; p++) {
-            const sdrx_backend_cfg& o = cfg[p];
-            if (o.in_rate == k.in_rate && o.interp_cutoff == k.interp_cutoff && o.taps_per_phase == k.taps_per_phase) same = p;
-        }
-        if (same >= 0) {
-            b->taps_off[(size_t)c] = b->taps_off[(size_t)same]; b->ntaps[(size_t)c] = b->ntaps[(size_t)same];
-        } else {
-            std::vector<float> poly; int nt = 0;
-            design_interp(16, (double)k.in_rate, (double)k.interp_cutoff, (double)k.taps_per_phase, poly, &nt);
-            b->taps_off[(size_t)c] = (int)b->taps_all.size(); b->ntaps[(size_t)c] = nt;
-            b->taps_all.insert(b->taps_all.end(), poly.begin(), poly.end());
-        }
-        const int nt = b->ntaps[(size_t)c];
-        b->filt_off[(size_t)c] = c * 2 * BE_FFT_MAX;
+        b->taps.add((double)k.in_rate, (double)k.interp_cutoff, (double)k.taps_per_phase);
         const int flen = k.filt_mode >= 4 ? BE_FFT_MAX : BE_FFT;          // runDSB / runAsym: "double the FFT size used for SSB"
-        // fftfilt::create_filter / create_dsb_filter / create_asym_filter: windowed sinc in the first flen2 bins, forward FFT
-        // (on the GPU, with the same kernel code the data path uses), normalise to max |H| over bins 0..flen2-1.
-        // which: 0 = filter, 1 = filterOpp (runAsym only: low pass at f1 = the opposite band's width)
+        // fftfilt::create_filter / create_dsb_filter / create_asym_filter.  which: 0 = filter, 1 = filterOpp (runAsym only:
+        // low pass at f1 = the opposite band's width)
         auto design = [&](int which) -> int {
-            std::vector<float> f((size_t)flen * 2, 0.0f);
-            const int h2 = flen / 2;
-            if (k.filt_mode >= 4) {
-                const float fc = which ? k.f1 : k.f2;                                            // fftfilt(f2, len) / create_asym_filter(fopp = f1, fin = f2)
-                for (int i = 0; i < h2; i++) f[(size_t)(2 * i)] = fsinc(fc, i, h2);
-            } else {
-                const bool lp = k.f2 != 0, hp = k.f1 != 0;
-                for (int i = 0; i < h2; i++) {
-                    float v = 0;
-                    if (lp) v += fsinc(k.f2, i, h2);
-                    if (hp) v -= fsinc(k.f1, i, h2);
-                    f[(size_t)(2 * i)] = v;
-                }
-                if (hp && k.f2 < k.f1) f[(size_t)(2 * (h2 / 2))] += 1;
-            }
-            for (int i = 0; i < h2; i++) { const float w = blackman(i, h2); f[(size_t)(2 * i)] *= w; f[(size_t)(2 * i + 1)] *= w; }
             float2* dst = b->d_filters + (size_t)c * 2 * BE_FFT_MAX + (size_t)which * BE_FFT_MAX;
-            SDRX_HIP(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice));
-            if (flen == BE_FFT) hipLaunchKernelGGL(be_fft_design_kernel<BE_FFT>, dim3(1), dim3(BE_FFT / 8), 0, b->core.stream, dst, b->d_utbl);
-            else hipLaunchKernelGGL(be_fft_design_kernel<BE_FFT_MAX>, dim3(1), dim3(BE_FFT_MAX / 8), 0, b->core.stream, dst, b->d_utbl2);
-            SDRX_HIP(hipGetLastError());
-            SDRX_HIP(hipStreamSynchronize(b->core.stream));
-            SDRX_HIP(hipMemcpy(f.data(), dst, (size_t)flen * 8, hipMemcpyDeviceToHost));
-            float scale = 0;
-            for (int i = 0; i < h2; i++) { const float mag = hypotf(f[(size_t)(2 * i)], f[(size_t)(2 * i + 1)]); if (mag > scale) scale = mag; }
-            if (scale != 0) for (int i = 0; i < flen * 2; i++) f[(size_t)i] /= scale;
-            SDRX_HIP(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice));
-            std::memcpy(&b->filters_all[((size_t)c * 2 + (size_t)which) * BE_FFT_MAX * 2], f.data(), (size_t)flen * 8);
-            return SDRX_OK;
+            float* copy = &b->filters_all[((size_t)c * 2 + (size_t)which) * BE_FFT_MAX * 2];
+            if (k.filt_mode < 4)
+                return design_fft_filter<BE_FFT>(dst, b->d_utbl, b->core.stream, copy, [&](float* f, int h2) { fftfilt_fill_band(k.f1, k.f2, f, h2); });
+            // fftfilt(f2, len) / create_asym_filter(fopp = f1, fin = f2)
+            return design_fft_filter<BE_FFT_MAX>(dst, b->d_utbl2, b->core.stream, copy, [&](float* f, int h2) { fftfilt_fill_lowpass(which ? k.f1 : k.f2, f, h2); });
         };
         if (k.filt_mode) {
             int drc = design(0);
@@ -236,8 +165,8 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
         std::memset(&s, 0, sizeof s);
         s.nco_inc = (int)(((float)k.nco_freq * BE_NCO_N) / (float)k.in_rate);          // NCO::setFreq (float math, truncation)
         set_step(s, (float)k.in_rate / (float)k.out_rate);
-        s.ntaps = nt; s.phase_steps = 16;
-        s.taps_off = b->taps_off[(size_t)c]; s.filt_mode = k.filt_mode; s.filt_off = b->filt_off[(size_t)c];
+        s.ntaps = b->taps.ntaps[(size_t)c]; s.phase_steps = 16;
+        s.taps_off = b->taps.off[(size_t)c]; s.filt_mode = k.filt_mode; s.filt_off = c * 2 * BE_FFT_MAX;
         s.discri = k.discri; s.fm_scaling = k.fm_scaling;
         if (s.dy_q >= 0) b->any_dyadic = true;
         s.half = flen / 2;
@@ -249,12 +178,12 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
     // schedule columns: channels sorted by tap table, so that a FIR tile of 16 columns normally sees one design
     b->perm.resize((size_t)n_ch); b->col_of.resize((size_t)n_ch);
     for (int c = 0; c < n_ch; c++) b->perm[(size_t)c] = c;
-    std::stable_sort(b->perm.begin(), b->perm.end(), [&](int x, int y) { return b->taps_off[(size_t)x] < b->taps_off[(size_t)y]; });
+    std::stable_sort(b->perm.begin(), b->perm.end(), [&](int x, int y) { return b->taps.off[(size_t)x] < b->taps.off[(size_t)y]; });
     for (int q = 0; q < n_ch; q++) b->col_of[(size_t)b->perm[(size_t)q]] = q;
     SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_perm), (size_t)n_ch * sizeof(int)), sdrx_backend_destroy(b));
     SDRX_HIP_ELSE(hipMemcpy(b->d_perm, b->perm.data(), (size_t)n_ch * sizeof(int), hipMemcpyHostToDevice), sdrx_backend_destroy(b));
-    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_taps), b->taps_all.size() * 4), sdrx_backend_destroy(b));
-    SDRX_HIP_ELSE(hipMemcpy(b->d_taps, b->taps_all.data(), b->taps_all.size() * 4, hipMemcpyHostToDevice), sdrx_backend_destroy(b));
+    rc = design_upload(&b->d_taps, b->taps.all);
+    if (rc) { sdrx_backend_destroy(b); return rc; }
     SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(BeChan)), sdrx_backend_destroy(b));
     SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(BeBufs)), sdrx_backend_destroy(b));
     SDRX_HIP_ELSE(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(BeBufs), hipHostMallocDefault), sdrx_backend_destroy(b));
@@ -275,7 +204,8 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
     int64_t n_max = 0, n_res_bound = 0;
     for (int c = 0; c < b->n_ch; c++) {
         if (n_per_ch[c] < 0 || n_per_ch[c] > 0x0fffffff) { set_error("sdrx_backend_feed: bad length"); return SDRX_EINVAL; }
-        int rc = ensure_capacity(b, c, std::max<int64_t>(n_per_ch[c], 1)); if (rc) return rc;
+        ChanHost& h = b->ch[(size_t)c];
+        int rc = demod_grow_arena<BeBufs>(h.arena, h.cap_in, std::max<int64_t>(n_per_ch[c], 1), b->core.stream, h.lay()); if (rc) return rc;
         n_max = std::max(n_max, n_per_ch[c]);
         // every resampler output after the first two of a stream consumes >= floor(step) inputs (distance >= step before the `-= 1` walk)
         const int64_t per_out = std::max<int64_t>(1, (int64_t)std::floor(b->h_chan[(size_t)c].step));
@@ -295,13 +225,12 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
         BeBufs& u = b->h_bufs[c];
         u.in = reinterpret_cast<const uint32_t*>(d_iq[c]);
         u.hist = h.hist[h.cur]; u.hist_next = h.hist[h.cur ^ 1];
-        u.mixed = static_cast<float2*>(h.mixed.p); u.sched = static_cast<uint2*>(b->sched.p) + b->col_of[(size_t)c]; u.sched_stride = b->n_ch;
-        u.res = static_cast<float2*>(h.res.p); u.head = static_cast<float2*>(h.head.p); u.tail = static_cast<float2*>(h.tail.p);
-        u.cplx_out = static_cast<float2*>(h.cplx_out.p); u.real_out = static_cast<float*>(h.real_out.p);
+        u.sched = static_cast<uint2*>(b->sched.p) + b->col_of[(size_t)c]; u.sched_stride = b->n_ch;
+        Carver k{static_cast<char*>(h.arena.p)};
+        h.lay()(k, h.cap_in, u);
         u.n_in = n_per_ch[c];
     }
-    SDRX_HIP(hipMemcpyAsync(b->d_bufs, b->h_bufs, (size_t)b->n_ch * sizeof(BeBufs), hipMemcpyHostToDevice, b->core.stream));
-    SDRX_HIP(hipEventRecord(b->bufs_ev, b->core.stream));
+    int rc = demod_upload_bufs(b->d_bufs, b->h_bufs, b->n_ch, b->bufs_ev, b->core.stream); if (rc) return rc;
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (n_max + BE_HIST + 255) / 256));
     // closed-form schedule for dyadic ratios (prep decides per channel and feed), the serial walk for the rest
     hipLaunchKernelGGL(be_sched_dyadic_prep_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
@@ -314,18 +243,12 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
     // always launched: lanes whose channel the closed form took exit at once (prep's off-grid guard can hand a channel back)
     hipLaunchKernelGGL(be_schedule_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
     SDRX_HIP(hipGetLastError());
-    if (producer && producer != b->core.stream) {
-        SDRX_HIP(hipEventRecord(b->prod_ev, producer));
-        SDRX_HIP(hipStreamWaitEvent(b->core.stream, b->prod_ev, 0));
-    }
+    rc = demod_stream_after(b->core.stream, producer, b->prod_ev); if (rc) return rc;
     // be_mix stages the 16 KB NCO table per workgroup: at least 8192 samples each
     const unsigned gx_mix = (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (n_max + BE_HIST + 8191) / 8192));
     hipLaunchKernelGGL(be_mix_kernel, dim3(gx_mix, (unsigned)b->n_ch), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_nco);
     SDRX_HIP(hipGetLastError());
-    if (producer && producer != b->core.stream) {
-        SDRX_HIP(hipEventRecord(b->cons_ev, b->core.stream));
-        SDRX_HIP(hipStreamWaitEvent(producer, b->cons_ev, 0));
-    }
+    rc = demod_stream_after(producer, b->core.stream, b->cons_ev); if (rc) return rc;
     hipLaunchKernelGGL(be_fir_kernel, dim3((unsigned)((n_res_bound + BE_FIR_TO - 1) / BE_FIR_TO), (unsigned)((b->n_ch + BE_FIR_TC - 1) / BE_FIR_TC)), dim3(256), 0,
                        b->core.stream, b->d_chan, b->d_bufs, b->d_taps, b->d_perm, b->n_ch);
     SDRX_HIP(hipGetLastError());
@@ -360,12 +283,9 @@ int sdrx_backend_feed_bank(sdrx_backend_t* b, sdrx_chan_bank_t* bank)
     SDRX_HIP(hipSetDevice(b->core.device));
     void* ps = nullptr;
     int rc = sdrx_chan_bank_get_stream(bank, &ps); if (rc) return rc;
-    std::vector<const int16_t*> d((size_t)b->n_ch);
-    std::vector<int64_t> n((size_t)b->n_ch);
-    for (int c = 0; c < b->n_ch; c++) {
-        rc = sdrx_chan_bank_last_dev(bank, c, &d[(size_t)c], &n[(size_t)c]);
-        if (rc) { set_error("sdrx_backend_feed_bank: the bank has fewer channels than the back-end"); return rc; }
-    }
+    std::vector<const int16_t*> d;
+    std::vector<int64_t> n;
+    rc = demod_gather_bank(bank, b->n_ch, "sdrx_backend_feed_bank", d, n, "the back-end"); if (rc) return rc;
     return feed_common(b, d.data(), n.data(), static_cast<hipStream_t>(ps));
 }
 
@@ -387,30 +307,22 @@ int sdrx_backend_feed(sdrx_backend_t* b, const int16_t* const* iq, const int64_t
 int64_t sdrx_backend_read(sdrx_backend_t* b, int32_t c, float* out, int64_t cap_floats)
 {
     if (!b || c < 0 || c >= b->n_ch || cap_floats < 0 || (cap_floats > 0 && !out)) { set_error("sdrx_backend_read: bad argument"); return SDRX_EINVAL; }
-    if (hipSetDevice(b->core.device) != hipSuccess) return SDRX_EHIP;
-    BeChan s;
-    hipError_t e = hipMemcpyAsync(&s, b->d_chan + c, sizeof s, hipMemcpyDeviceToHost, b->core.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(b->core.stream);
-    if (e != hipSuccess) return hip_fail(e, "read state", __FILE__, __LINE__);
-    const bool real = s.discri != 0;
-    int64_t n_floats = (int64_t)s.n_out * (real ? 1 : 2);
+    const float* src; int64_t n_floats;
+    int rc = sdrx_backend_last_dev(b, c, &src, &n_floats); if (rc) return rc;
     if (n_floats > cap_floats) n_floats = cap_floats;
     if (n_floats == 0) return 0;
-    const void* src = real ? b->ch[(size_t)c].real_out.p : b->ch[(size_t)c].cplx_out.p;
-    e = hipMemcpy(out, src, (size_t)n_floats * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "read data", __FILE__, __LINE__);
+    SDRX_HIP(hipMemcpy(out, src, (size_t)n_floats * 4, hipMemcpyDeviceToHost));
     return n_floats;
 }
 
 int sdrx_backend_last_dev(sdrx_backend_t* b, int32_t c, const float** d_out, int64_t* n_floats)
 {
     if (!b || c < 0 || c >= b->n_ch || !d_out || !n_floats) { set_error("sdrx_backend_last_dev: bad argument"); return SDRX_EINVAL; }
-    SDRX_HIP(hipSetDevice(b->core.device));
     BeChan s;
-    SDRX_HIP(hipMemcpyAsync(&s, b->d_chan + c, sizeof s, hipMemcpyDeviceToHost, b->core.stream));
-    SDRX_HIP(hipStreamSynchronize(b->core.stream));
+    int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     const bool real = s.discri != 0;
-    *d_out = static_cast<const float*>(real ? b->ch[(size_t)c].real_out.p : b->ch[(size_t)c].cplx_out.p);
+    const BeBufs u = b->ch[(size_t)c].placed();
+    *d_out = real ? u.real_out : reinterpret_cast<const float*>(u.cplx_out);
     *n_floats = (int64_t)s.n_out * (real ? 1 : 2);
     return SDRX_OK;
 }
@@ -419,9 +331,9 @@ int sdrx_backend_get_design(sdrx_backend_t* b, int32_t c, int32_t* ntaps_per_pha
                             float* filter_iq, int32_t* nco_inc)
 {
     if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_backend_get_design: bad channel"); return SDRX_EINVAL; }
-    const int nt = b->ntaps[(size_t)c];
+    const int nt = b->taps.ntaps[(size_t)c];
     if (ntaps_per_phase) *ntaps_per_phase = nt;
-    if (taps) std::memcpy(taps, &b->taps_all[(size_t)b->taps_off[(size_t)c]], (size_t)std::min(taps_cap, nt * 16) * 4);
+    if (taps) std::memcpy(taps, &b->taps.all[(size_t)b->taps.off[(size_t)c]], (size_t)std::min(taps_cap, nt * 16) * 4);
     if (filter_iq) std::memcpy(filter_iq, &b->filters_all[(size_t)c * 2 * BE_FFT_MAX * 2], BE_FFT_MAX * 8);
     if (nco_inc) *nco_inc = b->h_chan[(size_t)c].nco_inc;
     return SDRX_OK;
@@ -437,7 +349,8 @@ int backend_view(sdrx_backend_t* b, int32_t c, BackendView* v)
 {
     if (!b || c < 0 || c >= b->n_ch || !v) { set_error("backend_view: bad argument"); return SDRX_EINVAL; }
     const ChanHost& h = b->ch[(size_t)c];
-    v->out = h.cfg.discri ? h.real_out.p : h.cplx_out.p;
+    const BeBufs u = h.placed();
+    v->out = h.cfg.discri ? static_cast<const void*>(u.real_out) : static_cast<const void*>(u.cplx_out);
     v->n_out = reinterpret_cast<const int*>(reinterpret_cast<const char*>(b->d_chan + c) + offsetof(BeChan, n_out));
     return SDRX_OK;
 }

@@ -19,15 +19,35 @@ using namespace sdrx;
 namespace {
 
 struct WfmHost {
-    DevBuf head, tail, arg, flag, blk, dem, sched, audio, stage_in;
+    DevBuf arena;                 // work()'s layout for cap_in samples
+    DevBuf stage_in;              // host-pointer feeds
     uint32_t* pend[2] = { nullptr, nullptr };
     int cur = 0;
     int64_t cap_in = 0;
     int pending = 0;              // host mirror of WfmChan::pending (a function of the feed lengths only)
 };
 
-// per-block scratch of one channel, carved out of one allocation
-constexpr size_t BLK_BYTES = sizeof(WfmClamp) + sizeof(double) + sizeof(float) + 3 * sizeof(int);
+// One channel's work arena for feeds of up to cap_in samples.  tail's slot 0 (ovlbuf) and the front of dem (the resampler's
+// window) carry state from feed to feed.
+void work(Carver& k, int64_t cap_in, WfmBufs& u)
+{
+    const size_t n_blk = (size_t)(cap_in + WFM_H) / WFM_H + 1;       // pending (< 512) + new
+    const size_t n_s = n_blk * WFM_H;
+    u.head = k.take<float2>(n_s);
+    u.tail = k.take_kept<float2>(n_s + WFM_H, WFM_H);
+    u.arg = k.take<float>(n_s);
+    u.flag = k.take<uint8_t>(n_s);
+    u.blk_sum = k.take<double>(n_blk);
+    u.blk_map = k.take<WfmClamp>(n_blk);
+    u.blk_peak = k.take<float>(n_blk);
+    u.blk_state = k.take<int>(n_blk);
+    u.blk_first = k.take<int>(n_blk);
+    u.blk_last = k.take<int>(n_blk + 64 / sizeof(int));
+    u.dem = k.take_kept<float>(WFM_HIST + n_s + WFM_HIST, WFM_HIST);
+    // every audio sample consumes at least one demodulated sample (step >= 1)
+    u.sched = k.take<uint2>(n_s + 8);
+    u.audio = k.take<int16_t>(n_s + 8);
+}
 
 } // namespace
 
@@ -40,10 +60,11 @@ struct sdrx_wfm {
     WfmChan* d_chan = nullptr;
     WfmBufs* d_bufs = nullptr;
     WfmBufs* h_bufs = nullptr;    // pinned: the per-feed table goes to the device in one async copy
-    hipEvent_t bufs_ev = nullptr, prod_ev = nullptr, cons_ev = nullptr;
+    hipEvent_t bufs_ev = nullptr;
+    hipEvent_t prod_ev = nullptr, cons_ev = nullptr;       // device-side ordering against a producer stream (sdrx_wfm_feed_bank)
     float* d_nco = nullptr; float* d_taps = nullptr; float2* d_filters = nullptr; float* d_utbl = nullptr;
-    std::vector<float> taps_all, filters_all;
-    std::vector<int> taps_off, ntaps;
+    InterpTables taps;
+    std::vector<float> filters_all;
     bool any_dyadic = false, any_serial = false;
 };
 
@@ -65,47 +86,12 @@ static int validate(int32_t n_ch, const sdrx_wfm_cfg* cfg)
     return SDRX_OK;
 }
 
-static int ensure_capacity(sdrx_wfm* b, int c, int64_t n_in)
-{
-    WfmHost& h = b->ch[(size_t)c];
-    if (n_in <= h.cap_in) return SDRX_OK;
-    int64_t cap = h.cap_in ? h.cap_in : 4096;
-    while (cap < n_in) cap *= 2;
-    const size_t n_blk = (size_t)(cap + WFM_H) / WFM_H + 1;          // pending (< 512) + new
-    const size_t n_s = n_blk * WFM_H;
-    // tail slot 0 (ovlbuf) and the front of dem (the resampler window) carry state: keep them
-    auto grow_keep = [&](DevBuf& buf, size_t bytes, size_t keep) -> int {
-        if (bytes <= buf.cap) return SDRX_OK;
-        void* np = nullptr;
-        SDRX_HIP(hipMalloc(&np, bytes));
-        SDRX_HIP(hipMemsetAsync(np, 0, bytes, b->core.stream));
-        if (buf.p && keep) SDRX_HIP(hipMemcpyAsync(np, buf.p, keep, hipMemcpyDeviceToDevice, b->core.stream));
-        SDRX_HIP(hipStreamSynchronize(b->core.stream));
-        if (buf.p) (void)hipFree(buf.p);
-        buf.p = np; buf.cap = bytes;
-        return SDRX_OK;
-    };
-    int rc;
-    if ((rc = grow_keep(h.head, n_s * 8, 0))) return rc;
-    if ((rc = grow_keep(h.tail, (n_s + WFM_H) * 8, WFM_H * 8))) return rc;
-    if ((rc = grow_keep(h.arg, n_s * 4, 0))) return rc;
-    if ((rc = grow_keep(h.flag, n_s, 0))) return rc;
-    if ((rc = grow_keep(h.blk, n_blk * BLK_BYTES + 64, 0))) return rc;
-    if ((rc = grow_keep(h.dem, (WFM_HIST + n_s + WFM_HIST) * 4, WFM_HIST * 4))) return rc;
-    // every audio sample consumes at least one demodulated sample (step >= 1)
-    if ((rc = grow_keep(h.sched, (n_s + 8) * 8, 0))) return rc;
-    if ((rc = grow_keep(h.audio, (n_s + 8) * 2, 0))) return rc;
-    h.cap_in = cap;
-    return SDRX_OK;
-}
-
 static int upload_fresh_state(sdrx_wfm* b)
 {
     SDRX_HIP(hipMemcpyAsync(b->d_chan, b->h_chan.data(), (size_t)b->n_ch * sizeof(WfmChan), hipMemcpyHostToDevice, b->core.stream));
     for (auto& h : b->ch) {
         for (int i = 0; i < 2; i++) SDRX_HIP(hipMemsetAsync(h.pend[i], 0, WFM_H * 4, b->core.stream));
-        if (h.tail.p) SDRX_HIP(hipMemsetAsync(h.tail.p, 0, WFM_H * 8, b->core.stream));
-        if (h.dem.p) SDRX_HIP(hipMemsetAsync(h.dem.p, 0, WFM_HIST * 4, b->core.stream));
+        int rc = demod_clear_kept<WfmBufs>(h.arena, h.cap_in, b->core.stream, work); if (rc) return rc;
         h.pending = 0;
     }
     SDRX_HIP(hipStreamSynchronize(b->core.stream));
@@ -120,8 +106,7 @@ int sdrx_wfm_destroy(sdrx_wfm_t* b)
     (void)hipSetDevice(b->core.device);
     if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
     for (auto& h : b->ch) {
-        h.head.release(); h.tail.release(); h.arg.release(); h.flag.release(); h.blk.release();
-        h.dem.release(); h.sched.release(); h.audio.release(); h.stage_in.release();
+        h.arena.release(); h.stage_in.release();
         for (int i = 0; i < 2; i++) if (h.pend[i]) (void)hipFree(h.pend[i]);
     }
     if (b->d_chan) (void)hipFree(b->d_chan);
@@ -151,72 +136,29 @@ int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_c
     b->n_ch = n_ch;
     b->cfg.assign(cfg, cfg + n_ch);
     b->ch.resize((size_t)n_ch); b->h_chan.resize((size_t)n_ch);
-    b->taps_off.resize((size_t)n_ch); b->ntaps.resize((size_t)n_ch);
 
     // NCO table (nco.cpp:30-39) and g_fft cosine table (gfft.h:141-150)
-    std::vector<float> nco(WFM_NCO_N);
-    for (int i = 0; i < WFM_NCO_N; i++) nco[(size_t)i] = (float)std::cos((2.0 * PI_D * i) / WFM_NCO_N);
-    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_nco), WFM_NCO_N * 4), sdrx_wfm_destroy(b));
-    SDRX_HIP_ELSE(hipMemcpy(b->d_nco, nco.data(), WFM_NCO_N * 4, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
-    {
-        const int n = WFM_FFT;
-        std::vector<float> utbl((size_t)n / 4 + 1);
-        utbl[0] = 1.0f;
-        for (int i = 1; i < n / 4; i++) utbl[(size_t)i] = (float)std::cos((2.0 * 3.141592653589793238462643383279502884197 * (float)i) / (float)n);
-        utbl[(size_t)n / 4] = 0.0f;
-        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_utbl), ((size_t)n / 4 + 1) * 4), sdrx_wfm_destroy(b));
-        SDRX_HIP_ELSE(hipMemcpy(b->d_utbl, utbl.data(), ((size_t)n / 4 + 1) * 4, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
-    }
+    rc = design_upload(&b->d_nco, design_nco_table(WFM_NCO_N));
+    if (!rc) rc = design_upload(&b->d_utbl, design_gfft_table(WFM_FFT));
+    if (rc) { sdrx_wfm_destroy(b); return rc; }
     SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_filters), (size_t)n_ch * WFM_FFT * 8), sdrx_wfm_destroy(b));
     b->filters_all.assign((size_t)n_ch * WFM_FFT * 2, 0.0f);
     for (int c = 0; c < n_ch; c++) {
         const sdrx_wfm_cfg& k = cfg[c];
         WfmHost& h = b->ch[(size_t)c];
-        // m_interpolator.create(16, inputSampleRate, afBandwidth): channels with the same arguments share one tap table
-        int same = -1;
-        for (int p = 0; p < c && same < 0; p++) if (cfg[p].in_rate == k.in_rate && cfg[p].af_bandwidth == k.af_bandwidth) same = p;
-        if (same >= 0) {
-            b->taps_off[(size_t)c] = b->taps_off[(size_t)same]; b->ntaps[(size_t)c] = b->ntaps[(size_t)same];
-        } else {
-            std::vector<float> poly; int nt = 0;
-            design_interp(16, (double)k.in_rate, (double)k.af_bandwidth, 4.5, poly, &nt);
-            b->taps_off[(size_t)c] = (int)b->taps_all.size(); b->ntaps[(size_t)c] = nt;
-            b->taps_all.insert(b->taps_all.end(), poly.begin(), poly.end());
-        }
-        // Real lowCut = -(rfBandwidth / 2.0) / inputSampleRate, hiCut = +...; m_rfFilter->create_filter(lowCut, hiCut):
-        // windowed sinc in the first 512 bins, forward FFT (the kernel code of the data path), normalised to max |H| over
-        // bins 0..511 (fftfilt.cpp:108-146)
+        // m_interpolator.create(16, inputSampleRate, afBandwidth)
+        b->taps.add((double)k.in_rate, (double)k.af_bandwidth, 4.5);
+        // Real lowCut = -(rfBandwidth / 2.0) / inputSampleRate, hiCut = +...; m_rfFilter->create_filter(lowCut, hiCut)
         const float f1 = (float)(-((double)k.rf_bandwidth / 2.0) / (double)k.in_rate);
         const float f2 = (float)(((double)k.rf_bandwidth / 2.0) / (double)k.in_rate);
-        {
-            const int flen = WFM_FFT, h2 = flen / 2;
-            std::vector<float> f((size_t)flen * 2, 0.0f);
-            const bool lp = f2 != 0, hp = f1 != 0;
-            for (int i = 0; i < h2; i++) {
-                float v = 0;
-                if (lp) v += fsinc(f2, i, h2);
-                if (hp) v -= fsinc(f1, i, h2);
-                f[(size_t)(2 * i)] = v;
-            }
-            if (hp && f2 < f1) f[(size_t)(2 * (h2 / 2))] += 1;
-            for (int i = 0; i < h2; i++) { const float w = blackman(i, h2); f[(size_t)(2 * i)] *= w; f[(size_t)(2 * i + 1)] *= w; }
-            float2* dst = b->d_filters + (size_t)c * WFM_FFT;
-            SDRX_HIP_ELSE(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
-            hipLaunchKernelGGL(be_fft_design_kernel<WFM_FFT>, dim3(1), dim3(WFM_FFT / 8), 0, b->core.stream, dst, b->d_utbl);
-            SDRX_HIP_ELSE(hipGetLastError(), sdrx_wfm_destroy(b));
-            SDRX_HIP_ELSE(hipStreamSynchronize(b->core.stream), sdrx_wfm_destroy(b));
-            SDRX_HIP_ELSE(hipMemcpy(f.data(), dst, (size_t)flen * 8, hipMemcpyDeviceToHost), sdrx_wfm_destroy(b));
-            float scale = 0;
-            for (int i = 0; i < h2; i++) { const float mag = hypotf(f[(size_t)(2 * i)], f[(size_t)(2 * i + 1)]); if (mag > scale) scale = mag; }
-            if (scale != 0) for (int i = 0; i < flen * 2; i++) f[(size_t)i] /= scale;
-            SDRX_HIP_ELSE(hipMemcpy(dst, f.data(), (size_t)flen * 8, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
-            std::memcpy(&b->filters_all[(size_t)c * WFM_FFT * 2], f.data(), (size_t)flen * 8);
-        }
+        rc = design_fft_filter<WFM_FFT>(b->d_filters + (size_t)c * WFM_FFT, b->d_utbl, b->core.stream, &b->filters_all[(size_t)c * WFM_FFT * 2],
+                                        [&](float* f, int h2) { fftfilt_fill_band(f1, f2, f, h2); });
+        if (rc) { sdrx_wfm_destroy(b); return rc; }
         WfmChan& s = b->h_chan[(size_t)c];
         std::memset(&s, 0, sizeof s);
         s.nco_inc = (int)(((float)k.nco_freq * WFM_NCO_N) / (float)k.in_rate);          // NCO::setFreq (float math, truncation)
         s.step = (float)k.in_rate / (float)k.audio_rate;
-        s.ntaps = b->ntaps[(size_t)c]; s.taps_off = b->taps_off[(size_t)c];
+        s.ntaps = b->taps.ntaps[(size_t)c]; s.taps_off = b->taps.off[(size_t)c];
         s.filt_off = c * WFM_FFT;
         const float excursion = k.rf_bandwidth / (float)k.in_rate;                        // m_fmExcursion
         s.fm_scaling = 1.0f / excursion;
@@ -224,19 +166,14 @@ int sdrx_wfm_create(sdrx_wfm_t** out, int device, int32_t n_ch, const sdrx_wfm_c
         s.cap_f = k.rf_bandwidth / 10; s.open_f = k.rf_bandwidth / 20;
         s.cap = wfm_counter_cap(s.cap_f);
         s.volume = k.volume; s.mute = k.audio_mute ? 1 : 0;
-        s.dy_q = -1; s.dy_S = 0;
-        if (!getenv("SDRX_WFM_SERIAL_SCHEDULE"))
-            for (int q = 0; q <= 10; q++) {
-                const float v = s.step * (float)(1 << q);                                  // exact (power of two)
-                if (v == std::floor(v) && v < (float)(1 << 20)) { s.dy_q = q; s.dy_S = (int)v; break; }
-            }
+        design_dyadic_step(s.step, "SDRX_WFM_SERIAL_SCHEDULE", &s.dy_q, &s.dy_S);
         (s.dy_q >= 0 ? b->any_dyadic : b->any_serial) = true;
         s.distance = s.step;                                                               // m_interpolatorDistanceRemain starts at in / audio
         if (s.ntaps > WFM_HIST) { set_error("sdrx_wfm_create: resampler window does not fit"); sdrx_wfm_destroy(b); return SDRX_EINVAL; }
         for (int i = 0; i < 2; i++) SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.pend[i]), WFM_H * 4), sdrx_wfm_destroy(b));
     }
-    SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_taps), b->taps_all.size() * 4), sdrx_wfm_destroy(b));
-    SDRX_HIP_ELSE(hipMemcpy(b->d_taps, b->taps_all.data(), b->taps_all.size() * 4, hipMemcpyHostToDevice), sdrx_wfm_destroy(b));
+    rc = design_upload(&b->d_taps, b->taps.all);
+    if (rc) { sdrx_wfm_destroy(b); return rc; }
     SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_chan), (size_t)n_ch * sizeof(WfmChan)), sdrx_wfm_destroy(b));
     SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_bufs), (size_t)n_ch * sizeof(WfmBufs)), sdrx_wfm_destroy(b));
     SDRX_HIP_ELSE(hipHostMalloc(reinterpret_cast<void**>(&b->h_bufs), (size_t)n_ch * sizeof(WfmBufs), hipHostMallocDefault), sdrx_wfm_destroy(b));
@@ -268,8 +205,9 @@ static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n
     int rc = demod_check_lengths(b->n_ch, n_per_ch, "sdrx_wfm_feed"); if (rc) return rc;
     rc = demod_check_dev_pointers(b->n_ch, d_iq, n_per_ch, "sdrx_wfm_feed"); if (rc) return rc;
     for (int c = 0; c < b->n_ch; c++) {
-        rc = ensure_capacity(b, c, std::max<int64_t>(n_per_ch[c], 1)); if (rc) return rc;
-        const int64_t nb = (b->ch[(size_t)c].pending + n_per_ch[c]) / WFM_H;
+        WfmHost& h = b->ch[(size_t)c];
+        rc = demod_grow_arena<WfmBufs>(h.arena, h.cap_in, std::max<int64_t>(n_per_ch[c], 1), b->core.stream, work); if (rc) return rc;
+        const int64_t nb = (h.pending + n_per_ch[c]) / WFM_H;
         max_blocks = std::max(max_blocks, nb);
         // every audio sample after the first of a feed consumes >= floor(step) demodulated samples
         const int64_t per_out = std::max<int64_t>(1, (int64_t)std::floor(b->h_chan[(size_t)c].step));
@@ -279,19 +217,10 @@ static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n
     for (int c = 0; c < b->n_ch; c++) {
         WfmHost& h = b->ch[(size_t)c];
         WfmBufs& u = b->h_bufs[c];
-        const size_t n_blk = (size_t)(h.cap_in + WFM_H) / WFM_H + 1;
         u.in = reinterpret_cast<const uint32_t*>(d_iq[c]);
         u.pend = h.pend[h.cur]; u.pend_next = h.pend[h.cur ^ 1];
-        u.head = static_cast<float2*>(h.head.p); u.tail = static_cast<float2*>(h.tail.p);
-        u.arg = static_cast<float*>(h.arg.p); u.flag = static_cast<uint8_t*>(h.flag.p);
-        char* p = static_cast<char*>(h.blk.p);
-        u.blk_sum = reinterpret_cast<double*>(p); p += n_blk * sizeof(double);
-        u.blk_map = reinterpret_cast<WfmClamp*>(p); p += n_blk * sizeof(WfmClamp);
-        u.blk_peak = reinterpret_cast<float*>(p); p += n_blk * sizeof(float);
-        u.blk_state = reinterpret_cast<int*>(p); p += n_blk * sizeof(int);
-        u.blk_first = reinterpret_cast<int*>(p); p += n_blk * sizeof(int);
-        u.blk_last = reinterpret_cast<int*>(p);
-        u.dem = static_cast<float*>(h.dem.p); u.sched = static_cast<uint2*>(h.sched.p); u.audio = static_cast<int16_t*>(h.audio.p);
+        Carver k{static_cast<char*>(h.arena.p)};
+        work(k, h.cap_in, u);
         u.n_in = n_per_ch[c];
     }
     rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
@@ -306,11 +235,7 @@ static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n
     // lanes whose channel the closed form took exit at once (prep's off-grid guard can hand a channel back)
     hipLaunchKernelGGL(wfm_sched_walk_kernel, dim3(gc), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch);
     SDRX_HIP(hipGetLastError());
-    const bool cross = producer && producer != b->core.stream;
-    if (cross) {
-        SDRX_HIP(hipEventRecord(b->prod_ev, producer));
-        SDRX_HIP(hipStreamWaitEvent(b->core.stream, b->prod_ev, 0));
-    }
+    rc = demod_stream_after(b->core.stream, producer, b->prod_ev); if (rc) return rc;
     if (nblk) {
         hipLaunchKernelGGL(wfm_fft_kernel, dim3(nblk, nc), dim3(WFM_FFT / 8), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl, b->d_nco);
         SDRX_HIP(hipGetLastError());
@@ -318,10 +243,7 @@ static int feed_common(sdrx_wfm* b, const int16_t* const* d_iq, const int64_t* n
     }
     hipLaunchKernelGGL(wfm_pend_kernel, dim3(nc), dim3(WFM_H), 0, b->core.stream, b->d_chan, b->d_bufs);
     SDRX_HIP(hipGetLastError());
-    if (cross) {
-        SDRX_HIP(hipEventRecord(b->cons_ev, b->core.stream));
-        SDRX_HIP(hipStreamWaitEvent(producer, b->cons_ev, 0));
-    }
+    rc = demod_stream_after(producer, b->core.stream, b->cons_ev); if (rc) return rc;
     if (nblk) {
         hipLaunchKernelGGL(wfm_level_kernel, dim3(nblk, nc), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs);
         SDRX_HIP(hipGetLastError());
@@ -382,7 +304,7 @@ int64_t sdrx_wfm_read(sdrx_wfm_t* b, int32_t c, int16_t* audio, int64_t cap)
     int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
     const int64_t n = std::min<int64_t>(s.n_out, cap);
     if (n == 0) return 0;
-    SDRX_HIP(hipMemcpy(audio, b->ch[(size_t)c].audio.p, (size_t)n * 2, hipMemcpyDeviceToHost));
+    SDRX_HIP(hipMemcpy(audio, demod_place<WfmBufs>(b->ch[(size_t)c].arena.p, b->ch[(size_t)c].cap_in, work).audio, (size_t)n * 2, hipMemcpyDeviceToHost));
     return n;
 }
 
@@ -391,7 +313,7 @@ int sdrx_wfm_last_dev(sdrx_wfm_t* b, int32_t c, const int16_t** d_audio, int64_t
     if (!b || c < 0 || c >= b->n_ch || !d_audio || !n) { set_error("sdrx_wfm_last_dev: bad argument"); return SDRX_EINVAL; }
     WfmChan s;
     int rc = demod_fetch_state(b->core, b->d_chan, c, &s); if (rc) return rc;
-    *d_audio = static_cast<const int16_t*>(b->ch[(size_t)c].audio.p);
+    *d_audio = demod_place<WfmBufs>(b->ch[(size_t)c].arena.p, b->ch[(size_t)c].cap_in, work).audio;
     *n = s.n_out;
     return SDRX_OK;
 }
@@ -420,9 +342,9 @@ int sdrx_wfm_get_design(sdrx_wfm_t* b, int32_t c, int32_t* ntaps_per_phase, floa
                         float* filter_iq, int32_t* nco_inc, float* squelch_level)
 {
     if (!b || c < 0 || c >= b->n_ch) { set_error("sdrx_wfm_get_design: bad channel"); return SDRX_EINVAL; }
-    const int nt = b->ntaps[(size_t)c];
+    const int nt = b->taps.ntaps[(size_t)c];
     if (ntaps_per_phase) *ntaps_per_phase = nt;
-    if (taps && taps_cap > 0) std::memcpy(taps, &b->taps_all[(size_t)b->taps_off[(size_t)c]], (size_t)std::min(taps_cap, nt * 16) * 4);
+    if (taps && taps_cap > 0) std::memcpy(taps, &b->taps.all[(size_t)b->taps.off[(size_t)c]], (size_t)std::min(taps_cap, nt * 16) * 4);
     if (filter_iq) std::memcpy(filter_iq, &b->filters_all[(size_t)c * WFM_FFT * 2], WFM_FFT * 8);
     if (nco_inc) *nco_inc = b->h_chan[(size_t)c].nco_inc;
     if (squelch_level) *squelch_level = b->h_chan[(size_t)c].squelch_level;
