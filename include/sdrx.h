@@ -689,8 +689,8 @@ int sdrx_am_last_launch(const sdrx_am_t* h, char* kernel_name, int name_cap,
                         int* grid, int* block, int* lds_bytes);
 
 /* ------------------------------------------------------------------------------------------
- * NFM demodulator bank: NFMDemod::feed (plugins/channelrx/demodnfm/nfmdemod.cpp:140-332) with m_deltaSquelch = false and
- * m_ctcssOn = false (the defaults), N channels per handle, each fed with int16 I/Q at the channelizer's output rate:
+ * NFM demodulator bank: NFMDemod::feed (plugins/channelrx/demodnfm/nfmdemod.cpp:140-332), N channels per handle, each fed with
+ * int16 I/Q at the channelizer's output rate.  With the power squelch (CTCSS and the AF squelch: sdrx_nfm_create_ex, below):
  *     c = Complex(re, im) * m_nco.nextIQ();  m_interpolator.decimate(&dist, c, &ci)        as sdrx_backend_* (filt_mode 0)
  *     per ci: demod = m_phaseDiscri.phaseDiscriminatorDelta(ci, magsqRaw, dev); magsq = (Real)(magsqRaw / 2^30);
  *             m_movingAverage(magsq) (MovingAverageUtil<Real, double, 32>); level sum, peak, count;
@@ -712,8 +712,43 @@ int sdrx_am_last_launch(const sdrx_am_t* h, char* kernel_name, int name_cap,
  *     clear; applyAudioSampleRate's resize(rate / 2) is not on this path)
  *   - readBack clamps its delay to the line's size, and at delay == size the slot it names is the one just written: for
  *     m_squelchGate >= 24000 the Bandpass is given the current sample, not one 24000 back
- *   - left out: the AF squelch (m_deltaSquelch) and CTCSS (Goertzel recurrences on libm cosines that feed the GUI), AudioFifo,
- *     the interpolating branch (audio_rate > in_rate: SDRX_EINVAL), and mid-stream retune -- a channel is configured at creation
+ *   - left out: AudioFifo, the interpolating branch (audio_rate > in_rate: SDRX_EINVAL), mid-stream retune -- a channel is
+ *     configured at creation -- and applyAudioSampleRate's low-rate AF tones and delay-line resize
+ * AF squelch (m_deltaSquelch, sdrx_nfm_create_ex; sdrbase/dsp/afsquelch.cpp, all in double).  The squelch source of a sample is then
+ *     if (m_afSquelch.analyze(demod * comp)) { m_afSquelchOpen = m_afSquelch.evaluate();
+ *                                              if (!m_afSquelchOpen) m_squelchDelayLine.zeroBack(audio_rate / 10); }
+ *     up = m_afSquelchOpen;   write(up ? demod * comp : 0), counter, open, readBack as above.
+ *   The 32-sample power average still runs, for sdrx_nfm_levels.  Without delta_squelch the AF squelch is never called.
+ *   - the constructor's setCoefficients(audio_rate / 2000, 600, audio_rate, 200, 0, {1000.0, 6000.0}): each tone capped at 0.4 *
+ *     audio_rate, coef = 2.0 * cos((2.0 * M_PI * tone) / (double) rate); applySettings then sets m_squelchLevel = (Real)((-squelch)
+ *     / 1000.0) ("negative millis"), the threshold to its double, and calls reset()
+ *   - analyze is feedback on every sample; a block is N + 1 samples (the test is m_samplesProcessed < m_N before the increment).
+ *     At a block end feedForward computes the powers, feeds the two MovingAverage<double> (sum += value - oldest: the difference
+ *     first, then one rounded add), zeroes u and calls evaluate() itself.  For the first 600 block ends analyze returns false;
+ *     from then on true, and NFMDemod's evaluate() is a second one: the counter moves twice per block
+ *   - the two MovingAverage histories have 128 entries, not 600: AFSquelch's constructor makes them with m_nbAvg = 128, and
+ *     setCoefficients' m_movingAverages.resize(m_nTones, MovingAverage<double>(600, 0.0)) finds the vector at that size already and
+ *     leaves its elements alone.  Only the warm-up count is 600 (the recorder around the class decides this)
+ *   - evaluate: maxPower == 0.0 (no sum above 0) returns the old state untouched; open condition minPower / maxPower < threshold
+ *     && minIndex > maxIndex: counter++ up to 200, else-- if above 200, else 0; isOpen = counter >= 200
+ *   - zeroBack zeroes ONE of the two copies the delay line keeps of each element, m_data[cur + size - i] for i < min(reach, size):
+ *     a read returns 0 or the written value depending on the laps the write, the event and the read fall in.  The line is kept
+ *     as the class keeps it, both copies and the write position carried across feeds
+ * CTCSS (m_ctcssOn, sdrx_nfm_create_ex).  Per audio sample m_sampleCount++ comes first, muted or not.  Then, unmuted:
+ *     open:   ctcss_sample = m_lowpass.filter(demod * m_discriCompensation)    the current, undelayed sample, every open sample
+ *             if ((m_sampleCount & 7) == 7 && m_ctcssDetector.analyze(&ctcss_sample))        at every audio rate
+ *                 m_ctcssIndex = toneDetected ? maxPowerIndex + 1 : 0
+ *             m_ctcssIndexSelected && m_ctcssIndexSelected != m_ctcssIndex: 0, and the Bandpass does not advance;  else as above
+ *     closed: m_ctcssIndex = 0; the detector's partial block and samplesProcessed stay
+ *   a muted channel runs none of it: the detector, both FIRs and m_ctcssIndex stand still.
+ *   - m_lowpass.create(301, audio_rate, 250.0); m_ctcssDetector.setCoefficients(audio_rate / 16, audio_rate / 8.0f): N =
+ *     audio_rate / 16, the detector's rate is the float quotient cut to int, coef[j] = (Real)(2.0 * cos((2.0 * M_PI * (double)
+ *     toneSet[j]) / (double) rate)) for the 32 EIA tones of the constructor, computed once on the host
+ *   - feedback: u0 = (in + (coef * u0)) - u1;  feedForward: power = ((u0 * u0) + (u1 * u1)) - ((coef * u0) * u1), u0 = u1 = 0;
+ *     evaluatePower: float sum over j = 0..31 in order, the first strict maximum above 0, toneDetected = maxPower > sum / 32 + 2.0f
+ *   - u0, u1 and power start at 0 (CTCSSDetector allocates them with new Real[] and NFMDemod never calls its reset())
+ *   - of m_sampleCount only the low three bits are carried
+ *   The audio, m_ctcssIndex, its changes and the detector's powers are bit-identical to the strict-IEEE scalar reference build.
  * ------------------------------------------------------------------------------------------ */
 typedef struct sdrx_nfm sdrx_nfm_t;
 typedef struct sdrx_nfm_cfg {
@@ -729,6 +764,17 @@ typedef struct sdrx_nfm_cfg {
     int32_t audio_mute;       /* m_audioMute */
 } sdrx_nfm_cfg;
 int sdrx_nfm_create(sdrx_nfm_t** out, int device, int32_t n_ch, const sdrx_nfm_cfg* cfg);
+typedef struct sdrx_nfm_tone_cfg {
+    int32_t delta_squelch;   /* m_deltaSquelch: 1 = AF squelch; cfg.squelch is then "negative millis" */
+    int32_t ctcss_on;        /* m_ctcssOn */
+    int32_t ctcss_index;     /* m_ctcssIndex -> m_ctcssIndexSelected: 0 = any tone, 1..32 = that EIA tone */
+    int32_t reserved;        /* 0 */
+} sdrx_nfm_tone_cfg;
+/* tone[c] goes with cfg[c]; NULL: all zero, which is sdrx_nfm_create.  Channels of one handle may mix every combination; one
+ * with both options off gives the audio of sdrx_nfm_create bit for bit, and a handle with no option on in any channel launches
+ * the kernels of sdrx_nfm_create and no others (a handle with an AF squelch channel adds nfm_af_walk_kernel, one with a CTCSS
+ * channel three more).  Every other entry point works unchanged on such a handle. */
+int sdrx_nfm_create_ex(sdrx_nfm_t** out, int device, int32_t n_ch, const sdrx_nfm_cfg* cfg, const sdrx_nfm_tone_cfg* tone);
 int sdrx_nfm_destroy(sdrx_nfm_t* h);
 /* the state of a fresh handle with the same configuration */
 int sdrx_nfm_reset(sdrx_nfm_t* h);
@@ -752,6 +798,23 @@ int sdrx_nfm_levels(sdrx_nfm_t* h, int32_t ch, double* magsq, double* sum, doubl
  * m_squelchGate in samples */
 int sdrx_nfm_get_design(sdrx_nfm_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
                         float* bandpass_taps, int32_t* nco_inc, float* squelch_level, int32_t* squelch_gate);
+/* m_ctcssIndex after the last feed (0: none), its tone in Hz (0 for none), and how many times it has changed since create / reset */
+int sdrx_nfm_ctcss(sdrx_nfm_t* h, int32_t ch, int32_t* index, float* tone_hz, int64_t* n_changes);
+/* the changes of m_ctcssIndex during the last feed, i.e. what MsgReportCTCSSFreq carries: audio sample position in the feed, new
+ * index.  Returns how many there were (may exceed cap; <0: error) */
+int64_t sdrx_nfm_ctcss_events(sdrx_nfm_t* h, int32_t ch, int64_t* at, int32_t* index, int64_t cap);
+/* power[32] and toneDetected / maxPowerIndex of the last completed detector block (blocks completed since create / reset in
+ * *n_blocks) */
+int sdrx_nfm_ctcss_powers(sdrx_nfm_t* h, int32_t ch, float* power32, int32_t* detected, int32_t* max_index, int64_t* n_blocks);
+/* m_afSquelchOpen after the last feed; AFSquelch's two moving-average sums and its m_squelchCount, bit-identical to the
+ * reference's.  A channel without delta_squelch never calls its AFSquelch: 0, {0.0, 0.0}, 0 */
+int sdrx_nfm_af_squelch(sdrx_nfm_t* h, int32_t ch, int32_t* open, double* sums2, int32_t* count);
+/* design products: CTCSS N, detector rate, coef[32]; the 151 folded Lowpass taps; AF N, tones[2], coef[2], threshold -- AFSquelch as
+ * the constructor's setCoefficients(audio_rate / 2000, 600, audio_rate, 200, 0, {1000.0, 6000.0}) leaves it: each tone capped at
+ * 0.4 * audio_rate, coef = 2.0 * cos((2.0 * M_PI * tone) / (double) rate), threshold (double) m_squelchLevel with delta_squelch, 0.0
+ * without.  sdrx_nfm_get_design's squelch_level is m_squelchLevel as the mode defines it */
+int sdrx_nfm_get_tone_design(sdrx_nfm_t* h, int32_t ch, int32_t* ctcss_n, int32_t* ctcss_rate, float* coef32,
+                             float* lowpass_taps, int32_t* af_n, double* af_tones2, double* af_coef2, double* af_threshold);
 int sdrx_nfm_sync(sdrx_nfm_t* h);
 int sdrx_nfm_set_stream(sdrx_nfm_t* h, void* hip_stream);
 int sdrx_nfm_get_stream(sdrx_nfm_t* h, void** hip_stream);

@@ -172,6 +172,12 @@ def lib() -> C.CDLL:
         "sdrx_am_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_am_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
         "sdrx_nfm_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_nfm_create_ex": (C.c_int, [pp, C.c_int, i32, vp, vp]),
+        "sdrx_nfm_ctcss": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(i64)]),
+        "sdrx_nfm_ctcss_events": (i64, [vp, i32, vp, vp, i64]),
+        "sdrx_nfm_ctcss_powers": (C.c_int, [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]),
+        "sdrx_nfm_af_squelch": (C.c_int, [vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]),
+        "sdrx_nfm_get_tone_design": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp, C.POINTER(i32), vp, vp, C.POINTER(C.c_double)]),
         "sdrx_nfm_destroy": (C.c_int, [vp]),
         "sdrx_nfm_reset": (C.c_int, [vp]),
         "sdrx_nfm_feed": (C.c_int, [vp, vp, vp]),
@@ -876,10 +882,21 @@ class AmCfg(C.Structure):
 
 
 class NfmCfg(C.Structure):
-    """sdrx_nfm_cfg: one NFMDemod, power squelch, no CTCSS (in_rate, nco_freq = -frequencyOffset, audio_rate, NFMDemodSettings)"""
+    """sdrx_nfm_cfg: one NFMDemod, power squelch (in_rate, nco_freq = -frequencyOffset, audio_rate, NFMDemodSettings)"""
     _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
                 ("rf_bandwidth", C.c_float), ("af_bandwidth", C.c_float), ("fm_deviation", C.c_int32), ("volume", C.c_float),
                 ("squelch", C.c_float), ("squelch_gate", C.c_int32), ("audio_mute", C.c_int32)]
+
+
+class NfmToneCfg(C.Structure):
+    """sdrx_nfm_tone_cfg: the tone options of one NFMDemod (delta_squelch 1 = AF squelch, NfmCfg.squelch is then "negative millis";
+    ctcss_index 0 = any tone, 1..32 = that EIA tone)"""
+    _fields_ = [("delta_squelch", C.c_int32), ("ctcss_on", C.c_int32), ("ctcss_index", C.c_int32), ("reserved", C.c_int32)]
+
+
+#: the 32 EIA tones of CTCSSDetector, index 1..32 of NfmToneCfg.ctcss_index
+CTCSS_TONES = (67.0, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8, 118.8, 123.0, 127.3, 131.8,
+               136.5, 141.3, 146.2, 151.4, 156.7, 162.2, 167.9, 173.8, 179.9, 186.2, 192.8, 203.5)
 
 
 class SsbCfg(C.Structure):
@@ -986,9 +1003,58 @@ class AmDemodBank(_DemodBank):
 
 
 class NfmDemodBank(_DemodBank):
-    """N narrowband-FM demodulators (NFMDemod::feed, power squelch, no CTCSS): int16 I/Q at the channelizer's output rate in,
-    mono qint16 audio out."""
+    """N narrowband-FM demodulators (NFMDemod::feed, power squelch): int16 I/Q at the channelizer's output rate in, mono qint16
+    audio out.  `tone`: one NfmToneCfg per channel (CTCSS), None for none."""
     _prefix, _cfg = "nfm", NfmCfg
+
+    def __init__(self, cfgs, tone=None, device: int = 0):
+        if tone is None:
+            super().__init__(cfgs, device)
+            return
+        if len(tone) != len(cfgs):
+            raise ValueError("one NfmToneCfg per channel")
+        self.n_ch = len(cfgs)
+        self._open(device, self.n_ch, (NfmCfg * self.n_ch)(*cfgs), (NfmToneCfg * self.n_ch)(*tone), create="create_ex")
+        self.cfgs = list(cfgs)
+
+    def ctcss(self, ch: int):
+        """(m_ctcssIndex after the last feed, its tone in Hz, changes since create / reset)"""
+        i, f, n = C.c_int32(), C.c_float(), C.c_int64()
+        self._call("ctcss", ch, C.byref(i), C.byref(f), C.byref(n))
+        return i.value, f.value, n.value
+
+    def ctcss_events(self, ch: int):
+        """the changes of m_ctcssIndex during the last feed: (audio sample positions, new indices)"""
+        n = self._fn("ctcss_events")(self._h, ch, None, None, 0)
+        if n < 0:
+            raise SdrxError(f"sdrx_nfm_ctcss_events rc={n}: {lib().sdrx_last_error().decode()}")
+        at, idx = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32)
+        self._fn("ctcss_events")(self._h, ch, at.ctypes.data, idx.ctypes.data, n)
+        return at[:n].copy(), idx[:n].copy()
+
+    def ctcss_powers(self, ch: int):
+        """(power[32], toneDetected, maxPowerIndex of the last completed detector block, blocks completed since create / reset)"""
+        p = np.zeros(32, np.float32)
+        d, m, n = C.c_int32(), C.c_int32(), C.c_int64()
+        self._call("ctcss_powers", ch, p.ctypes.data, C.byref(d), C.byref(m), C.byref(n))
+        return p, bool(d.value), m.value, n.value
+
+    def af_squelch(self, ch: int):
+        """(m_afSquelchOpen after the last feed, AFSquelch's two moving-average sums, its m_squelchCount)"""
+        o, k = C.c_int32(), C.c_int32()
+        sums = np.zeros(2, np.float64)
+        self._call("af_squelch", ch, C.byref(o), sums.ctypes.data, C.byref(k))
+        return bool(o.value), sums, k.value
+
+    def tone_design(self, ch: int):
+        """(CTCSS block length N, detector rate, coef[32], the 151 folded Lowpass taps, AF block length N, AF tones[2], AF coef[2],
+        AF threshold)"""
+        n, r, an, th = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        coef, lp = np.zeros(32, np.float32), np.zeros(151, np.float32)
+        at, ac = np.zeros(2, np.float64), np.zeros(2, np.float64)
+        self._call("get_tone_design", ch, C.byref(n), C.byref(r), coef.ctypes.data, lp.ctypes.data, C.byref(an), at.ctypes.data, ac.ctypes.data,
+                   C.byref(th))
+        return n.value, r.value, coef, lp, an.value, at, ac, th.value
 
     def levels(self, ch: int, reset: bool = False):
         """(m_movingAverage, m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""

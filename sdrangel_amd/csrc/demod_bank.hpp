@@ -10,7 +10,7 @@
 //                                bp_taps Bandpass taps at bp (nullptr where bp_taps is 0)
 //   hist(k, s, u)                the layout of one history set: a k.pair() per carried array
 //   fresh(s, u)                  fills a zeroed host image of one history set through u's *_next pointers
-//   work(k, n, u)                the layout of the per-feed work arena for n = capacity + work_extra + 16 elements
+//   work(k, n, s, u)             the layout of channel s's per-feed work arena for n = capacity + work_extra + 16 elements
 //   outputs_bound(k, n_in)       most outputs channel k's feed of n_in inputs can have: sizes the grids
 //   launch(b, nc, gx)            the kernel sequence with its note_launch; gx blocks of 256 cover the bound
 //   front_made(front, n, cfg)    runs on a fresh front before it is fed
@@ -79,10 +79,10 @@ struct DemodBank {
         F::hist(k, s, u);
         return k.cur.off;
     }
-    static size_t lay_work(int64_t cap_in, Bufs& u, char* base)
+    static size_t lay_work(int64_t cap_in, const Chan& s, Bufs& u, char* base)
     {
         Carver k{base};
-        F::work(k, (size_t)cap_in + F::work_extra + 16, u);
+        F::work(k, (size_t)cap_in + F::work_extra + 16, s, u);
         return k.off;
     }
 
@@ -94,7 +94,7 @@ struct DemodBank {
         while (cap < n_in) cap *= 2;
         // every output consumes at least one input (step >= 1): at most `cap` per feed, plus work_extra; nothing here carries state
         Bufs u{};
-        const size_t bytes = lay_work(cap, u, nullptr);
+        const size_t bytes = lay_work(cap, b->h_chan[(size_t)c], u, nullptr);
         SDRX_HIP(hipStreamSynchronize(b->core.stream));
         int rc = h.work.reserve(bytes); if (rc) return rc;
         h.cap_in = cap;
@@ -218,7 +218,7 @@ struct DemodBank {
             int rc = backend_view(b->front, c, &v); if (rc) return rc;
             u.*F::input = static_cast<const float2*>(v.out); u.n_ptr = v.n_out;
             lay_hist(b->h_chan[(size_t)c], u, h.hist + (size_t)h.cur * h.hist_set, h.hist + (size_t)(h.cur ^ 1) * h.hist_set);
-            lay_work(h.cap_in, u, static_cast<char*>(h.work.p));
+            lay_work(h.cap_in, b->h_chan[(size_t)c], u, static_cast<char*>(h.work.p));
         }
         int rc = demod_upload_bufs(b->d_bufs, b->h_bufs, b->n_ch, b->bufs_ev, b->core.stream); if (rc) return rc;
         rc = F::launch(*b, (unsigned)b->n_ch, (unsigned)std::max<int64_t>(1, (bound + 255) / 256)); if (rc) return rc;

@@ -10,7 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "nfm_scan.hpp"
+#include "nfm_tone_scan.hpp"
 #include "demod_psum.hpp"
 #include "demod_wg.hpp"
 #include "dsp_device.hpp"
@@ -37,6 +37,22 @@ struct NfmChan {                        // device resident: config + carried sta
     // --- per feed
     int n, n_act;                       // audio samples; open and unmuted ones
     double total_next;                  // written by nfm_psum_kernel, committed by nfm_carry_kernel
+    // --- CTCSS (nfm_tone_kernels.hpp).  Every channel carries this state, 440 B, and its row of the tap table has the Lowpass
+    // taps and the 32 coefficients whether CTCSS is on or not (ct_n is filled too): measured as no difference in a plain
+    // handle's feed.  Without ct_on no kernel reads or writes any of it
+    int ct_on, ct_sel, ct_n;            // m_ctcssOn, m_ctcssIndexSelected, CTCSSDetector::N
+    int ct_fill, ct_index;              // samplesProcessed, m_ctcssIndex
+    int ct_detected, ct_max_index;      // toneDetected, maxPowerIndex of the last completed block
+    int sc;                             // m_sampleCount & 7
+    int n_act_a, n_ev;                  // per feed: open and unmuted samples (n_act becomes those that pass the tone test); index changes
+    long long ct_changes, ct_blocks;    // index changes and completed blocks since create / reset
+    float ct_u0[32], ct_u1[32], ct_power[32];
+    // --- AF squelch (nfm_af_walk_kernel, nfm_tone_kernels.hpp); af_on 0: none of it is read or written
+    int af_on, af_n, af_z;              // m_deltaSquelch, AFSquelch::m_N, audio_rate / 10 (zeroBack's reach)
+    int af_sq_count;                    // m_squelchCount of NFMDemod in delta mode (count above is then a copy of it)
+    double af_coef[2], af_thr;          // AFSquelch::m_coef, m_threshold
+    AfState af;
+    AfDelay afq;
 };
 
 struct NfmBufs {                        // per channel device pointers (per feed capacity ensured by the host)
@@ -52,6 +68,19 @@ struct NfmBufs {                        // per channel device pointers (per feed
     float* x;                           // per open sample: the delayed sample the Bandpass is given
     int16_t* audio;
     double* blk_sum; float* blk_peak;   // per 256 samples
+    // --- CTCSS channels only
+    const float* lhist; float* lhist_next;       // last 300 Lowpass inputs
+    int* aidx_a;                        // aidx as nfm_gate_kernel left it (open and unmuted)
+    float* xl; float* xa;               // per open sample: demod * comp (the Lowpass input), and x as nfm_gate_kernel left it
+    float* ctl;                         // per sample: the Lowpass output where the detector takes one
+    float* cs; int* cpos;               // per detector sample: its input, its audio sample position
+    int* ev;                            // per sample: the index event (-1: none)
+    int* cblk;                          // per detector block ended in this feed: its maxPowerIndex (-1: no power above 0)
+    int* ev_at; int* ev_idx;            // per index change: audio sample position, new index
+    // --- AF squelch channels only: the reference's containers.  The walk alone touches them, in place, in the lower of the
+    // two history sets (af_set0)
+    const float* dl; float* dl_next;             // DoubleBufferFIFO's 2 * 24000 entries
+    const double* afh; double* afh_next;         // the two MovingAverage<double> histories, 128 entries each
 };
 
 constexpr int NFM_OUT_WIN = 256 + AM_BP_HIST;              // Bandpass inputs one block of nfm_out_kernel can touch

@@ -73,7 +73,7 @@ struct AmFamily : DemodDefaults {
     // DoubleBufferFIFO does not clear its array, see sdrx.h)
     static void fresh(const AmChan& s, AmBufs& u) { for (int i = 0; i < s.H; i++) u.vhist_next[i] = am_agc_initial(); }
 
-    static void work(Carver& k, size_t n, AmBufs& u)
+    static void work(Carver& k, size_t n, const AmChan&, AmBufs& u)
     {
         const size_t nblk = n / 256 + 1;
         u.msq = k.take<float>(n); u.root = k.take<float>(n);

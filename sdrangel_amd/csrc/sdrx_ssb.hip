@@ -109,7 +109,7 @@ struct SsbFamily : DemodDefaults {
         k.pair(u.whist, u.whist_next, (size_t)(s.D + 1));
     }
 
-    static void work(Carver& k, size_t n, SsbBufs& u)
+    static void work(Carver& k, size_t n, const SsbChan&, SsbBufs& u)
     {
         const size_t nblk = n / 256 + 1;
         u.pw = k.take<float>(n); u.sv = k.take<float>(n);

@@ -124,7 +124,7 @@ struct UdpFamily : DemodDefaults {
         if (s.fmt == UDP_AM_NODC_MONO) for (int i = 0; i < s.xk; i++) u.xhist_next[i] = udp_ma_initial();
     }
 
-    static void work(Carver& k, size_t n, UdpBufs& u)
+    static void work(Carver& k, size_t n, const UdpChan&, UdpBufs& u)
     {
         const size_t nblk = n / 256 + 1;
         u.dterm = k.take<double>(n); u.tot = k.take<double>(n);
