@@ -9,7 +9,10 @@ channels:
             samples
         ->  cut into the 512-byte datagrams UDPSink<T>::write would send, appended to one file per channel
 
-    python examples/filesource_to_udp.py [out_dir]   # writes a synthetic recording, replays it, saves the datagram payloads
+    python examples/filesource_to_udp.py [out_dir] [--format 0,1,3,9]
+        writes a synthetic recording, replays it, saves the datagram payloads.  --format names the four channels' sample formats
+        (UDPSrcSettings::SampleFormat, a trailing `a` turns m_agc on): `--format 4,5a,6,7a` sends the carriers out as LSB (with
+        its interleaved raw I/Q), USB, LSB mono and USB mono in blocks of 256 elements from fftfilt's 512-point filter
 
 NO socket is opened anywhere: the datagram payloads go to files (`udp_ch<N>.bin`, datagram after datagram, 512 bytes each);
 sending them is one sendto() per 512 bytes for whoever has a network to send them on.
@@ -47,16 +50,26 @@ def synth_recording(path, seconds=0.4, dev=2000.0):
     return n
 
 
-def channel_cfgs(bank):
+def channel_cfgs(bank, formats=None, agc=None):
+    formats, agc = formats or FORMATS, agc or AGC
     cfgs = []
     for c in range(len(CARRIERS)):
         _modes, out_rate, ofs = bank.info(c)
-        cfgs.append(sa.UdpSrcCfg(in_rate=out_rate, nco_freq=-ofs, output_sample_rate=OUT_RATE, sample_format=FORMATS[c], rf_bandwidth=RF_BW,
-                                 fm_deviation=FM_DEV, gain=GAIN, squelch_db=SQUELCH_DB, squelch_gate=GATE, squelch_enabled=1, agc=AGC[c]))
+        cfgs.append(sa.UdpSrcCfg(in_rate=out_rate, nco_freq=-ofs, output_sample_rate=OUT_RATE, sample_format=formats[c], rf_bandwidth=RF_BW,
+                                 fm_deviation=FM_DEV, gain=GAIN, squelch_db=SQUELCH_DB, squelch_gate=GATE, squelch_enabled=1, agc=agc[c]))
     return cfgs
 
 
-def main(out_dir):
+def parse_formats(text):
+    """`4,5a,6,7a` -> ([4, 5, 6, 7], [0, 1, 0, 1])"""
+    items = text.split(",")
+    if len(items) != len(CARRIERS):
+        raise SystemExit(f"--format takes {len(CARRIERS)} comma-separated sample formats, one per carrier")
+    return [int(v.rstrip("a")) for v in items], [int(v.endswith("a")) for v in items]
+
+
+def main(out_dir, formats=None, agc=None):
+    formats, agc = formats or FORMATS, agc or AGC
     os.makedirs(out_dir, exist_ok=True)
     rec = os.path.join(out_dir, "synthetic_udp.sdriq")
     n = synth_recording(rec)
@@ -66,7 +79,7 @@ def main(out_dir):
 
     fifo = sa.SampleSinkFifo(FS // 4)
     bank = sa.ChannelizerBank(FS, [REQ_RATE] * len(CARRIERS), CARRIERS)
-    udp = sa.UdpSrcBank(channel_cfgs(bank))
+    udp = sa.UdpSrcBank(channel_cfgs(bank, formats, agc))     # sdrx_udpsrc_create_ex when a channel has an SSB format
 
     paths = [os.path.join(out_dir, f"udp_ch{c}.bin") for c in range(len(CARRIERS))]
     files = [open(p, "wb") for p in paths]
@@ -88,11 +101,17 @@ def main(out_dir):
     for f in files:
         f.close()
     for c, fc in enumerate(CARRIERS):
-        print(f"carrier {c}: {fc:+8d} Hz  format {FORMATS[c]}, {udp.total(c)} samples of {udp.sample_bytes(c)} bytes at {OUT_RATE:.0f} S/s, "
+        print(f"carrier {c}: {fc:+8d} Hz  format {formats[c]}, {udp.total(c)} samples of {udp.sample_bytes(c)} bytes at {OUT_RATE:.0f} S/s, "
               f"{sent[c]} datagrams, squelch {'open' if udp.squelch_open(c) else 'closed'}, input power {udp.in_magsq(c):.3e} -> {paths[c]}")
     print(f"{n} input samples replayed from {rec}")
     return {"recording": rec, "payloads": paths, "spans": spans, "datagrams": sent, "totals": [udp.total(c) for c in range(len(CARRIERS))]}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "examples_out")
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out_dir", nargs="?", default="examples_out")
+    ap.add_argument("--format", default=",".join(f"{f}{'a' if a else ''}" for f, a in zip(FORMATS, AGC)),
+                    help="one sample format per carrier, 0 .. 10; a trailing a: m_agc on")
+    args = ap.parse_args()
+    main(args.out_dir, *parse_formats(args.format))

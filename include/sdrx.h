@@ -962,9 +962,29 @@ int sdrx_ssb_last_launch(const sdrx_ssb_t* h, char* kernel_name, int name_cap,
  *     fed on open samples only; m_interpolator.create(16, in_rate, rf_bandwidth / 2.0)
  *   - the payload conversions are what x86-64 gives: float -> qint16 is cvttss2si and the low 16 bits, double -> int16_t
  *     cvttsd2si and the low 16 bits; outside the int32 range, and for NaN, both give 0
- *   - left out: the SSB formats 4 .. 7 (SDRX_EINVAL).  They run fftfilt(0, bw / 2 / rate, 512), and the 512-point g_fft
- *     network (bitrevR2, one radix-4 stage, two radix-8 stages) is not among the device's (1024 and 2048 only); they also
- *     multiply ci by the AGC factor in front of the filter, which splits the front.  The follow-up.
+ *   - the SSB formats 4 .. 7 (FormatLSB, FormatUSB, FormatLSBMono, FormatUSBMono) need sdrx_udpsrc_create_ex with
+ *     SDRX_UDPSRC_SSB_FORMATS; sdrx_udpsrc_create refuses them (SDRX_EINVAL).  Per resampled sample: ci *= agcFactor (the double
+ *     narrowed to float once, two float products; 1.0 with agc off), then UDPFilter->runSSB(ci, &sideband, usb) (fftfilt.cpp:285-325)
+ *     on the 512-point g_fft (bitrevR2, bfR4 with NDiffU = 2, two radix-8 stages): nothing until 256 samples are in, then 256
+ *     sideband values = ovlbuf + the lower half of the filtered block; bin 0 times filter[0], bin 256 untouched, the other
+ *     sideband's bins zeroed.  inptr and ovlbuf carry across feeds.  Rulings:
+ *       . the filter never follows the settings: fftfilt(0.0, (12500 / 2.0) / 48000, 512) is built in the constructor from the default
+ *         settings and applySettings never calls create_filter, so every channel of every handle runs the same low pass
+ *         (sdrx_udpsrc_ssb_state returns it)
+ *       . m_squelchGate = (int)(output_sample_rate * 0.05), a double product, whatever squelch_gate says; m_squelchRelease stays
+ *         (int)((rate * squelch_gate) / 100) in float, so squelch_gate = 0 gives a release of 0 behind a gate that is not
+ *       . m_squelchOpen is sampled when the block completes: the 256 elements of a block are written in the loop iteration of
+ *         the sample that filled it, after that sample's calculateSquelch, and all of them use that one flag
+ *       . format 4 also emits raw I/Q: its `if` is not chained to the ladder behind it, whose last branch therefore runs too.
+ *         Per resampled sample, in order: the 256 LSB elements if the sample completes a block, then one element
+ *         (qint16)(re * gain), (qint16)(im * gain) of the SCALED ci (0, 0 while closed).  Formats 5, 6, 7 emit the blocks only
+ *       . elements: formats 4, 5 {int16, int16} = (int16)(double)(sideband.re * gain), likewise .im; formats 6, 7 int16 =
+ *         (int16)((double)(re + im) * 0.7 * (double)gain); 0 while closed; 4, 4, 2, 2 bytes
+ *       . agc != 0 feeds MagAGC for these formats too (udpsrc.cpp:155-163 excludes 0 .. 3 only); the spectrum Sample and inMagSq
+ *         come from the unscaled ci.  Zero input with the AGC on: m_u0 = inf, 0 * inf = NaN, an all-NaN block and a NaN ovlbuf; the
+ *         payload is 0 by the conversion ruling and so is every later block's
+ *     read / last_dev / total count payload ELEMENTS for these formats (format 4's raw elements included); the spectrum stays one
+ *     Sample per resampled sample
  *   - agc != 0 with formats 8 .. 10: agcFactor = m_agc.feedAndGetValue(ci) on EVERY sample, open or not, and inMagSq = getMagSq(),
  *     the same (double)(re*re + im*im).  MagAGC (sdrbase/dsp/agc.cpp:98-182) as UDPSrc sets it up: (9600, 16384.0f, 1e-6), clampMax
  *     2^30 with clamping on, m_squared false, the threshold enabled; resize((int)(rate / 5), (int)(rate / 20), 16384) leaves the
@@ -984,16 +1004,20 @@ typedef struct sdrx_udpsrc_cfg {
     int32_t in_rate;              /* channelizer output rate (m_inputSampleRate) */
     int32_t nco_freq;             /* m_nco.setFreq(nco_freq, in_rate): UDPSrc passes -frequencyOffset */
     float   output_sample_rate;   /* m_outputSampleRate, a float in the reference; 1000 <= rate <= in_rate */
-    int32_t sample_format;        /* UDPSrcSettings::SampleFormat, the reference's values: 0, 1, 2, 3, 8, 9, 10 */
+    int32_t sample_format;        /* UDPSrcSettings::SampleFormat, the reference's values: 0, 1, 2, 3, 8, 9, 10; 4 .. 7 with sdrx_udpsrc_create_ex */
     float   rf_bandwidth;         /* m_rfBandwidth */
     int32_t fm_deviation;         /* m_fmDeviation, Hz; > 0 */
     float   gain;                 /* m_gain */
     int32_t squelch_db;           /* m_squelchdB, power dB */
     int32_t squelch_gate;         /* m_squelchGate, 1/100 s; 0 .. 1000 */
     int32_t squelch_enabled;      /* m_squelchEnabled */
-    int32_t agc;                  /* m_agc: MagAGC for formats 8 .. 10; ignored by formats 0 .. 3 */
+    int32_t agc;                  /* m_agc: MagAGC for formats 4 .. 10; ignored by formats 0 .. 3 */
 } sdrx_udpsrc_cfg;
 int sdrx_udpsrc_create(sdrx_udpsrc_t** out, int device, int32_t n_ch, const sdrx_udpsrc_cfg* cfg);
+/* flags = 0: sdrx_udpsrc_create exactly, formats 4 .. 7 refused.  SDRX_UDPSRC_SSB_FORMATS: sample_format 4 .. 7 are accepted too.
+ * Any other bit: SDRX_EINVAL. */
+#define SDRX_UDPSRC_SSB_FORMATS 1u
+int sdrx_udpsrc_create_ex(sdrx_udpsrc_t** out, int device, int32_t n_ch, const sdrx_udpsrc_cfg* cfg, uint32_t flags);
 int sdrx_udpsrc_destroy(sdrx_udpsrc_t* h);
 /* the state of a fresh handle with the same configuration */
 int sdrx_udpsrc_reset(sdrx_udpsrc_t* h);
@@ -1003,13 +1027,15 @@ int sdrx_udpsrc_feed(sdrx_udpsrc_t* h, const int16_t* const* iq, const int64_t* 
 int sdrx_udpsrc_feed_dev(sdrx_udpsrc_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
 /* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
 int sdrx_udpsrc_feed_bank(sdrx_udpsrc_t* h, sdrx_chan_bank_t* bank);
-/* bytes of one payload sample of channel ch: 4, 8, 4, 2, 2, 2, 2 for formats 0, 1, 2, 3, 8, 9, 10 (<0: error) */
+/* bytes of one payload sample of channel ch: 4, 8, 4, 2, 2, 2, 2 for formats 0, 1, 2, 3, 8, 9, 10 and 4, 4, 2, 2 for formats
+ * 4, 5, 6, 7 (<0: error) */
 int32_t sdrx_udpsrc_sample_bytes(sdrx_udpsrc_t* h, int32_t ch);
 /* raw payload bytes of the last feed for channel ch; returns the number of SAMPLES written (<0: error) */
 int64_t sdrx_udpsrc_read(sdrx_udpsrc_t* h, int32_t ch, void* payload, int64_t cap_samples);
 /* device-side view of the same (valid until the next feed): pointer and number of samples */
 int sdrx_udpsrc_last_dev(sdrx_udpsrc_t* h, int32_t ch, const void** d_payload, int64_t* n_samples);
-/* the Samples {re, im} the last feed handed to the spectrum sink (m_sampleBuffer), one per payload sample */
+/* the Samples {re, im} the last feed handed to the spectrum sink (m_sampleBuffer), one per resampled sample: one per payload
+ * sample for formats 0 .. 3 and 8 .. 10, not for formats 4 .. 7 */
 int64_t sdrx_udpsrc_read_spectrum(sdrx_udpsrc_t* h, int32_t ch, int16_t* samples_iq, int64_t cap_samples);
 int sdrx_udpsrc_spectrum_last_dev(sdrx_udpsrc_t* h, int32_t ch, const int16_t** d_samples_iq, int64_t* n_samples);
 /* m_squelchOpen after the last feed: 1 / 0 (<0: error); m_squelchOpenCount and m_squelchCloseCount */
@@ -1019,6 +1045,9 @@ int sdrx_udpsrc_squelch_counts(sdrx_udpsrc_t* h, int32_t ch, int32_t* open_count
 int sdrx_udpsrc_in_magsq(sdrx_udpsrc_t* h, int32_t ch, double* in_magsq);
 /* payload samples since creation or reset (<0: error): datagram k of the stream holds samples [k * M, (k + 1) * M), M = 512 / element size */
 int64_t sdrx_udpsrc_total(sdrx_udpsrc_t* h, int32_t ch);
+/* formats 4 .. 7 (SDRX_EINVAL for a channel of another format): fftfilt's inptr after the last feed, the blocks completed since
+ * creation or reset, and the shared filter design (512 complex bins = 1024 floats, or NULL) */
+int sdrx_udpsrc_ssb_state(sdrx_udpsrc_t* h, int32_t ch, int32_t* pending, int64_t* blocks, float* filter_iq);
 /* design products, for inspection: polyphase taps [16][ntaps] and the 151 folded Bandpass taps (Reals, widened), NCO increment,
  * windows[3] = entries of m_inMovingAverage, m_amMovingAverage, m_outMovingAverage, gate and release in samples, m_squelch,
  * the discriminator's scaling, the distance step, agc_ints[4] = MagAGC's history length, step length, step-down delay and gate in

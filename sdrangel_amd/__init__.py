@@ -203,6 +203,8 @@ def lib() -> C.CDLL:
         "sdrx_ssb_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
                                           C.POINTER(C.c_double), C.POINTER(C.c_float)]),
         "sdrx_udpsrc_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_udpsrc_create_ex": (C.c_int, [pp, C.c_int, i32, vp, C.c_uint32]),
+        "sdrx_udpsrc_ssb_state": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i64), vp]),
         "sdrx_udpsrc_destroy": (C.c_int, [vp]),
         "sdrx_udpsrc_reset": (C.c_int, [vp]),
         "sdrx_udpsrc_feed": (C.c_int, [vp, vp, vp]),
@@ -1131,7 +1133,10 @@ class UdpSrcCfg(C.Structure):
 
 #: numpy dtype of one payload sample per UDPSrcSettings::SampleFormat: Sample16, Sample24 (two int32), Sample16, int16 ...
 UDPSRC_PAYLOAD_DTYPES = {0: np.dtype((np.int16, 2)), 1: np.dtype((np.int32, 2)), 2: np.dtype((np.int16, 2)), 3: np.dtype(np.int16),
+                         4: np.dtype((np.int16, 2)), 5: np.dtype((np.int16, 2)), 6: np.dtype(np.int16), 7: np.dtype(np.int16),
                          8: np.dtype(np.int16), 9: np.dtype(np.int16), 10: np.dtype(np.int16)}
+#: sdrx_udpsrc_create_ex: accept the SSB formats 4 .. 7
+UDPSRC_SSB_FORMATS = 1
 #: UDPSrc::udpBlockSize: bytes of one datagram
 UDPSRC_BLOCK_BYTES = 512
 
@@ -1160,13 +1165,21 @@ class UdpPayloadCutter:
 
 
 class UdpSrcBank(_DemodBank):
-    """N UDPSrc channels (UDPSrc::feed; formats IQ16, IQ24, NFM, NFMMono, AMMono, AMNoDCMono, AMBPFMono): int16 I/Q at the
-    channelizer's output rate in (MagAGC for the AM formats when agc is set), the datagram payload samples and the spectrum Samples out.  No socket is opened anywhere:
-    payloads(ch) returns the bytes of the datagrams the reference would send."""
+    """N UDPSrc channels (UDPSrc::feed, every sample format): int16 I/Q at the channelizer's output rate in (MagAGC for the SSB
+    and AM formats when agc is set), the datagram payload samples and the spectrum Samples out.  A bank with an SSB format
+    (LSB, USB, LSBMono, USBMono: 4 .. 7) is created through sdrx_udpsrc_create_ex; such a channel's payload comes in blocks of 256
+    elements, format 4's interleaved with one raw I/Q element per resampled sample.  No socket is opened anywhere: payloads(ch)
+    returns the bytes of the datagrams the reference would send."""
     _prefix, _cfg = "udpsrc", UdpSrcCfg
 
     def __init__(self, cfgs, device: int = 0):
-        super().__init__(cfgs, device)
+        self.n_ch = len(cfgs)
+        arr = (self._cfg * self.n_ch)(*cfgs)
+        if any(4 <= k.sample_format <= 7 for k in cfgs):
+            self._open(device, self.n_ch, arr, UDPSRC_SSB_FORMATS, create="create_ex")
+        else:
+            self._open(device, self.n_ch, arr)
+        self.cfgs = list(cfgs)
         self._cutters = [UdpPayloadCutter(self.sample_bytes(c)) for c in range(self.n_ch)]
 
     def reset(self):
@@ -1189,7 +1202,7 @@ class UdpSrcBank(_DemodBank):
         return out[: n * size].tobytes()
 
     def read(self, ch: int, cap: int | None = None) -> np.ndarray:
-        """the last feed's payload samples: [n, 2] int16 (formats 0, 2), [n, 2] int32 (format 1) or [n] int16"""
+        """the last feed's payload samples: [n, 2] int16 (formats 0, 2, 4, 5), [n, 2] int32 (format 1) or [n] int16"""
         dt = UDPSRC_PAYLOAD_DTYPES[self.cfgs[ch].sample_format]
         a = np.frombuffer(self.read_raw(ch), dt.base).reshape((-1,) + dt.shape)
         return (a if cap is None else a[:cap]).copy()
@@ -1237,6 +1250,14 @@ class UdpSrcBank(_DemodBank):
         if n < 0:
             raise SdrxError(f"sdrx_udpsrc_total rc={n}: {lib().sdrx_last_error().decode()}")
         return n
+
+    def ssb_state(self, ch: int):
+        """formats 4 .. 7: (fftfilt's inptr after the last feed, blocks completed since creation or reset, the shared filter design
+        as 512 complex64 bins)"""
+        pend, blocks = C.c_int32(), C.c_int64()
+        filt = np.zeros(1024, np.float32)
+        self._call("ssb_state", ch, C.byref(pend), C.byref(blocks), filt.ctypes.data)
+        return pend.value, blocks.value, filt.view(np.complex64)
 
     def design(self, ch: int) -> dict:
         nt, inc, gate, rel, lvl, fms, step = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_float(), C.c_float()

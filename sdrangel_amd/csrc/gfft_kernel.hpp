@@ -25,14 +25,16 @@ __device__ __forceinline__ float2 c_mul(float2 a, float2 b) { float2 t; t.x = a.
 
 // y: LDS work array (N float2); x: LDS input copy (N float2); u: cosine table (N/4+1 floats); N/8 threads.
 // N = 1024: stage list R2(bitrev) + 3 x radix-8 (D = 2, 16, 128);  N = 2048: R2(bitrev) + bfR2 (:531-635 /
-// ibfR2 :1577-1681: twiddles 1 and -/+i) + 3 x radix-8 (D = 4, 32, 256).  inverse: first stage scaled by 1/N,
-// multipliers conjugated.
+// ibfR2 :1577-1681: twiddles 1 and -/+i) + 3 x radix-8 (D = 4, 32, 256);  N = 512: R2(bitrev) + bfR4 (:637-841 / ibfR4
+// :1683-1887, NDiffU = 2: per 8 points the even ones take twiddles 1 and -/+i, the odd ones -/+i and w1 = cos(pi/4) in the
+// `a - b*w1 ...; partner = 2*a - result` form) + 2 x radix-8 (D = 8, 64).  inverse: first stage scaled by 1/N, multipliers
+// conjugated.
 template<int N, bool INVERSE>
 __device__ __forceinline__ void gfft(float2* __restrict__ y, const float2* __restrict__ x, const float* __restrict__ u, int tid)
 {
     constexpr int NT = N / 8;
-    constexpr int M = N == 1024 ? 10 : 11;
-    static_assert(N == 1024 || N == 2048, "fftfilt lengths of the demods");
+    constexpr int M = N == 512 ? 9 : (N == 1024 ? 10 : 11);
+    static_assert(N == 512 || N == 1024 || N == 2048, "fftfilt lengths of the demods and of UDPSrc");
     const float scale = (float)(1.0 / N);
     for (int j = tid; j < N / 2; j += NT) {
         const unsigned r = __brev((unsigned)(2 * j)) >> (32 - M);
@@ -42,7 +44,7 @@ __device__ __forceinline__ void gfft(float2* __restrict__ y, const float2* __res
         y[2 * j] = s; y[2 * j + 1] = d;
     }
     __syncthreads();
-    constexpr int D0 = N == 1024 ? 2 : 4;
+    constexpr int D0 = N == 512 ? 8 : (N == 1024 ? 2 : 4);
     if constexpr (N == 2048) {
         for (int k = 4 * tid; k < N; k += 4 * NT) {
             const float2 a = y[k], b = y[k + 2], c = y[k + 1], d = y[k + 3];
@@ -51,6 +53,37 @@ __device__ __forceinline__ void gfft(float2* __restrict__ y, const float2* __res
             t.x = a.x - b.x; t.y = a.y - b.y; y[k + 2] = t;
             if (!INVERSE) { t.x = c.x + d.y; t.y = c.y - d.x; y[k + 1] = t; t.x = c.x - d.y; t.y = c.y + d.x; y[k + 3] = t; }
             else          { t.x = c.x - d.y; t.y = c.y + d.x; y[k + 1] = t; t.x = c.x + d.y; t.y = c.y - d.x; y[k + 3] = t; }
+        }
+        __syncthreads();
+    }
+    if constexpr (N == 512) {
+        const float w1 = (float)(1.0 / 1.414213562373095048801688724209698078569);       // FFT_TYPE w1r = 1.0 / FFT_ROOT2
+        for (int k = 8 * tid; k < N; k += 8 * NT) {
+            // even points: twiddles 1, then 1 and -/+i
+            const float2 a0 = y[k], a1 = y[k + 2], a2 = y[k + 4], a3 = y[k + 6];
+            float2 e5, e0, e6, e3, t;
+            e5.x = a0.x - a1.x; e5.y = a0.y - a1.y; e0.x = a0.x + a1.x; e0.y = a0.y + a1.y;
+            e6.x = a2.x + a3.x; e6.y = a2.y + a3.y; e3.x = a2.x - a3.x; e3.y = a2.y - a3.y;
+            t.x = e0.x + e6.x; t.y = e0.y + e6.y; y[k] = t;
+            t.x = e0.x - e6.x; t.y = e0.y - e6.y; y[k + 4] = t;
+            if (!INVERSE) { t.x = e5.x + e3.y; t.y = e5.y - e3.x; y[k + 2] = t; t.x = e5.x - e3.y; t.y = e5.y + e3.x; y[k + 6] = t; }
+            else          { t.x = e5.x - e3.y; t.y = e5.y + e3.x; y[k + 2] = t; t.x = e5.x + e3.y; t.y = e5.y - e3.x; y[k + 6] = t; }
+            // odd points: twiddles -/+i, then w1 and i*w1
+            const float2 b0 = y[k + 1], b1 = y[k + 3], b2 = y[k + 5], b3 = y[k + 7];
+            float2 o7, o2, o4, t1, o5, o6;
+            if (!INVERSE) {
+                o7.x = b2.x - b3.y; o7.y = b2.y + b3.x; o2.x = b2.x + b3.y; o2.y = b2.y - b3.x;
+                o4.x = b0.x + b1.y; o4.y = b0.y - b1.x; t1.x = b0.x - b1.y; t1.y = b0.y + b1.x;
+                o5.x = t1.x - o7.x * w1 + o7.y * w1; o5.y = t1.y - o7.x * w1 - o7.y * w1;
+                o6.x = o4.x - o2.x * w1 - o2.y * w1; o6.y = o4.y + o2.x * w1 - o2.y * w1;
+            } else {
+                o7.x = b2.x + b3.y; o7.y = b2.y - b3.x; o2.x = b2.x - b3.y; o2.y = b2.y + b3.x;
+                o4.x = b0.x - b1.y; o4.y = b0.y + b1.x; t1.x = b0.x + b1.y; t1.y = b0.y - b1.x;
+                o5.x = t1.x - o7.x * w1 - o7.y * w1; o5.y = t1.y + o7.x * w1 - o7.y * w1;
+                o6.x = o4.x - o2.x * w1 + o2.y * w1; o6.y = o4.y - o2.x * w1 - o2.y * w1;
+            }
+            y[k + 3] = o5; y[k + 7] = c_two_minus(t1, o5);
+            y[k + 5] = o6; y[k + 1] = c_two_minus(o4, o6);
         }
         __syncthreads();
     }

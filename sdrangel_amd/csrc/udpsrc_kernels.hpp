@@ -9,10 +9,13 @@
 // operand order and the file is compiled with -ffp-contract=off.  udpsrc_scan.hpp has the cut of the recurrences; DESIGN.md 4.14 the
 // kernel table.  The only loop that is serial along time is psum_rows' (demod_psum.hpp).  A channel's format is uniform over a
 // block (blockIdx.y is the channel), so the format branches diverge per block, not per lane.
+// The SSB formats LSB, USB, LSBMono and USBMono (4 .. 7) share kernels 1 .. 3 and 6 with the others; their filter, payload and
+// carry are udpsrc_ssb_kernels.hpp's, which run between udp_out_kernel and udp_carry_kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "udpsrc_scan.hpp"
+#include "udpsrc_ssb_sched.hpp"
 #include "demod_psum.hpp"
 #include "demod_wg.hpp"
 
@@ -42,6 +45,12 @@ struct UdpChan {                        // device resident: config + carried sta
     // --- per feed
     int n, n_act;                       // output samples; open ones
     double in_sum_next, am_sum_next;    // written by the psum kernels, committed by udp_carry_kernel
+    // --- formats 4 .. 7 (udpsrc_ssb_kernels.hpp); all zero for the other formats but n_pay
+    int ssb;                            // config: an SSB format
+    int s_pend;                         // state: fftfilt::inptr
+    long long s_blocks;                 // state: blocks completed since creation or reset
+    long long total_pay;                // state: payload elements since creation or reset
+    int nb, n_pay;                      // per feed: blocks completed; payload elements (= n for the other formats)
 };
 
 struct UdpBufs {                        // per channel device pointers (per feed capacity ensured by the host)
@@ -57,6 +66,11 @@ struct UdpBufs {                        // per channel device pointers (per feed
     double* x;                          // per open sample: sqrt(inMagSq) (formats 9, 10) or the float2 ci (formats 2, 3)
     int16_t* spec;                      // Sample {re, im} per output sample
     void* out;                          // payload samples
+    // formats 4 .. 7, null for the others: the scaled samples waiting for a full block and fftfilt::ovlbuf (256 each, carried),
+    // the two halves of every block's inverse FFT
+    const float2* pend; float2* pend_next;
+    const float2* ovl; float2* ovl_next;
+    float2* head; float2* tail;
 };
 
 constexpr int UDP_OUT_WIN = 256 + AM_BP_HIST;              // Bandpass inputs one block of udp_out_kernel can touch
@@ -84,7 +98,12 @@ void udp_level_kernel(UdpChan* __restrict__ ch, const UdpBufs* __restrict__ bufs
     const int c = blockIdx.y, tid = threadIdx.x;
     const UdpBufs b = bufs[c];
     const int n = *b.n_ptr;
-    if (blockIdx.x == 0 && tid == 0) ch[c].n = n;
+    if (blockIdx.x == 0 && tid == 0) {
+        ch[c].n = n;
+        const int nb = ch[c].ssb ? udp_ssb_blocks(ch[c].s_pend, n) : 0;
+        ch[c].nb = nb;
+        ch[c].n_pay = ch[c].ssb ? (int)udp_ssb_payload_count(ch[c].fmt, ch[c].s_pend, n) : n;
+    }
     const long i = (long)blockIdx.x * 256 + tid;
     if (i >= n) return;
     const int w = ch[c].w_in;
@@ -230,6 +249,7 @@ void udp_out_kernel(const UdpChan* __restrict__ ch, const UdpBufs* __restrict__ 
     const UdpBufs& b = bufs[c];
     const long i = (long)blockIdx.x * 256 + tid;
     const int fmt = s.fmt;
+    if (udp_fmt_ssb(fmt)) return;                           // udp_ssb_out_kernel writes these payloads
     const int a = i < s.n ? b.aidx[i] : -1;
     const float gain = s.gain;
     const double factor = s.agc && i < s.n ? b.gterm[i] : 1.0;     // agcFactor

@@ -34,7 +34,7 @@ def main():
     ap.add_argument("--channels", type=int, default=256)
     ap.add_argument("--in-rate", type=int, default=48000)
     ap.add_argument("--feeds", type=int, default=12)
-    ap.add_argument("--formats", default="0,1,2,3,8,9,10,8a,9a,10a", help="sample formats; a trailing a: m_agc on")
+    ap.add_argument("--formats", default="0,1,2,3,8,9,10,8a,9a,10a", help="sample formats; a trailing a: m_agc on (the SSB formats: 4,5,6,7,4a,6a)")
     ap.add_argument("--no-baseline", action="store_true", help="skip the NFM bank and the CPU oracle (profiling runs)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -95,7 +95,12 @@ def main():
         L = uc.build_oracle()
         x = uc.signal(sigs[1], n, in_rate, 901)
         for fmt, agc in formats:
-            o = uc.OracleUdp(L, (in_rate, ncos[1], float(in_rate), fmt, rf, fmdev, gain, sqdb, gate, 1, agc))
+            cfg = (in_rate, ncos[1], float(in_rate), fmt, rf, fmdev, gain, sqdb, gate, 1, agc)
+            if 4 <= fmt <= 7:                               # the SSB formats have an oracle of their own
+                from tests import udpsrc_ssb_cases as sc
+                o = sc.OracleSsb(sc.build_oracle(), cfg)
+            else:
+                o = uc.OracleUdp(L, cfg)
             t0 = time.perf_counter()
             o.feed(x)
             res[f"{label(fmt, agc)}_cpu_oracle_ms_all_channels_one_core"] = round((time.perf_counter() - t0) * 1e3 * n_ch, 1)
