@@ -228,7 +228,9 @@ typedef struct sdrx_backend_cfg {
     float   taps_per_phase;  /* 4.5 (default, NFM) or 2.0 (SSB): (int)(taps_per_phase * 16) taps per phase, made even;
                               * 0.0625 .. 16.0 (1 .. 256 taps), anything else is refused with SDRX_EINVAL */
     int32_t filt_mode;       /* 0 none, 1 runFilt, 2 runSSB usb, 3 runSSB lsb, 4 runDSB  (getDC = true),
-                              * 5 runAsym usb, 6 runAsym lsb: fftfilt(f2, 2048) + create_asym_filter(fopp = f1, fin = f2) (atvdemod.cpp:262,647) */
+                              * 5 runAsym usb, 6 runAsym lsb: fftfilt(f2, 2048) + create_asym_filter(fopp = f1, fin = f2) (atvdemod.cpp:262,647),
+                              * 7 runFilt at length 2048 on create_rrc_filter(fb = f1, a = f2) (chanalyzer.cpp:305): the root raised
+                              * cosine written in the frequency domain */
     float   f1, f2;          /* modes 1-3: fftfilt(f1, f2, 1024); mode 4: fftfilt(f2, 2048) (DSBFilter, ssbdemod.cpp:92); normalised to the OUTPUT rate */
     int32_t discri;          /* 0 none, 1 phaseDiscriminatorDelta (NFM; bit-identical to the strict-IEEE reference),
                               * 2 phaseDiscriminator (UDPSrc): std::arg = atan2f.  The device evaluates a double atan2 rounded once
@@ -922,6 +924,89 @@ int sdrx_ssb_get_timing(sdrx_ssb_t* h, double* total_ms, int64_t* feeds, int res
 /* the output kernel of the last feed (delay line, step value, volume, conversion): ssb_out_kernel, its grid, block and LDS bytes */
 int sdrx_ssb_last_launch(const sdrx_ssb_t* h, char* kernel_name, int name_cap,
                          int* grid, int* block, int* lds_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * ChannelAnalyzer bank: ChannelAnalyzer::feed (plugins/channelrx/chanalyzer/chanalyzer.cpp:92-182) with m_pll off, N channels
+ * per handle, each fed with int16 I/Q at the channelizer's output rate; every feed produces the Samples the analyzer hands to
+ * its scope / spectrum sink (m_sampleBuffer):
+ *     c = Complex(re, im) * m_nco.nextIQ()                          NCOF (sdrbase/dsp/ncof.h): float phase, float increment
+ *     down_sample: m_interpolator.decimate(&remain, c, &ci) -> processOneSample(ci); remain += in_rate / down_sample_rate
+ *     else:        processOneSample(c)
+ *     processOneSample: ssb: runSSB(c, &sideband, m_usb), length 1024; else rrc: runFilt on the root raised cosine, length 2048;
+ *                       else runDSB, length 2048
+ *     per filtered sample: m_sum += s; every (1 << span_log2)-th (the very first closes a group of one): m_sum /= decim,
+ *         re = m_sum.real() / SDR_RX_SCALEF (likewise im), m_magsq = re*re + im*im, feedOneSample(m_sum), m_sum = 0
+ *     feedOneSample: input_type 0: Sample(re, im) of m_sum, (im, re) for ssb with a negative bandwidth
+ *                    input_type 2: a = m_corr->run(m_sum / (SDR_RX_SCALEF / 768.0f), 0), fftcorr(8192); Sample(a) with the same swap.
+ *                        Call t = 1, 2, ... returns P_b[t mod 4096], b = t / 4096; P_0 = 0 and P_b = InverseComplexFFT(A .* conj(A)),
+ *                        A the ComplexFFT of the b-th run of 4096 inputs padded with zeros to 8192: the first 4095 Samples are 0
+ * Output: qint16 re,im pairs, bit-identical to the strict-IEEE scalar reference build; out of qint16's range the conversion is
+ * what x86-64 gives (the autocorrelation's lag 0 is the block's energy and leaves the range for inputs above a few tens of LSB).
+ * Any feed length is valid (0 included); everything carries across feeds.  A fresh handle is the object after the constructor,
+ * applySettings(settings, true), applyChannelSettings(in_rate, -nco_freq) and start():
+ *   - m_nco.setFreq(nco_freq, in_rate); m_interpolator.create(16, in_rate, in_rate / 2.2f), 4.5 taps per phase, distance 0
+ *   - setFilters(rate, bandwidth, low_cutoff) with rate = down_sample ? down_sample_rate : in_rate: a negative bandwidth flips
+ *     both signs and clears m_usb, a magnitude below 100 becomes 100 with a low cutoff of 0; create_filter(low / rate, band / rate),
+ *     create_dsb_filter(band / rate), create_rrc_filter(band / rate, rrc_rolloff / 100.0)
+ *   - with down_sample the last design of the root raised cosine is applySettings' own, create_rrc_filter(bandwidth / (float)
+ *     down_sample_rate, rrc_rolloff / 100.0), on the bandwidth as the settings have it (no flip, no clamp)
+ *   - frrc's cosine is the host's cosf
+ *   - left out: m_channelPowerAvg (GUI only), mid-stream changes of settings, the PLL, the FLL and the PLL input
+ * SDRX_EINVAL for pll, fll, input_type 1 (or anything but 0 and 2), span_log2 outside 0 .. 8, rrc_rolloff outside 0 .. 100,
+ * down_sample with down_sample_rate outside 1 .. in_rate, and |nco_freq| > in_rate (NCOF's wrap loops would not end).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_chana sdrx_chana_t;
+typedef struct sdrx_chana_cfg {
+    int32_t in_rate;              /* channelizer output rate (m_inputSampleRate) */
+    int32_t nco_freq;             /* m_nco.setFreq(nco_freq, in_rate): the analyzer passes -inputFrequencyOffset */
+    int32_t down_sample;          /* m_downSample: the Interpolator is in use */
+    int32_t down_sample_rate;     /* m_downSampleRate; 1 .. in_rate when down_sample */
+    int32_t bandwidth;            /* m_bandwidth, Hz; negative: the lower side */
+    int32_t low_cutoff;           /* m_lowCutoff, Hz */
+    int32_t span_log2;            /* m_spanLog2, 0 .. 8 */
+    int32_t ssb;                  /* m_ssb */
+    int32_t rrc;                  /* m_rrc (used when ssb is 0) */
+    int32_t rrc_rolloff;          /* m_rrcRolloff, hundredths, 0 .. 100 */
+    int32_t input_type;           /* m_inputType: 0 signal, 2 autocorrelation */
+    int32_t pll;                  /* m_pll: must be 0 */
+    int32_t fll;                  /* m_fll: must be 0 */
+} sdrx_chana_cfg;
+int sdrx_chana_create(sdrx_chana_t** out, int device, int32_t n_ch, const sdrx_chana_cfg* cfg);
+int sdrx_chana_destroy(sdrx_chana_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_chana_reset(sdrx_chana_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to ChannelAnalyzer::feed) */
+int sdrx_chana_feed(sdrx_chana_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_chana_feed_dev(sdrx_chana_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_chana_feed_bank(sdrx_chana_t* h, sdrx_chan_bank_t* bank);
+/* the Samples {re, im} of the last feed for channel ch; returns their number (<0: error) */
+int64_t sdrx_chana_read(sdrx_chana_t* h, int32_t ch, int16_t* samples_iq, int64_t cap_samples);
+/* device-side view of the same (valid until the next feed): pointer and number of Samples */
+int sdrx_chana_last_dev(sdrx_chana_t* h, int32_t ch, const int16_t** d_samples_iq, int64_t* n_samples);
+/* what the analyzer passes as the sink's third argument: m_ssb, 1 / 0 (<0: error) */
+int sdrx_chana_positive_only(sdrx_chana_t* h, int32_t ch);
+/* m_magsq after the last feed, exact */
+int sdrx_chana_magsq(sdrx_chana_t* h, int32_t ch, double* magsq);
+/* design products, for inspection: polyphase taps [16][ntaps], the spectrum of the filter in use (2048 complex slots; 1024 used
+ * with ssb), NCOF's phase increment */
+int sdrx_chana_get_design(sdrx_chana_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap, float* filter_iq,
+                          float* nco_inc);
+/* a fresh (or reset) channel whose filter has already put out `filtered_samples` samples of silence: m_undersampleCount and
+ * fftcorr's call counter start from there (the oscillator and the filters start as on a fresh handle).  For streams whose
+ * counters have passed 2^31: only the counter's low bits matter, and they carry as the mask sees them */
+int sdrx_chana_seek(sdrx_chana_t* h, int32_t ch, uint64_t filtered_samples);
+int sdrx_chana_sync(sdrx_chana_t* h);
+int sdrx_chana_set_stream(sdrx_chana_t* h, void* hip_stream);
+int sdrx_chana_get_stream(sdrx_chana_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_chana_set_timing(sdrx_chana_t* h, int enabled);
+int sdrx_chana_get_timing(sdrx_chana_t* h, double* total_ms, int64_t* feeds, int reset);
+/* chana_corr_kernel (grid = blocks x channels, 1024 threads, its LDS bytes) when a channel computes the autocorrelation, else
+ * chana_group_kernel */
+int sdrx_chana_last_launch(const sdrx_chana_t* h, char* kernel_name, int name_cap,
+                           int* grid, int* block, int* lds_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * UDPSrc bank: UDPSrc::feed (plugins/channelrx/udpsrc/udpsrc.cpp:136-321), N channels per handle, each fed with int16 I/Q at

@@ -204,6 +204,18 @@ def lib() -> C.CDLL:
                                           C.POINTER(C.c_double), C.POINTER(C.c_float)]),
         "sdrx_udpsrc_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_udpsrc_create_ex": (C.c_int, [pp, C.c_int, i32, vp, C.c_uint32]),
+        "sdrx_chana_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_chana_destroy": (C.c_int, [vp]),
+        "sdrx_chana_reset": (C.c_int, [vp]),
+        "sdrx_chana_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_chana_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_chana_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_chana_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_chana_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_chana_positive_only": (C.c_int, [vp, i32]),
+        "sdrx_chana_magsq": (C.c_int, [vp, i32, C.POINTER(C.c_double)]),
+        "sdrx_chana_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(C.c_float)]),
+        "sdrx_chana_seek": (C.c_int, [vp, i32, C.c_uint64]),
         "sdrx_udpsrc_ssb_state": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i64), vp]),
         "sdrx_udpsrc_destroy": (C.c_int, [vp]),
         "sdrx_udpsrc_reset": (C.c_int, [vp]),
@@ -270,7 +282,7 @@ def lib() -> C.CDLL:
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
                 "wfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
-                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
         for name in names:
@@ -910,6 +922,14 @@ class SsbCfg(C.Structure):
                 ("agc_threshold_gate", C.c_int32)]
 
 
+class ChanaCfg(C.Structure):
+    """sdrx_chana_cfg: one ChannelAnalyzer (in_rate, nco_freq = -frequencyOffset, ChannelAnalyzerSettings; bandwidth < 0 is the
+    lower side; input_type 0 signal, 2 autocorrelation)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("down_sample", C.c_int32), ("down_sample_rate", C.c_int32),
+                ("bandwidth", C.c_int32), ("low_cutoff", C.c_int32), ("span_log2", C.c_int32), ("ssb", C.c_int32), ("rrc", C.c_int32),
+                ("rrc_rolloff", C.c_int32), ("input_type", C.c_int32), ("pll", C.c_int32), ("fll", C.c_int32)]
+
+
 def wfm_required_bw(rf_bw: int) -> int:
     """WFMDemod::requiredBW: the rate the demodulator asks its channelizer for"""
     return 48000 if rf_bw <= 48000 else (3 * rf_bw) // 2
@@ -1162,6 +1182,44 @@ class UdpPayloadCutter:
     def pending(self) -> int:
         """samples waiting for a full datagram"""
         return len(self._rest) // self.sample_bytes
+
+
+class ChannelAnalyzerBank(_DemodBank):
+    """N ChannelAnalyzers (ChannelAnalyzer::feed, PLL off): int16 I/Q at the channelizer's output rate in; the Samples the
+    analyzer hands to its scope / spectrum sink out, the signal itself or its autocorrelation."""
+    _prefix, _cfg = "chana", ChanaCfg
+
+    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
+        """the last feed's Samples as an [n, 2] array of (re, im)"""
+        if cap is None:
+            cap = self.last_dev(ch)[1]
+        out = np.empty((max(cap, 1), 2), np.int16)
+        n = self._fn("read")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_chana_read rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def positive_only(self, ch: int) -> bool:
+        rc = self._fn("positive_only")(self._h, ch)
+        if rc < 0:
+            raise SdrxError(f"sdrx_chana_positive_only rc={rc}: {lib().sdrx_last_error().decode()}")
+        return bool(rc)
+
+    def magsq(self, ch: int) -> float:
+        m = C.c_double()
+        self._call("magsq", ch, C.byref(m))
+        return m.value
+
+    def seek(self, ch: int, filtered_samples: int):
+        """a fresh channel whose filter has already put out this many samples of silence (sdrx_chana_seek)"""
+        self._call("seek", ch, C.c_uint64(filtered_samples))
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], filter spectrum as 4096 floats, NCOF's phase increment)"""
+        nt, inc = C.c_int32(), C.c_float()
+        taps, filt = np.zeros(16 * 256, np.float32), np.zeros(4096, np.float32)
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc))
+        return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value
 
 
 class UdpSrcBank(_DemodBank):

@@ -124,6 +124,28 @@ inline void fftfilt_fill_lowpass(float fc, float* f, int h2)
     for (int i = 0; i < h2; i++) f[(size_t)(2 * i)] = fsinc(fc, i, h2);
 }
 
+// create_rrc_filter(fb, a) (fftfilt.cpp:223-246) with frrc (fftfilt.h:68-87): the root raised cosine written straight into the
+// len complex bins at f[2 * i], f[2 * i + 1], then normalised to max |H| over all of them.  frrc's operand order and widths:
+// x and tr are floats, the fold and the transition's argument are double expressions stored as floats, and cos() sees a float.
+inline void fftfilt_rrc(float fb, float a, float* f, int len)
+{
+    for (int i = 0; i < len; i++) {
+        float x = i / (float)len;
+        x = (float)(0.5 - std::fabs((double)x - 0.5));
+        const float tr = fb * a;
+        float v;
+        if (x < fb - tr) v = 1.0f;
+        else if (x < fb + tr) {
+            const float y = (float)(((double)(x - (fb - tr)) / (2.0 * (double)tr)) * PI_D);
+            v = (std::cos(y) + 1.0f) / 2.0f;
+        } else v = 0.0f;
+        f[(size_t)(2 * i)] = v; f[(size_t)(2 * i + 1)] = 0.0f;
+    }
+    float scale = 0;
+    for (int i = 0; i < len; i++) { const float mag = hypotf(f[(size_t)(2 * i)], f[(size_t)(2 * i + 1)]); if (mag > scale) scale = mag; }
+    if (scale != 0) for (int i = 0; i < 2 * len; i++) f[(size_t)i] /= scale;
+}
+
 #if defined(__HIPCC__)          // after sdrx_common.hpp and gfft_kernel.hpp
 // a design table into device memory of its own
 inline int design_upload(float** dst, const std::vector<float>& t)

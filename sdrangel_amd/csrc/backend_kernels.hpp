@@ -33,12 +33,17 @@ struct BeChan {                         // device resident: config + carried sta
     int ntaps;                          // taps per phase
     int phase_steps;
     int taps_off;                       // float offset into the taps table: [phase][ntaps]
-    int filt_mode;                      // 0 none, 1 runFilt, 2 runSSB usb, 3 runSSB lsb, 4 runDSB, 5 runAsym usb, 6 runAsym lsb (4..6: fft length 2048)
+    int filt_mode;                      // 0 none, 1 runFilt, 2 runSSB usb, 3 runSSB lsb, 4 runDSB, 5 runAsym usb, 6 runAsym lsb, 7 runFilt on an
+                                        // uploaded spectrum (4..7: fft length 2048)
     int filt_off;                       // complex offset into the filter table (2 * BE_FFT_MAX entries per channel: filter, filterOpp)
     int discri;                         // 0 none, 1 phaseDiscriminatorDelta, 2 phaseDiscriminator
     float fm_scaling;
+    int bypass;                         // 1: no Interpolator, every NCO-mixed sample goes into the fftfilt blocks (backend_set_front)
+    int ncof;                           // 1: the oscillator is NCOF (ncof.h): a float phase and a float increment
+    float ncof_inc;                     // NCOF::setFreq: (freq * 4096) / rate
     // --- state
     int nco_phase;                      // phase after the last consumed input sample
+    float ncof_phase;                   // NCOF::m_phase after the last consumed input sample
     float distance;
     int pending;                        // resampled samples waiting for a full fftfilt block
     float prev_arg, m1r, m1i;
@@ -60,6 +65,9 @@ struct BeBufs {                         // per channel device pointers (per feed
     const uint32_t* in;                 // n_in packed Samples
     uint32_t* hist;                     // BE_HIST packed Samples: tail of the previous feeds
     uint32_t* hist_next;
+    const uint16_t* ph_hist;            // NCOF channels: the table index of each history sample
+    uint16_t* ph_hist_next;
+    uint16_t* ph;                       // NCOF channels: the table index (0 .. 4096) of each new sample, written by be_ncof_kernel
     float2* mixed;                      // BE_HIST + n_in: NCO-mixed samples, index BE_HIST + k
     uint2* sched;                       // per resampler output o: sched[o * sched_stride] = {k, bits(distance)} (channel-interleaved
                                         // so that the serial schedule lanes of a wave store to neighbouring addresses)
@@ -165,6 +173,15 @@ __global__ void be_sched_dyadic_prep_kernel(BeChan* __restrict__ ch, const BeBuf
     const int c = perm[col];
     BeChan& s = ch[c];
     s.dy_active = 0;
+    if (s.bypass) {
+        // no resampler: the mix kernel writes the filter's input itself; the channel is marked as taken with no entries, so
+        // neither schedule kernel writes anything for it and the FIR skips it
+        const int n = (int)bufs[c].n_in;
+        s.dy_active = 1; s.dy_mode = 0; s.dy_pre = 0; s.dy_cnt = 0; s.dy_kb = 0; s.dy_P0 = 0;
+        s.n_in = n; s.n_res = n;
+        s.n_blocks = s.filt_mode ? (s.pending + n) / s.half : 0;
+        return;
+    }
     if (s.dy_q < 0) return;
     const int q = s.dy_q;
     const long Q = 1L << q, S = s.dy_S;
@@ -232,6 +249,46 @@ __global__ void __launch_bounds__(256) be_sched_dyadic_fill_kernel(const BeChan*
     }
 }
 
+// ---- 1c. NCOF::nextPhase (ncof.h:45-55) for the channels whose oscillator it is: m_phase += m_phaseIncrement in float, then
+// the two wrap loops; the table index of sample j is (int) m_phase.  The sum rounds wherever the phase's exponent is above
+// the increment's, so the walk is serial: one lane per channel, a dependent float add and the wraps per sample.
+// The index can be 4096 itself (a phase just below 0 plus 4096 rounds up); the table's entry 4096 equals entry 0.
+__global__ void __launch_bounds__(64) be_ncof_kernel(BeChan* __restrict__ ch, const BeBufs* __restrict__ bufs, int n_ch)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= n_ch) return;
+    BeChan& s = ch[c];
+    if (!s.ncof) return;
+    const int n = (int)bufs[c].n_in;
+    uint16_t* __restrict__ ph = bufs[c].ph;
+    const float inc = s.ncof_inc;
+    float p = s.ncof_phase;
+    const float T = (float)BE_NCO_N;
+    int j = 0;
+    if (fabsf(inc) <= T) {
+        // the phase is in [0, T] and the increment within +-T: the first loop runs at most twice (T itself wraps to 0), the
+        // second at most once, so both are selects; four samples a trip, one 8-byte store (the arena is 256-byte aligned)
+        auto step = [&]() -> uint32_t {
+            p += inc;
+            p = p >= T ? p - T : p;
+            p = p >= T ? p - T : p;
+            p = p < 0.0f ? p + T : p;
+            return (uint32_t)(int)p;
+        };
+        for (; j + 4 <= n; j += 4) {
+            const uint32_t a = step(), b = step(), c2 = step(), d = step();
+            *reinterpret_cast<uint2*>(ph + j) = make_uint2(a | (b << 16), c2 | (d << 16));
+        }
+    }
+    for (; j < n; j++) {
+        p += inc;
+        while (p >= T) p -= T;
+        while (p < 0.0f) p += T;
+        ph[j] = (uint16_t)(int)p;
+    }
+    s.ncof_phase = p;
+}
+
 // ---- 2a. NCO mix of history + new samples into float (exact: int16 -> float, complex product)
 __global__ __launch_bounds__(256)
 void be_mix_kernel(const BeChan* __restrict__ ch, const BeBufs* __restrict__ bufs, const float* __restrict__ nco_tbl)
@@ -251,17 +308,23 @@ void be_mix_kernel(const BeChan* __restrict__ ch, const BeBufs* __restrict__ buf
         // phase after nextPhase() for this sample; s.nco_phase is still the phase BEFORE this feed
         // (phase + (j + 1) * inc) mod 4096, non-negative -- what NCO::nextPhase's add-and-wrap loop arrives at; in 24-bit
         // arithmetic on the residues (the table size is a power of two, so the masks are exact for negative j + 1 and inc too)
-        const uint32_t p = ((uint32_t)s.nco_phase + ((uint32_t)(j + 1) & (BE_NCO_N - 1)) * ((uint32_t)s.nco_inc & (BE_NCO_N - 1))) & (BE_NCO_N - 1);
+        uint32_t p = ((uint32_t)s.nco_phase + ((uint32_t)(j + 1) & (BE_NCO_N - 1)) * ((uint32_t)s.nco_inc & (BE_NCO_N - 1))) & (BE_NCO_N - 1);
+        if (s.ncof) p = (uint32_t)(j < 0 ? b.ph_hist[i] : b.ph[j]) & (BE_NCO_N - 1);       // NCOF: m_table[4096] == m_table[0]
         const float o_r = tbl[p], o_i = -tbl[(p + BE_NCO_N / 4) & (BE_NCO_N - 1)];
         const float a = (float)(int16_t)(v & 0xffffu), q = (float)(int16_t)(v >> 16);
         float2 m; m.x = a * o_r - q * o_i; m.y = a * o_i + q * o_r;         // std::complex<float> operator*=
         b.mixed[i] = m;
+        if (s.bypass && j >= 0) {                           // processOneSample(c): straight into the filter's block
+            b.res[s.pending + j] = m;
+            if (s.filt_mode == 0 && s.discri == 0) b.cplx_out[j] = m;
+        }
     }
     // raw history for the next feed: last BE_HIST of (old history ++ new input); double-buffered, so nothing read here is overwritten
     if (blockIdx.x == 0) {
         for (int i = threadIdx.x; i < BE_HIST; i += blockDim.x) {
             const long src = (long)i + s.n_in - BE_HIST;
             b.hist_next[i] = src >= 0 ? b.in[src] : b.hist[i + s.n_in];
+            if (s.ncof) b.ph_hist_next[i] = src >= 0 ? b.ph[src] : b.ph_hist[i + s.n_in];
         }
     }
 }
@@ -327,7 +390,7 @@ __global__ void __launch_bounds__(256) be_fir_kernel(const BeChan* __restrict__ 
     bool shared = nt0 <= BE_FIR_NT_MAX;
     for (int q = q0; q < q_end; q++) {
         const BeChan& s = ch[perm[q]];
-        n_res_max = max(n_res_max, s.n_res);
+        n_res_max = max(n_res_max, s.bypass ? 0 : s.n_res);
         shared = shared && s.taps_off == off0 && s.ntaps == nt0 && s.phase_steps == 16;
     }
     if (o0 >= n_res_max) return;                            // uniform
@@ -352,7 +415,7 @@ __global__ void __launch_bounds__(256) be_fir_kernel(const BeChan* __restrict__ 
         const int c = perm[q0 + col];
         const BeChan& s = ch[c];
         const BeBufs& b = bufs[c];
-        const int n_res = s.n_res;
+        const int n_res = s.bypass ? 0 : s.n_res;           // a channel without the Interpolator has no schedule entries
         if (o0 >= n_res) continue;                          // wave-uniform
         const bool valid = o < n_res;
         const uint2 e = tile[lane][col];
@@ -407,7 +470,7 @@ void be_fft_kernel(const BeChan* __restrict__ ch, const BeBufs* __restrict__ buf
     const float2* filt = filters + s.filt_off;
     for (int i = tid; i < H; i += NT) {
         float2 lo = ya[i], hi = ya[H + i];
-        if (s.filt_mode == 1 || s.filt_mode == 4) { lo = c_mul(lo, filt[i]); hi = c_mul(hi, filt[H + i]); }   // runFilt / runDSB (getDC)
+        if (s.filt_mode == 1 || s.filt_mode == 4 || s.filt_mode == 7) { lo = c_mul(lo, filt[i]); hi = c_mul(hi, filt[H + i]); }   // runFilt / runDSB (getDC)
         else if (i == 0) { lo = c_mul(lo, filt[0]); /* bin N/2 is left untouched (fftfilt.cpp:294-311, 374-392) */ }
         else if (s.filt_mode == 5) { lo = c_mul(lo, filt[i]); hi = c_mul(hi, filt[BE_FFT_MAX + H + i]); }         // runAsym usb: lsb side through filterOpp
         else if (s.filt_mode == 6) { lo = c_mul(lo, filt[BE_FFT_MAX + i]); hi = c_mul(hi, filt[H + i]); }         // runAsym lsb

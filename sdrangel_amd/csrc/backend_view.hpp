@@ -15,5 +15,9 @@ int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream);
 // A back-end that has not been fed yet: channel ch resamples with this distance step (UDPSrc divides by a float rate) and its
 // m_sampleDistanceRemain starts at `distance` instead of 0 (UDPSrc starts at one step).  step >= 1, distance >= 0.
 int backend_start_at(sdrx_backend_t* b, int32_t ch, float step, float distance);
+// A back-end that has not been fed yet: channel ch runs without the Interpolator (bypass: every NCO-mixed sample is a filter
+// input, as ChannelAnalyzer does with m_useInterpolator off) and / or with NCOF, the oscillator with a float phase and a float
+// increment (ncof.h), in place of NCO.
+int backend_set_front(sdrx_backend_t* b, int32_t ch, int bypass, int ncof);
 
 } // namespace sdrx

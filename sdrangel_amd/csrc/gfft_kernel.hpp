@@ -27,14 +27,15 @@ __device__ __forceinline__ float2 c_mul(float2 a, float2 b) { float2 t; t.x = a.
 // N = 1024: stage list R2(bitrev) + 3 x radix-8 (D = 2, 16, 128);  N = 2048: R2(bitrev) + bfR2 (:531-635 /
 // ibfR2 :1577-1681: twiddles 1 and -/+i) + 3 x radix-8 (D = 4, 32, 256);  N = 512: R2(bitrev) + bfR4 (:637-841 / ibfR4
 // :1683-1887, NDiffU = 2: per 8 points the even ones take twiddles 1 and -/+i, the odd ones -/+i and w1 = cos(pi/4) in the
-// `a - b*w1 ...; partner = 2*a - result` form) + 2 x radix-8 (D = 8, 64).  inverse: first stage scaled by 1/N, multipliers
-// conjugated.
+// `a - b*w1 ...; partner = 2*a - result` form) + 2 x radix-8 (D = 8, 64);  N = 8192 (fftcorr): R2(bitrev) + 4 x radix-8
+// (D = 2, 16, 128, 1024), the stages ffts1 reaches through fftrecurs (:1161-1177), whose blocking reorders the passes of
+// separate sub-transforms and no arithmetic.  inverse: first stage scaled by 1/N, multipliers conjugated.
 template<int N, bool INVERSE>
 __device__ __forceinline__ void gfft(float2* __restrict__ y, const float2* __restrict__ x, const float* __restrict__ u, int tid)
 {
     constexpr int NT = N / 8;
-    constexpr int M = N == 512 ? 9 : (N == 1024 ? 10 : 11);
-    static_assert(N == 512 || N == 1024 || N == 2048, "fftfilt lengths of the demods and of UDPSrc");
+    constexpr int M = N == 512 ? 9 : (N == 1024 ? 10 : (N == 2048 ? 11 : 13));
+    static_assert(N == 512 || N == 1024 || N == 2048 || N == 8192, "fftfilt lengths of the demods and of UDPSrc; fftcorr's 8192");
     const float scale = (float)(1.0 / N);
     for (int j = tid; j < N / 2; j += NT) {
         const unsigned r = __brev((unsigned)(2 * j)) >> (32 - M);
@@ -44,7 +45,7 @@ __device__ __forceinline__ void gfft(float2* __restrict__ y, const float2* __res
         y[2 * j] = s; y[2 * j + 1] = d;
     }
     __syncthreads();
-    constexpr int D0 = N == 512 ? 8 : (N == 1024 ? 2 : 4);
+    constexpr int D0 = N == 512 ? 8 : (N == 2048 ? 4 : 2);
     if constexpr (N == 2048) {
         for (int k = 4 * tid; k < N; k += 4 * NT) {
             const float2 a = y[k], b = y[k + 2], c = y[k + 1], d = y[k + 3];

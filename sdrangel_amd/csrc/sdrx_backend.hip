@@ -27,6 +27,7 @@ void work(Carver& k, int64_t cap_in, size_t half, BeBufs& u)
     const size_t n_res_max = (size_t)cap_in + 1024;
     const size_t n_blk_max = n_res_max / half + 2;
     u.mixed = k.take<float2>((size_t)(BE_HIST + cap_in));
+    u.ph = k.take<uint16_t>((size_t)cap_in);
     u.res = k.take_kept<float2>(n_res_max + BE_FFT, BE_FFT);
     u.head = k.take<float2>(n_blk_max * half);
     u.tail = k.take_kept<float2>((n_blk_max + 1) * half, half);
@@ -37,7 +38,7 @@ void work(Carver& k, int64_t cap_in, size_t half, BeBufs& u)
 struct ChanHost {
     sdrx_backend_cfg cfg;
     DevBuf arena;                 // work()'s layout for cap_in samples
-    uint32_t* hist[2] = { nullptr, nullptr };
+    uint32_t* hist[2] = { nullptr, nullptr };   // BE_HIST packed Samples, then BE_HIST NCOF table indices
     int cur = 0;
     int64_t cap_in = 0;
     DevBuf stage_in;              // host-pointer feeds
@@ -63,6 +64,8 @@ struct sdrx_backend {
     float* d_utbl = nullptr; float* d_utbl2 = nullptr;     // g_fft cosine tables for N = 1024 / 2048
     bool any1024 = false, any2048 = false;
     bool any_dyadic = false;      // some resampling ratio has a closed-form schedule
+    bool any_ncof = false;        // some channel's oscillator is NCOF (backend_set_front)
+    bool all_bypass = false;      // no channel has an Interpolator: no schedule, no FIR
     InterpTables taps; std::vector<float> filters_all;     // kept for inspection (tests)
     std::vector<int> perm, col_of;    // schedule column q holds channel perm[q]; col_of[c] is its inverse
     int* d_perm = nullptr;
@@ -112,7 +115,7 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
     if (n_ch <= 0 || !cfg) { set_error("sdrx_backend_create: bad argument"); return SDRX_EINVAL; }
     for (int c = 0; c < n_ch; c++) {
         const sdrx_backend_cfg& k = cfg[c];
-        if (k.in_rate <= 0 || k.out_rate <= 0 || k.out_rate > k.in_rate || k.filt_mode < 0 || k.filt_mode > 6 ||
+        if (k.in_rate <= 0 || k.out_rate <= 0 || k.out_rate > k.in_rate || k.filt_mode < 0 || k.filt_mode > 7 ||
             k.discri < 0 || k.discri > 2 || k.taps_per_phase <= 0 || k.taps_per_phase * 16 > BE_HIST) {
             set_error("sdrx_backend_create: bad channel configuration (need out_rate <= in_rate, taps_per_phase*16 <= 256)");
             return SDRX_EINVAL;
@@ -150,6 +153,13 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
         auto design = [&](int which) -> int {
             float2* dst = b->d_filters + (size_t)c * 2 * BE_FFT_MAX + (size_t)which * BE_FFT_MAX;
             float* copy = &b->filters_all[((size_t)c * 2 + (size_t)which) * BE_FFT_MAX * 2];
+            if (k.filt_mode == 7) {                         // create_rrc_filter(fb = f1, a = f2): no transform, the bins themselves
+                std::vector<float> f((size_t)BE_FFT_MAX * 2);
+                fftfilt_rrc(k.f1, k.f2, f.data(), BE_FFT_MAX);
+                SDRX_HIP(hipMemcpy(dst, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+                std::copy(f.begin(), f.end(), copy);
+                return SDRX_OK;
+            }
             if (k.filt_mode < 4)
                 return design_fft_filter<BE_FFT>(dst, b->d_utbl, b->core.stream, copy, [&](float* f, int h2) { fftfilt_fill_band(k.f1, k.f2, f, h2); });
             // fftfilt(f2, len) / create_asym_filter(fopp = f1, fin = f2)
@@ -171,8 +181,8 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
         if (s.dy_q >= 0) b->any_dyadic = true;
         s.half = flen / 2;
         for (int i = 0; i < 2; i++) {
-            SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.hist[i]), BE_HIST * 4), sdrx_backend_destroy(b));
-            SDRX_HIP_ELSE(hipMemsetAsync(h.hist[i], 0, BE_HIST * 4, b->core.stream), sdrx_backend_destroy(b));   // on the handle's own (non-blocking) stream: ordered before its kernels
+            SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&h.hist[i]), BE_HIST * 6), sdrx_backend_destroy(b));
+            SDRX_HIP_ELSE(hipMemsetAsync(h.hist[i], 0, BE_HIST * 6, b->core.stream), sdrx_backend_destroy(b));   // on the handle's own (non-blocking) stream: ordered before its kernels
         }
     }
     // schedule columns: channels sorted by tap table, so that a FIR tile of 16 columns normally sees one design
@@ -209,7 +219,7 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
         n_max = std::max(n_max, n_per_ch[c]);
         // every resampler output after the first two of a stream consumes >= floor(step) inputs (distance >= step before the `-= 1` walk)
         const int64_t per_out = std::max<int64_t>(1, (int64_t)std::floor(b->h_chan[(size_t)c].step));
-        n_res_bound = std::max(n_res_bound, n_per_ch[c] / per_out + 4);
+        if (!b->h_chan[(size_t)c].bypass) n_res_bound = std::max(n_res_bound, n_per_ch[c] / per_out + 4);
     }
     if (n_max + 1024 > b->sched_cap) {
         int64_t cap = b->sched_cap ? b->sched_cap : 8192;
@@ -225,6 +235,7 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
         BeBufs& u = b->h_bufs[c];
         u.in = reinterpret_cast<const uint32_t*>(d_iq[c]);
         u.hist = h.hist[h.cur]; u.hist_next = h.hist[h.cur ^ 1];
+        u.ph_hist = reinterpret_cast<const uint16_t*>(u.hist + BE_HIST); u.ph_hist_next = reinterpret_cast<uint16_t*>(u.hist_next + BE_HIST);
         u.sched = static_cast<uint2*>(b->sched.p) + b->col_of[(size_t)c]; u.sched_stride = b->n_ch;
         Carver k{static_cast<char*>(h.arena.p)};
         h.lay()(k, h.cap_in, u);
@@ -235,23 +246,31 @@ static int feed_common(sdrx_backend* b, const int16_t* const* d_iq, const int64_
     // closed-form schedule for dyadic ratios (prep decides per channel and feed), the serial walk for the rest
     hipLaunchKernelGGL(be_sched_dyadic_prep_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
     SDRX_HIP(hipGetLastError());
-    if (b->any_dyadic) {
+    if (b->any_dyadic && !b->all_bypass) {
         hipLaunchKernelGGL(be_sched_dyadic_fill_kernel, dim3((unsigned)((n_res_bound + 255) / 256), (unsigned)((b->n_ch + 63) / 64)), dim3(256), 0,
                            b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
         SDRX_HIP(hipGetLastError());
     }
     // always launched: lanes whose channel the closed form took exit at once (prep's off-grid guard can hand a channel back)
-    hipLaunchKernelGGL(be_schedule_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
-    SDRX_HIP(hipGetLastError());
+    if (!b->all_bypass) {
+        hipLaunchKernelGGL(be_schedule_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_perm, b->n_ch);
+        SDRX_HIP(hipGetLastError());
+    }
+    if (b->any_ncof) {                                      // needs the counts only, like the schedule
+        hipLaunchKernelGGL(be_ncof_kernel, dim3((unsigned)((b->n_ch + 63) / 64)), dim3(64), 0, b->core.stream, b->d_chan, b->d_bufs, b->n_ch);
+        SDRX_HIP(hipGetLastError());
+    }
     rc = demod_stream_after(b->core.stream, producer, b->prod_ev); if (rc) return rc;
     // be_mix stages the 16 KB NCO table per workgroup: at least 8192 samples each
     const unsigned gx_mix = (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (n_max + BE_HIST + 8191) / 8192));
     hipLaunchKernelGGL(be_mix_kernel, dim3(gx_mix, (unsigned)b->n_ch), dim3(256), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_nco);
     SDRX_HIP(hipGetLastError());
     rc = demod_stream_after(producer, b->core.stream, b->cons_ev); if (rc) return rc;
-    hipLaunchKernelGGL(be_fir_kernel, dim3((unsigned)((n_res_bound + BE_FIR_TO - 1) / BE_FIR_TO), (unsigned)((b->n_ch + BE_FIR_TC - 1) / BE_FIR_TC)), dim3(256), 0,
-                       b->core.stream, b->d_chan, b->d_bufs, b->d_taps, b->d_perm, b->n_ch);
-    SDRX_HIP(hipGetLastError());
+    if (!b->all_bypass) {
+        hipLaunchKernelGGL(be_fir_kernel, dim3((unsigned)((n_res_bound + BE_FIR_TO - 1) / BE_FIR_TO), (unsigned)((b->n_ch + BE_FIR_TC - 1) / BE_FIR_TC)), dim3(256), 0,
+                           b->core.stream, b->d_chan, b->d_bufs, b->d_taps, b->d_perm, b->n_ch);
+        SDRX_HIP(hipGetLastError());
+    }
     if (b->any1024) {
         const unsigned max_blocks = (unsigned)((n_max + BE_FFT) / (BE_FFT / 2) + 1);
         hipLaunchKernelGGL(be_fft_kernel<BE_FFT>, dim3(max_blocks, (unsigned)b->n_ch), dim3(BE_FFT / 8), 0, b->core.stream, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl);
@@ -358,6 +377,22 @@ int backend_view(sdrx_backend_t* b, int32_t c, BackendView* v)
 int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream)
 {
     return b ? b->core.set_stream(hip_stream) : SDRX_EINVAL;
+}
+
+int backend_set_front(sdrx_backend_t* b, int32_t c, int bypass, int ncof)
+{
+    if (!b || c < 0 || c >= b->n_ch) { set_error("backend_set_front: bad argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
+    BeChan& s = b->h_chan[(size_t)c];                       // the config part and a fresh state
+    const sdrx_backend_cfg& k = b->ch[(size_t)c].cfg;
+    s.bypass = bypass ? 1 : 0;
+    s.ncof = ncof ? 1 : 0;
+    s.ncof_inc = ((float)k.nco_freq * BE_NCO_N) / (float)k.in_rate;     // NCOF::setFreq(Real freq, Real sampleRate)
+    b->any_ncof = false; b->all_bypass = true;
+    for (const BeChan& q : b->h_chan) { b->any_ncof = b->any_ncof || q.ncof; b->all_bypass = b->all_bypass && q.bypass; }
+    SDRX_HIP(hipMemcpy(b->d_chan + c, &s, sizeof s, hipMemcpyHostToDevice));
+    return SDRX_OK;
 }
 
 int backend_start_at(sdrx_backend_t* b, int32_t c, float step, float distance)

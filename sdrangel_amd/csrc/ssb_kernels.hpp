@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ssb_scan.hpp"
+#include "span_group.hpp"
 #include "demod_psum.hpp"
 #include "demod_wg.hpp"
 #include "dsp_device.hpp"
@@ -82,10 +83,7 @@ void ssb_level_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs
     }
     double m = 0.0;
     if (i < ncl) {
-        const int last = i0 + (int)i * decim, first = last - decim + 1;
-        float2 acc = make_float2(0.0f, 0.0f);
-        if (first < 0) acc = s.open_sum;                    // the group that was open when the feed began
-        for (int j = max(first, 0); j <= last; j++) { const float2 v = b.s[j]; acc.x += v.x; acc.y += v.y; }
+        const float2 acc = span_group_sum(b.s, s.open_sum, i0, decim, (int)i);
         const float avgr = acc.x / (float)decim, avgi = acc.y / (float)decim;
         m = (double)(avgr * avgr + avgi * avgi) / (32768.0 * 32768.0);
         const int re = sdrx_to_q16(s.swap_iq ? avgi : avgr), im = sdrx_to_q16(s.swap_iq ? avgr : avgi);
@@ -202,11 +200,7 @@ void ssb_carry_kernel(SsbChan* __restrict__ ch, const SsbBufs* __restrict__ bufs
     for (int i = tid; i < K; i += 256) b.whist_next[i] = am_hist_next(b.whist, K, (const float2*)b.w, n, i);
     if (tid == 0) {
         s.total = s.total_next;
-        // the open group: what was carried if nothing closed, then the samples after the last close (fewer than decim)
-        const int i0 = ssb_first_close(s.usc, s.decim), ncl = s.n_spec;
-        float2 acc = ncl > 0 ? make_float2(0.0f, 0.0f) : s.open_sum;
-        for (int j = ncl > 0 ? i0 + (ncl - 1) * s.decim + 1 : 0; j < n; j++) { const float2 v = b.s[j]; acc.x += v.x; acc.y += v.y; }
-        s.open_sum = acc;
+        s.open_sum = span_open_sum(b.s, s.open_sum, ssb_first_close(s.usc, s.decim), s.decim, s.n_spec, n);
         s.usc += (unsigned)n;
     }
 }
