@@ -8,10 +8,11 @@ ChannelAnalyzer channels:
             root raised cosine) -> span decimation -> the Samples the analyzer's scope and spectrum see, or their autocorrelation
         ->  one .npy file of Samples (re, im) per slice
 
-    python examples/filesource_to_chanalyzer.py [out_dir]   # writes a synthetic recording, replays it, saves the Samples
+    python examples/filesource_to_chanalyzer.py [out_dir] [--pll]   # writes a synthetic recording, replays it, saves the Samples
 
 The slices are an upper-sideband view, a lower-sideband view, a root-raised-cosine view behind the Interpolator and the
-autocorrelation of a slice.  Everything numeric runs on the MI355X through the C ABI (include/sdrx.h); this script is host glue
+autocorrelation of a slice.  With --pll the first slice becomes a DSB view with the PLL on (its tone is followed and mixed down to
+0 Hz; the lock state is printed) and the third a view of the FLL's own oscillator (input type 1).  Everything numeric runs on the MI355X through the C ABI (include/sdrx.h); this script is host glue
 only."""
 import os
 import sys
@@ -49,14 +50,20 @@ def synth_recording(path, seconds=0.4):
     return n
 
 
-def channel_settings(c, out_rate, ofs):
+#: --pll: what the first and the third slice become
+PLL_KINDS = {0: dict(pll=1), 2: dict(pll=1, fll=1, input_type=1)}
+
+
+def channel_settings(c, out_rate, ofs, pll=False):
     """the sdrx_chana_cfg fields of slice c behind a channelizer that delivers out_rate with the slice's centre at ofs"""
-    d = dict(COMMON); d.update(KINDS[c])
+    d = dict(COMMON); d.update(PLL_KINDS[c] if pll and c in PLL_KINDS else KINDS[c])
     d.update(in_rate=out_rate, nco_freq=-ofs)
+    if pll and c == 0:
+        d["nco_freq"] -= int(TONES[0]) - 10                 # the slice's tone 10 Hz above the loop's centre
     return d
 
 
-def main(out_dir):
+def main(out_dir, pll=False):
     os.makedirs(out_dir, exist_ok=True)
     rec = os.path.join(out_dir, "synthetic_chanalyzer.sdriq")
     n = synth_recording(rec)
@@ -66,7 +73,7 @@ def main(out_dir):
 
     fifo = sa.SampleSinkFifo(FS // 4)
     bank = sa.ChannelizerBank(FS, [REQ_RATE] * len(CENTRES), CENTRES)
-    ana = sa.ChannelAnalyzerBank([sa.ChanaCfg(**channel_settings(c, *bank.info(c)[1:])) for c in range(len(CENTRES))])
+    ana = sa.ChannelAnalyzerBank([sa.ChanaCfg(**channel_settings(c, *bank.info(c)[1:], pll=pll)) for c in range(len(CENTRES))])
 
     samples = [[] for _ in CENTRES]
     spans = []
@@ -90,9 +97,13 @@ def main(out_dir):
         what = "autocorrelation" if KINDS[c].get("input_type") == 2 else "signal"
         print(f"slice {c}: {fc:+8d} Hz  {s.shape[0]} Samples ({what}, positive only: {ana.positive_only(c)}), magsq {ana.magsq(c):.3e}, "
               f"peak |re| {int(np.abs(s[:, 0].astype(np.int32)).max()) if s.size else 0} -> {p}")
+    if pll:
+        locked, freq, dphi, phi = ana.pll_state(0)
+        print(f"slice 0: PLL locked {locked}, frequency {float(freq) * bank.info(0)[1] / (2 * np.pi):+.1f} Hz, delta phi {float(dphi):+.4f}, phase {float(phi):+.4f}")
     print(f"{n} input samples replayed from {rec}")
-    return {"recording": rec, "npy": paths, "spans": spans}
+    return {"recording": rec, "npy": paths, "spans": spans, "pll_state": ana.pll_state(0) if pll else None}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "examples_out")
+    _args = [a for a in sys.argv[1:] if a != "--pll"]
+    main(_args[0] if _args else "examples_out", pll="--pll" in sys.argv[1:])

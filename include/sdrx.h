@@ -951,7 +951,8 @@ int sdrx_ssb_last_launch(const sdrx_ssb_t* h, char* kernel_name, int name_cap,
  *   - with down_sample the last design of the root raised cosine is applySettings' own, create_rrc_filter(bandwidth / (float)
  *     down_sample_rate, rrc_rolloff / 100.0), on the bandwidth as the settings have it (no flip, no clamp)
  *   - frrc's cosine is the host's cosf
- *   - left out: m_channelPowerAvg (GUI only), mid-stream changes of settings, the PLL, the FLL and the PLL input
+ *   - left out: m_channelPowerAvg (GUI only) and mid-stream changes of settings; the PLL, the FLL and the PLL input are
+ *     sdrx_chanapll_create's (below)
  * SDRX_EINVAL for pll, fll, input_type 1 (or anything but 0 and 2), span_log2 outside 0 .. 8, rrc_rolloff outside 0 .. 100,
  * down_sample with down_sample_rate outside 1 .. in_rate, and |nco_freq| > in_rate (NCOF's wrap loops would not end).
  * ------------------------------------------------------------------------------------------ */
@@ -967,9 +968,9 @@ typedef struct sdrx_chana_cfg {
     int32_t ssb;                  /* m_ssb */
     int32_t rrc;                  /* m_rrc (used when ssb is 0) */
     int32_t rrc_rolloff;          /* m_rrcRolloff, hundredths, 0 .. 100 */
-    int32_t input_type;           /* m_inputType: 0 signal, 2 autocorrelation */
-    int32_t pll;                  /* m_pll: must be 0 */
-    int32_t fll;                  /* m_fll: must be 0 */
+    int32_t input_type;           /* m_inputType: 0 signal, 2 autocorrelation; 1, the PLL, through sdrx_chanapll_create */
+    int32_t pll;                  /* m_pll: must be 0 for sdrx_chana_create */
+    int32_t fll;                  /* m_fll: must be 0 for sdrx_chana_create */
 } sdrx_chana_cfg;
 int sdrx_chana_create(sdrx_chana_t** out, int device, int32_t n_ch, const sdrx_chana_cfg* cfg);
 int sdrx_chana_destroy(sdrx_chana_t* h);
@@ -1007,6 +1008,37 @@ int sdrx_chana_get_timing(sdrx_chana_t* h, double* total_ms, int64_t* feeds, int
  * chana_group_kernel */
 int sdrx_chana_last_launch(const sdrx_chana_t* h, char* kernel_name, int name_cap,
                            int* grid, int* block, int* lds_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * ChannelAnalyzer bank with the PLL, the FLL and the PLL input: what sdrx_chana_create leaves out.  The handle is a
+ * sdrx_chana_t and works with every sdrx_chana_* call above; sdrx_chana_create and its rejections stay as they are.
+ *     per closed group, between m_magsq and feedOneSample (chanalyzer.cpp:160-178):
+ *       pll & !fll: m_pll.feed(re, im), PhaseLockComplex::feed (sdrbase/dsp/phaselockcomplex.cpp:119-214): m_y = (cos, sin) of
+ *                   m_phiHat; m_deltaPhi = arg(x * conj(m_y)), times m_pskOrder and normalizeAngle for an order above 1; the
+ *                   v0 / v1 / v2 filter, both saturation branches, ExpAvg, the lock counters;  mix = m_sum * conj(m_y)
+ *       pll &  fll: m_fll.feed(re, im), FreqLockComplex::feed (freqlockcomplex.cpp:64-80), whose m_phi is never wrapped;
+ *                   mix = m_sum * conj(m_y) likewise
+ *       feedOneSample(pll ? mix : m_sum, fll ? m_fll.getComplex() : m_pll.getComplex())
+ *     input_type 1 (InputPLL): Sample(y.real() * SDR_RX_SCALEF, y.imag() * SDR_RX_SCALEF) of the second argument, swapped for ssb
+ *       with a negative bandwidth; 32768 converts as x86-64 does, to -32768
+ *     with fll set and pll clear, or input_type 1 with both clear, no loop runs and the oscillator is the unfed one, (1, 0)
+ * Both loops feed their own output back, so only the very bits of the reference's cos, sin and arg keep a stream equal to the
+ * reference's.  They are restated (sdrangel_amd/csrc/pll_math.hpp) and run on the device: cosf / sinf are glibc's from 2.28 to
+ * 2.40 on x86-64 in the build a CPU with FMA is given (fused multiply-adds in double, rounded once), atan2f is the fdlibm float
+ * routine that glibc had up to 2.40.  The bank equals a reference built strictly (-ffp-contract=off) on such a host.
+ * A fresh handle is the object after the constructor, applySettings(settings, true), applyChannelSettings and start(), with what
+ * that order of calls leaves behind: computeCoefficients(0.002f, 0.5f, 10.0f) once; without down_sample the last setSampleRate
+ * is applyChannelSettings' (in_rate >> span_log2, the channel's own psk order); with down_sample it is applySettings' own at
+ * chanalyzer.cpp:363, which divides by the span of the settings before (0) and runs before setPskOrder (m_lockFreq as of order 1).
+ * psk_order[c] is m_pllPskOrder, 1 .. 31; NULL is 1 for every channel.  SDRX_EINVAL for what sdrx_chana_create rejects other than
+ * pll, fll and input_type 1, and for a psk_order outside 1 .. 31.
+ * sdrx_chana_last_launch names chana_walk_kernel (one wave per channel, four to a workgroup) when a channel runs a loop and
+ * none computes the autocorrelation.
+ * ------------------------------------------------------------------------------------------ */
+int sdrx_chanapll_create(sdrx_chana_t** out, int device, int32_t n_ch, const sdrx_chana_cfg* cfg, const int32_t* psk_order);
+/* isPllLocked, getPllFrequency, getPllDeltaPhase and getPllPhase after the last feed (each pointer may be NULL).  They are
+ * m_pll's: with fll set they stay as a fresh PhaseLockComplex has them */
+int sdrx_chanapll_state(sdrx_chana_t* h, int32_t ch, int32_t* locked, float* freq, float* delta_phi, float* phi_hat);
 
 /* ------------------------------------------------------------------------------------------
  * UDPSrc bank: UDPSrc::feed (plugins/channelrx/udpsrc/udpsrc.cpp:136-321), N channels per handle, each fed with int16 I/Q at

@@ -216,6 +216,8 @@ def lib() -> C.CDLL:
         "sdrx_chana_magsq": (C.c_int, [vp, i32, C.POINTER(C.c_double)]),
         "sdrx_chana_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(C.c_float)]),
         "sdrx_chana_seek": (C.c_int, [vp, i32, C.c_uint64]),
+        "sdrx_chanapll_create": (C.c_int, [pp, C.c_int, i32, vp, vp]),
+        "sdrx_chanapll_state": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "sdrx_udpsrc_ssb_state": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i64), vp]),
         "sdrx_udpsrc_destroy": (C.c_int, [vp]),
         "sdrx_udpsrc_reset": (C.c_int, [vp]),
@@ -1185,9 +1187,32 @@ class UdpPayloadCutter:
 
 
 class ChannelAnalyzerBank(_DemodBank):
-    """N ChannelAnalyzers (ChannelAnalyzer::feed, PLL off): int16 I/Q at the channelizer's output rate in; the Samples the
-    analyzer hands to its scope / spectrum sink out, the signal itself or its autocorrelation."""
+    """N ChannelAnalyzers (ChannelAnalyzer::feed): int16 I/Q at the channelizer's output rate in; the Samples the analyzer
+    hands to its scope / spectrum sink out: the signal itself, its autocorrelation or the PLL's oscillator.  A bank in which a
+    cfg sets pll or fll, or input_type 1, or which is given psk_order (m_pllPskOrder per channel, 1 .. 31), is created through
+    sdrx_chanapll_create; pll_state(ch) then reads the loop."""
     _prefix, _cfg = "chana", ChanaCfg
+
+    def __init__(self, cfgs, device: int = 0, psk_order=None):
+        if psk_order is None and not any(k.pll or k.fll or k.input_type == 1 for k in cfgs):
+            super().__init__(cfgs, device)
+            return
+        self.n_ch = len(cfgs)
+        arr = (self._cfg * self.n_ch)(*cfgs)
+        order = None
+        if psk_order is not None:
+            if len(psk_order) != self.n_ch:
+                raise ValueError("psk_order: one per channel")
+            order = (C.c_int32 * self.n_ch)(*[int(v) for v in psk_order])
+        self._h = C.c_void_p()
+        _check(lib().sdrx_chanapll_create(C.byref(self._h), device, self.n_ch, arr, order), "sdrx_chanapll_create")
+        self.cfgs = list(cfgs)
+
+    def pll_state(self, ch: int):
+        """(isPllLocked, getPllFrequency, getPllDeltaPhase, getPllPhase) after the last feed, the floats as np.float32"""
+        k, f, d, p = C.c_int32(), C.c_float(), C.c_float(), C.c_float()
+        _check(lib().sdrx_chanapll_state(self._h, ch, C.byref(k), C.byref(f), C.byref(d), C.byref(p)), "sdrx_chanapll_state")
+        return bool(k.value), np.float32(f.value), np.float32(d.value), np.float32(p.value)
 
     def read(self, ch: int, cap: int | None = None) -> np.ndarray:
         """the last feed's Samples as an [n, 2] array of (re, im)"""

@@ -1,5 +1,5 @@
 // ChannelAnalyzer bank kernels: what ChannelAnalyzer::processOneSample and feedOneSample do with the filter's output
-// (plugins/channelrx/chanalyzer/chanalyzer.cpp:128-182, chanalyzer.h:250-287, m_pll off).  The front (NCOF, the optional
+// (plugins/channelrx/chanalyzer/chanalyzer.cpp:128-182, chanalyzer.h:250-287; what m_pll, m_fll and InputPLL add is chana_pll_kernels.hpp's).  The front (NCOF, the optional
 // Interpolator, fftfilt runSSB / runDSB / runFilt) is the channel back-end's (backend_kernels.hpp); these kernels start from
 // its stream `s`, which arrives in blocks of 512 (SSB) or 1024 samples.
 //     m_sum += s[j];  every (1 << span_log2)-th sample: m_sum /= decim, m_magsq, feedOneSample(m_sum), m_sum = 0
@@ -16,6 +16,7 @@
 #include "span_group.hpp"
 #include "gfft_kernel.hpp"
 #include "dsp_device.hpp"
+#include "pll_math.hpp"
 
 namespace sdrx {
 
@@ -28,11 +29,14 @@ struct ChanaChan {                      // device resident: config + carried sta
     int decim;                          // 1 << span_log2
     int swap_iq;                        // m_ssb & !m_usb: the Sample is (im, re)
     int corr;                           // input_type == InputAutoCorr
+    int osc_out;                        // input_type == InputPLL: the Sample is the oscillator
+    PllCfg pk;                          // m_pll / m_fll, m_pllPskOrder and what the configuration sequence left in both loops
     // --- state
     unsigned usc;                       // m_undersampleCount; only its low bits matter
     float2 open_sum;                    // m_sum of the open group
     double magsq;                       // m_magsq
     int fill;                           // fftcorr: calls so far modulo 4096 = inputs waiting in the open block
+    PllState ps;                        // PhaseLockComplex and FreqLockComplex
     // --- per feed
     int n, n_out;                       // filtered samples; Samples
 };
@@ -45,7 +49,12 @@ struct ChanaBufs {                      // per channel device pointers (per feed
     int16_t* out;                       // re, im pairs of this feed's Samples, 4-byte aligned
     float2* g;                          // fftcorr: this feed's inputs, one per closed group
     float2* pblk;                       // fftcorr: lags 0 .. 4095 of every block this feed completed
+    float2* avg;                        // PLL / FLL / InputPLL: m_sum of every closed group, for the stages behind the group kernel
+    float2* osc;                        // PLL / FLL: the oscillator (cos, sin) of every step
 };
+
+// the channel's Samples come from chana_post_kernel (chana_pll_kernels.hpp), not from the group kernel
+__device__ __forceinline__ bool chana_has_post(const ChanaChan& s) { return s.pk.mode != PLL_OFF || s.osc_out; }
 
 // input number idx of fftcorr counted from the start of the block that was open when the feed began
 __device__ __forceinline__ float2 chana_corr_in(const ChanaBufs& b, int fill, long idx) { return idx < fill ? b.part[idx] : b.g[idx - fill]; }
@@ -68,6 +77,7 @@ void chana_group_kernel(ChanaChan* __restrict__ ch, const ChanaBufs* __restrict_
     const float avgr = acc.x / (float)decim, avgi = acc.y / (float)decim;         // m_sum /= decim
     const float re = avgr / 32768.0f, im = avgi / 32768.0f;                       // SDR_RX_SCALEF
     if (i == ncl - 1) s.magsq = (double)(re * re + im * im);
+    if (chana_has_post(s)) { b.avg[i] = make_float2(avgr, avgi); return; }
     if (s.corr) {
         const float k = 32768.0f / 768.0f;                                        // s / (SDR_RX_SCALEF / 768.0f)
         b.g[i] = make_float2(avgr / k, avgi / k);

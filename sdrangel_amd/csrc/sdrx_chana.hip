@@ -1,11 +1,12 @@
-// libsdrx.so: sdrx_chana_* -- N ChannelAnalyzers (ChannelAnalyzer::feed, plugins/channelrx/chanalyzer/chanalyzer.cpp:92-182, m_pll
-// off) on one device: int16 I/Q at the channelizer's output rate in, the Samples the analyzer hands to its scope / spectrum sink
+// libsdrx.so: sdrx_chana_* and sdrx_chanapll_* -- N ChannelAnalyzers (ChannelAnalyzer::feed, plugins/channelrx/chanalyzer/
+// chanalyzer.cpp:92-182; with m_pll, m_fll and InputPLL through sdrx_chanapll_create) on one device: int16 I/Q at the channelizer's output rate in, the Samples the analyzer hands to its scope / spectrum sink
 // out.  The front (NCOF, the optional Interpolator, fftfilt runSSB / runDSB / runFilt) is a channel back-end the handle owns and
-// launches on its own stream; the tail's kernels are in chana_kernels.hpp.  Host side: the design products as the constructor,
+// launches on its own stream; the tail's kernels are in chana_kernels.hpp and chana_pll_kernels.hpp.  Host side: the design products as the constructor,
 // applySettings(settings, true), applyChannelSettings and start() leave them (:35-65, 247-392), the two layouts and the
 // launches; the rest is demod_bank.hpp's.
 #include "sdrx_common.hpp"
 #include "chana_kernels.hpp"
+#include "chana_pll_kernels.hpp"
 #include "backend_design.hpp"
 #include "demod_bank.hpp"
 #include <algorithm>
@@ -19,6 +20,10 @@ using namespace sdrx;
 
 namespace {
 constexpr int CHANA_BLOCK_MAX = 1024;               // runDSB and runFilt hand out 1024 samples at a time, runSSB 512
+
+// sdrx_chanapll_create's extras for the create underneath it: the PLL is let through, and the PSK order of every channel
+thread_local bool tl_pll_ok = false;
+thread_local const int32_t* tl_psk_order = nullptr;
 
 struct ChanaDerived { int rate; float band, low; bool usb; float rrc_fb; };
 
@@ -49,30 +54,36 @@ struct ChanaFamily : DemodDefaults {
 
     static int validate(int32_t n_ch, const sdrx_chana_cfg* cfg)
     {
-        if (n_ch <= 0 || !cfg) { set_error("sdrx_chana_create: bad argument"); return SDRX_EINVAL; }
+        const std::string who = tl_pll_ok ? "sdrx_chanapll_create" : "sdrx_chana_create";
+        if (n_ch <= 0 || !cfg) { set_error(who + ": bad argument"); return SDRX_EINVAL; }
         for (int c = 0; c < n_ch; c++) {
             const sdrx_chana_cfg& k = cfg[c];
-            if (k.in_rate <= 0) { set_error("sdrx_chana_create: bad channel configuration (need in_rate > 0)"); return SDRX_EINVAL; }
+            if (k.in_rate <= 0) { set_error(who + ": bad channel configuration (need in_rate > 0)"); return SDRX_EINVAL; }
             // NCOF's wrap loops take |nco_freq| / in_rate trips per sample and never end once 4096 is below the phase's ulp
             if ((int64_t)k.nco_freq > k.in_rate || (int64_t)k.nco_freq < -(int64_t)k.in_rate) {
-                set_error("sdrx_chana_create: bad channel configuration (need |nco_freq| <= in_rate)"); return SDRX_EINVAL;
+                set_error(who + ": bad channel configuration (need |nco_freq| <= in_rate)"); return SDRX_EINVAL;
             }
-            if (k.pll || k.fll || k.input_type == 1) {
+            if (!tl_pll_ok && (k.pll || k.fll || k.input_type == 1)) {
                 set_error("sdrx_chana_create: the PLL, the FLL and the PLL input (input_type 1) are left out: their loop is serial and calls libm (DESIGN.md 10)");
                 return SDRX_EINVAL;
             }
-            if (k.input_type != 0 && k.input_type != 2) { set_error("sdrx_chana_create: bad channel configuration (input_type is 0, signal, or 2, autocorrelation)"); return SDRX_EINVAL; }
-            if (k.span_log2 < 0 || k.span_log2 > 8) { set_error("sdrx_chana_create: bad channel configuration (need 0 <= span_log2 <= 8)"); return SDRX_EINVAL; }
-            if (k.rrc_rolloff < 0 || k.rrc_rolloff > 100) { set_error("sdrx_chana_create: bad channel configuration (need 0 <= rrc_rolloff <= 100, in hundredths)"); return SDRX_EINVAL; }
+            if (tl_pll_ok && tl_psk_order && (tl_psk_order[c] < 1 || tl_psk_order[c] > 31)) {
+                set_error(who + ": bad channel configuration (need 1 <= psk_order <= 31)"); return SDRX_EINVAL;
+            }
+            if (k.input_type < 0 || k.input_type > 2 || (!tl_pll_ok && k.input_type == 1)) {
+                set_error(who + ": bad channel configuration (input_type is 0, signal, or 2, autocorrelation" + (tl_pll_ok ? ", or 1, the PLL)" : ")")); return SDRX_EINVAL;
+            }
+            if (k.span_log2 < 0 || k.span_log2 > 8) { set_error(who + ": bad channel configuration (need 0 <= span_log2 <= 8)"); return SDRX_EINVAL; }
+            if (k.rrc_rolloff < 0 || k.rrc_rolloff > 100) { set_error(who + ": bad channel configuration (need 0 <= rrc_rolloff <= 100, in hundredths)"); return SDRX_EINVAL; }
             if (k.down_sample && (k.down_sample_rate < 1 || k.down_sample_rate > k.in_rate)) {
-                set_error("sdrx_chana_create: bad channel configuration (down_sample needs 1 <= down_sample_rate <= in_rate; the interpolating branch is left out)");
+                set_error(who + ": bad channel configuration (down_sample needs 1 <= down_sample_rate <= in_rate; the interpolating branch is left out)");
                 return SDRX_EINVAL;
             }
         }
         return SDRX_OK;
     }
 
-    static void design(int, const sdrx_chana_cfg& k, sdrx_backend_cfg& f, ChanaChan& s, float*)
+    static void design(int c, const sdrx_chana_cfg& k, sdrx_backend_cfg& f, ChanaChan& s, float*)
     {
         const ChanaDerived d = derive(k);
         f.in_rate = k.in_rate; f.nco_freq = k.nco_freq; f.out_rate = d.rate;
@@ -91,6 +102,10 @@ struct ChanaFamily : DemodDefaults {
         s.decim = 1 << k.span_log2;
         s.swap_iq = (k.ssb && !d.usb) ? 1 : 0;
         s.corr = k.input_type == 2 ? 1 : 0;
+        s.osc_out = k.input_type == 1 ? 1 : 0;
+        // both loops as the configuration sequence leaves them; the state of a fresh one is all zeros (reset() of either class)
+        s.pk = pll_design(k.in_rate, k.down_sample != 0, (unsigned)k.down_sample_rate, k.span_log2, k.pll != 0, k.fll != 0,
+                          (unsigned)(tl_psk_order ? tl_psk_order[c] : 1));
     }
 
     // the front of a ChannelAnalyzer: NCOF, and no Interpolator unless m_downSample
@@ -113,6 +128,8 @@ struct ChanaFamily : DemodDefaults {
         u.out = k.take<int16_t>(2 * n);
         u.g = k.take<float2>(s.corr ? n : 1);
         u.pblk = k.take<float2>(s.corr ? (n / CHANA_CORR_H + 1) * CHANA_CORR_H : 1);
+        u.avg = k.take<float2>(s.pk.mode != PLL_OFF || s.osc_out ? n : 1);
+        u.osc = k.take<float2>(s.pk.mode != PLL_OFF ? n : 1);
     }
 
     // the filter's inputs (one per input without the Interpolator), and the filter adds what it held back
@@ -128,6 +145,7 @@ struct ChanaFamily : DemodDefaults {
 
 struct sdrx_chana : DemodBank<ChanaFamily> {
     float* d_utbl = nullptr;      // g_fft cosine table for N = 8192, made when a channel wants the autocorrelation
+    bool walk = false, post = false;    // a channel runs a loop; a channel's Samples come from chana_post_kernel
 };
 using Bank = DemodBank<ChanaFamily>;
 
@@ -137,6 +155,16 @@ int ChanaFamily::launch(Bank& b, unsigned nc, unsigned gx)
     hipLaunchKernelGGL(chana_group_kernel, dim3(gx, nc), dim3(256), 0, b.core.stream, b.d_chan, b.d_bufs);
     SDRX_HIP(hipGetLastError());
     b.core.note_launch("chana_group_kernel", (int)(gx * nc), 256, 0);
+    if (h.walk) {
+        const unsigned gw = (nc + CHANA_WALK_WAVES - 1) / CHANA_WALK_WAVES;
+        hipLaunchKernelGGL(chana_walk_kernel, dim3(gw), dim3(64 * CHANA_WALK_WAVES), 0, b.core.stream, b.d_chan, b.d_bufs, (int)nc);
+        SDRX_HIP(hipGetLastError());
+        b.core.note_launch("chana_walk_kernel", (int)gw, 64 * CHANA_WALK_WAVES, 0);
+    }
+    if (h.post) {
+        hipLaunchKernelGGL(chana_post_kernel, dim3(gx, nc), dim3(256), 0, b.core.stream, b.d_chan, b.d_bufs);
+        SDRX_HIP(hipGetLastError());
+    }
     if (h.d_utbl) {
         // a feed whose groups number at most gx * 256 completes at most this many blocks on top of an open one
         const unsigned nblk = (unsigned)((CHANA_CORR_H - 1 + (size_t)gx * 256) / CHANA_CORR_H);
@@ -168,6 +196,30 @@ int sdrx_chana_create(sdrx_chana_t** out, int device, int32_t n_ch, const sdrx_c
         rc = design_upload(&(*out)->d_utbl, design_gfft_table(CHANA_CORR_N));
         if (rc) { sdrx_chana_destroy(*out); *out = nullptr; return rc; }
     }
+    return SDRX_OK;
+}
+
+int sdrx_chanapll_create(sdrx_chana_t** out, int device, int32_t n_ch, const sdrx_chana_cfg* cfg, const int32_t* psk_order)
+{
+    tl_pll_ok = true; tl_psk_order = psk_order;
+    const int rc = sdrx_chana_create(out, device, n_ch, cfg);
+    tl_pll_ok = false; tl_psk_order = nullptr;
+    if (rc) return rc;
+    for (const ChanaChan& s : (*out)->h_chan) {
+        (*out)->walk = (*out)->walk || s.pk.mode != PLL_OFF;
+        (*out)->post = (*out)->post || s.pk.mode != PLL_OFF || s.osc_out;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_chanapll_state(sdrx_chana_t* b, int32_t c, int32_t* locked, float* freq, float* delta_phi, float* phi_hat)
+{
+    ChanaChan s;
+    int rc = Bank::fetch(b, "state", c, &s); if (rc) return rc;
+    if (locked) *locked = s.pk.mode != PLL_OFF && pll_locked(s.pk, s.ps) ? 1 : 0;         // m_settings.m_pll && m_pll.locked()
+    if (freq) *freq = s.ps.freq;
+    if (delta_phi) *delta_phi = s.ps.dphi;
+    if (phi_hat) *phi_hat = s.ps.phi_hat;
     return SDRX_OK;
 }
 
