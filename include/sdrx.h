@@ -628,6 +628,80 @@ int sdrx_wfm_last_launch(const sdrx_wfm_t* h, char* kernel_name, int name_cap,
                          int* grid, int* block, int* lds_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * Broadcast-FM stereo demodulator bank: BFMDemod::feed (plugins/channelrx/demodbfm/bfmdemod.cpp:116-281) with m_rdsActive
+ * clear, N channels per handle, each fed with int16 I/Q at the channelizer's output rate:
+ *     Complex c(re / SDR_RX_SCALEF, im / SDR_RX_SCALEF); c *= m_nco.nextIQ();      NCO (sdrbase/dsp/nco.cpp:30-64)
+ *     rf_out = m_rfFilter->runFilt(c, &rf);                                         fftfilt 1024 at the CHANNEL rate
+ *     per rf[i]: msq = re*re + im*im (not divided by the scale) + level sums, squelch counter, phaseDiscriminator
+ *                (conj(m_m1Sample) * sample, atan2f, / M_PI * m_fmScaling) only while the squelch is open: m_m1Sample is
+ *                the last OPEN sample and survives closed stretches and feeds;
+ *                audio_stereo: m_pilotPLL.process(demod, ...) on every sample (RDSPhaseLock, phaselock.cpp:253-367),
+ *                m_interpolatorStereo.decimate on (demod * p[1], demod * p[2]) (lsb_stereo) or (demod * 1.17 * p[1], 0);
+ *                m_interpolator.decimate on Complex(demod, 0); the two LowPassFilterRC on ci + / - sampleStereo (mono: X on
+ *                ci alone); (qint16)(deemph * (1 << 12) * volume) into .l and .r
+ * Outputs: interleaved l, r qint16 audio, and the Samples of m_sampleBuffer (what the reference hands its spectrum sink):
+ * Sample(demod * SDR_RX_SCALEF, 0) per filtered sample when show_pilot is clear, Sample(m_pilotPLLSamples[1] * SDR_RX_SCALEF, 0)
+ * when show_pilot and audio_stereo are set, nothing when show_pilot is set alone.  Both are bit-identical to the strict-IEEE
+ * scalar reference build on a glibc >= 2.28 x86-64 host with FMA (the loop feeds back that libm's sinf / cosf, which are
+ * restated bit for bit; atan2f is the fdlibm routine glibc had up to 2.40).  Any feed length is valid; NCO phase, pending
+ * samples, ovlbuf, squelch counter, m_m1Sample, the pilot loop, both resampler windows and the distance, both de-emphasis
+ * filters and the level accumulators carry across feeds.
+ * NOT reproduced: RDS (m_rdsActive: the 57 kHz mixer, m_interpolatorRDS, RDSDemod / RDSDecoder / RDSParser), m_lowpass (created
+ * but never run by feed).  A channel is configured at creation; there is no mid-stream retune.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_bfm sdrx_bfm_t;
+typedef struct sdrx_bfm_cfg {
+    int32_t in_rate;        /* channelizer output rate (m_inputSampleRate): the pilot loop, m_fmScaling = in_rate / 750000.0f */
+    int32_t nco_freq;       /* m_nco.setFreq(nco_freq, in_rate): the demod passes -frequencyOffset */
+    int32_t audio_rate;     /* m_audioSampleRate; <= in_rate; de-emphasis time constant 50.0 * audio_rate * 1.0e-6 */
+    float   rf_bandwidth;   /* m_rfBandwidth: create_filter(-(rfBW / 2.0) / in_rate, +...), squelch cap rfBW / 10, open above rfBW / 20 */
+    float   af_bandwidth;   /* m_afBandwidth: both Interpolators' create(16, in_rate, afBW) */
+    float   volume;         /* m_volume */
+    float   squelch_db;     /* m_squelch: m_squelchLevel = pow(10.0, squelch / 10.0) */
+    int32_t audio_stereo;   /* m_audioStereo: 0 / 1 */
+    int32_t lsb_stereo;     /* m_lsbStereo: 0 / 1 */
+    int32_t show_pilot;     /* m_showPilot: 0 / 1 */
+} sdrx_bfm_cfg;
+/* SDRX_EINVAL with a text that names the field, before the device is touched */
+int sdrx_bfm_create(sdrx_bfm_t** out, int device, int32_t n_ch, const sdrx_bfm_cfg* cfg);
+int sdrx_bfm_destroy(sdrx_bfm_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_bfm_reset(sdrx_bfm_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to BFMDemod::feed) */
+int sdrx_bfm_feed(sdrx_bfm_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_bfm_feed_dev(sdrx_bfm_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_wfm_feed_bank */
+int sdrx_bfm_feed_bank(sdrx_bfm_t* h, sdrx_chan_bank_t* bank);
+/* audio of the last feed for channel ch as l, r pairs; cap and the return value count pairs (<0: error) */
+int64_t sdrx_bfm_read(sdrx_bfm_t* h, int32_t ch, int16_t* audio_lr, int64_t cap);
+/* device-side view of the same (valid until the next feed); n counts pairs */
+int sdrx_bfm_last_dev(sdrx_bfm_t* h, int32_t ch, const int16_t** d_audio_lr, int64_t* n);
+/* the sink stream of the last feed as (re, im) Samples, im = 0; returns the number of Samples written */
+int64_t sdrx_bfm_read_sink(sdrx_bfm_t* h, int32_t ch, int16_t* samples_iq, int64_t cap_samples);
+int sdrx_bfm_sink_last_dev(sdrx_bfm_t* h, int32_t ch, const int16_t** d_samples_iq, int64_t* n_samples);
+/* the pilot loop after the last feed: locked(), get_pilot_level(), the bits of m_freq and m_phase (any pointer may be null) */
+int sdrx_bfm_pilot(sdrx_bfm_t* h, int32_t ch, int32_t* locked, float* level, uint32_t* freq_bits, uint32_t* phase_bits);
+/* whether m_squelchState is above rfBW / 20 after the last feed: 1 / 0 (<0: error) */
+int sdrx_bfm_squelch_open(sdrx_bfm_t* h, int32_t ch);
+/* m_magsqSum / m_magsqPeak / m_magsqCount of getMagSqLevels; reset != 0 zeroes them as getMagSqLevels does.
+ * peak and count are exact; sum is a parallel double reduction (relative difference <= 2 * count * 2^-53) */
+int sdrx_bfm_levels(sdrx_bfm_t* h, int32_t ch, double* sum, double* peak, int64_t* count, int reset);
+/* design products, for inspection: as sdrx_wfm_get_design, then the pilot loop's m_minfreq, m_maxfreq, m_phasor_b0, m_phasor_a1,
+ * m_phasor_a2, m_loopfilter_b0, m_loopfilter_b1 (pll7), m_lock_delay, and LowPassFilterRC's m_b0, m_a1 (rc2) */
+int sdrx_bfm_get_design(sdrx_bfm_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap,
+                        float* filter_iq, int32_t* nco_inc, float* squelch_level, float* pll7, int32_t* lock_delay, float* rc2);
+int sdrx_bfm_sync(sdrx_bfm_t* h);
+int sdrx_bfm_set_stream(sdrx_bfm_t* h, void* hip_stream);
+int sdrx_bfm_get_stream(sdrx_bfm_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels */
+int sdrx_bfm_set_timing(sdrx_bfm_t* h, int enabled);
+int sdrx_bfm_get_timing(sdrx_bfm_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the kernel that bounds the last feed: bfm_walk_kernel with a stereo channel in the handle, else bfm_fft_kernel */
+int sdrx_bfm_last_launch(const sdrx_bfm_t* h, char* kernel_name, int name_cap,
+                         int* grid, int* block, int* lds_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * AM demodulator bank: AMDemod::feed and AMDemod::processOneSample (plugins/channelrx/demodam/amdemod.cpp:101-276) in
  * envelope mode (m_pll = false, the default), N channels per handle, each fed with int16 I/Q at the channelizer's output rate:
  *     c = Complex(re, im) * m_nco.nextIQ();  m_interpolator.decimate(&dist, c, &ci)        as sdrx_backend_* (filt_mode 0)

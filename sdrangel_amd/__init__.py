@@ -160,6 +160,20 @@ def lib() -> C.CDLL:
         "sdrx_wfm_squelch_open": (C.c_int, [vp, i32]),
         "sdrx_wfm_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_wfm_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
+        "sdrx_bfm_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_bfm_destroy": (C.c_int, [vp]),
+        "sdrx_bfm_reset": (C.c_int, [vp]),
+        "sdrx_bfm_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_bfm_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_bfm_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_bfm_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_bfm_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_bfm_read_sink": (i64, [vp, i32, vp, i64]),
+        "sdrx_bfm_sink_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_bfm_pilot": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(u32)]),
+        "sdrx_bfm_squelch_open": (C.c_int, [vp, i32]),
+        "sdrx_bfm_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+        "sdrx_bfm_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float), vp, C.POINTER(i32), vp]),
         "sdrx_am_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_am_destroy": (C.c_int, [vp]),
         "sdrx_am_reset": (C.c_int, [vp]),
@@ -283,7 +297,7 @@ def lib() -> C.CDLL:
     }
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
-                "wfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
+                "wfm": five + ("get_stream",), "bfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
                 "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
@@ -890,6 +904,13 @@ class WfmCfg(C.Structure):
                 ("audio_mute", C.c_int32)]
 
 
+class BfmCfg(C.Structure):
+    """sdrx_bfm_cfg: one BFMDemod (in_rate, nco_freq = -frequencyOffset, audio_rate, BFMDemodSettings without RDS)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
+                ("rf_bandwidth", C.c_float), ("af_bandwidth", C.c_float), ("volume", C.c_float), ("squelch_db", C.c_float),
+                ("audio_stereo", C.c_int32), ("lsb_stereo", C.c_int32), ("show_pilot", C.c_int32)]
+
+
 class AmCfg(C.Structure):
     """sdrx_am_cfg: one AMDemod in envelope mode (in_rate, nco_freq = -frequencyOffset, audio_rate, AMDemodSettings)"""
     _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
@@ -1009,6 +1030,61 @@ class WfmDemodBank(_DemodBank):
     def design(self, ch: int):
         """(taps per phase, taps [16 * ntaps], filter spectrum as 2048 floats, NCO increment, squelch level)"""
         return self._design(ch, np.zeros(2048, np.float32))
+
+
+class BfmBank(_DemodBank):
+    """N broadcast-FM stereo demodulators (BFMDemod::feed without RDS): int16 I/Q at the channelizer's output rate in; qint16 l, r
+    audio and the Samples of the sink stream out."""
+    _prefix, _cfg = "bfm", BfmCfg
+
+    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
+        """the last feed's audio as an [n, 2] array of (l, r)"""
+        if cap is None:
+            cap = self.last_dev(ch)[1]
+        out = np.empty((max(cap, 1), 2), np.int16)
+        n = self._fn("read")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_bfm_read rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def sink_last_dev(self, ch: int):
+        """(device pointer, count) of the sink stream's Samples of the last feed of channel ch"""
+        p, n = C.c_void_p(), C.c_int64()
+        self._call("sink_last_dev", ch, C.byref(p), C.byref(n))
+        return p.value or 0, n.value
+
+    def read_sink(self, ch: int, cap: int | None = None) -> np.ndarray:
+        """the Samples the last feed put into m_sampleBuffer, as an [n, 2] array of (re, im)"""
+        if cap is None:
+            cap = self.sink_last_dev(ch)[1]
+        out = np.empty((max(cap, 1), 2), np.int16)
+        n = self._fn("read_sink")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_bfm_read_sink rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def pilot(self, ch: int):
+        """(locked(), get_pilot_level(), the bits of m_freq, the bits of m_phase) after the last feed"""
+        k, lv, f, p = C.c_int32(), C.c_float(), C.c_uint32(), C.c_uint32()
+        self._call("pilot", ch, C.byref(k), C.byref(lv), C.byref(f), C.byref(p))
+        return bool(k.value), lv.value, f.value, p.value
+
+    def levels(self, ch: int, reset: bool = False):
+        """(m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""
+        s, p, n = C.c_double(), C.c_double(), C.c_int64()
+        self._call("levels", ch, C.byref(s), C.byref(p), C.byref(n), int(reset))
+        return s.value, p.value, n.value
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], filter spectrum as 2048 floats, NCO increment, squelch level, the pilot loop's
+        m_minfreq, m_maxfreq, m_phasor_b0, m_phasor_a1, m_phasor_a2, m_loopfilter_b0, m_loopfilter_b1, m_lock_delay, the RC filters'
+        (m_b0, m_a1))"""
+        nt, inc, lvl, ld = C.c_int32(), C.c_int32(), C.c_float(), C.c_int32()
+        taps, filt = np.zeros(16 * 128, np.float32), np.zeros(2048, np.float32)
+        pll, rc = np.zeros(7, np.float32), np.zeros(2, np.float32)
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, filt.ctypes.data, C.byref(inc), C.byref(lvl), pll.ctypes.data,
+                   C.byref(ld), rc.ctypes.data)
+        return nt.value, taps[: 16 * nt.value].copy(), filt, inc.value, lvl.value, pll, ld.value, rc
 
 
 class AmDemodBank(_DemodBank):

@@ -8,28 +8,11 @@
 // parallel again: chana_post_kernel makes the Sample, or fftcorr's input for the kernels of chana_kernels.hpp.
 #pragma once
 #include "chana_kernels.hpp"
+#include "wave_walk.hpp"
 
 namespace sdrx {
 
 constexpr int CHANA_WALK_WAVES = 4;                     // channels per workgroup of the walk, one wave each
-
-__device__ __forceinline__ float chana_lane_value(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// the walk's two streams as global memory by name: a generic access would count on the LDS / scalar-memory counter as well, and
-// the step's table lookups would then wait for the batch in flight
-typedef __attribute__((address_space(1))) unsigned long long chana_global_u64;
-__device__ __forceinline__ float2 chana_global_load(const float2* p)
-{
-    const unsigned long long v = *(const chana_global_u64*)p;
-    return make_float2(__int_as_float((int)(unsigned)v), __int_as_float((int)(unsigned)(v >> 32)));
-}
-__device__ __forceinline__ void chana_global_store(float2* p, float2 v)
-{
-    *(chana_global_u64*)p = (unsigned long long)(unsigned)__float_as_int(v.x) | ((unsigned long long)(unsigned)__float_as_int(v.y) << 32);
-}
 
 // ---- the serial walk, one wave per channel.  The chain never waits for memory: the wave loads 64 groups ahead, one per lane,
 // while it steps through the 64 it holds; every lane takes step j's input from lane j's register and runs the same step (the
@@ -47,21 +30,21 @@ void chana_walk_kernel(ChanaChan* __restrict__ ch, const ChanaBufs* __restrict__
     const ChanaBufs b = bufs[c];
     const int n = s.n_out;
     PllState st = s.ps;
-    float2 next = lane < n ? chana_global_load(b.avg + lane) : make_float2(0.0f, 0.0f);
+    float2 next = lane < n ? walk_global_load(b.avg + lane) : make_float2(0.0f, 0.0f);
     for (int base = 0; base < n; base += 64) {
         const float2 cur = next;
-        if (base + 64 + lane < n) next = chana_global_load(b.avg + base + 64 + lane);
+        if (base + 64 + lane < n) next = walk_global_load(b.avg + base + 64 + lane);
         const float re = cur.x / 32768.0f, im = cur.y / 32768.0f;             // SDR_RX_SCALEF
         const int cnt = min(64, n - base);
         float2 mine = make_float2(0.0f, 0.0f);
         for (int j = 0; j < cnt; j++) {
-            const float r = chana_lane_value(re, j), i = chana_lane_value(im, j);
+            const float r = walk_lane_value(re, j), i = walk_lane_value(im, j);
             float yr, yi;
             if (k.mode == PLL_FREQ) pll_freq_step(k, st, r, i, &yr, &yi, (PllProbe*)nullptr);
             else pll_phase_step(k, st, r, i, &yr, &yi, (PllProbe*)nullptr);
             if (lane == j) mine = make_float2(yr, yi);
         }
-        if (base + lane < n) chana_global_store(b.osc + base + lane, mine);
+        if (base + lane < n) walk_global_store(b.osc + base + lane, mine);
     }
     if (lane == 0) s.ps = st;
 }
