@@ -9,7 +9,8 @@
 
     python examples/filesource_to_bfm.py [out_dir]          # writes a synthetic recording, replays it, saves the audio
 
-Everything numeric runs on the MI355X through the C ABI (include/sdrx.h); this script is host glue only.  RDS is not decoded."""
+Everything numeric runs on the MI355X through the C ABI (include/sdrx.h); this script is host glue only.  RDS is not decoded here: the bank
+can (sdrx_bfmrds_*, BfmBank(cfgs, rds=[...])), but it needs 250 kS/s or more per station and seconds of signal."""
 import os
 import sys
 import wave

@@ -646,8 +646,10 @@ int sdrx_wfm_last_launch(const sdrx_wfm_t* h, char* kernel_name, int name_cap,
  * restated bit for bit; atan2f is the fdlibm routine glibc had up to 2.40).  Any feed length is valid; NCO phase, pending
  * samples, ovlbuf, squelch counter, m_m1Sample, the pilot loop, both resampler windows and the distance, both de-emphasis
  * filters and the level accumulators carry across feeds.
- * NOT reproduced: RDS (m_rdsActive: the 57 kHz mixer, m_interpolatorRDS, RDSDemod / RDSDecoder / RDSParser), m_lowpass (created
- * but never run by feed).  A channel is configured at creation; there is no mid-stream retune.
+ * RDS (m_rdsActive) is per channel through sdrx_bfmrds_create, below: the 57 kHz mixer, m_interpolatorRDS, RDSDemod::process and
+ * RDSDecoder::frameSync run on the device; the interface ends at groups.
+ * NOT reproduced: RDSParser (strings, tables), m_lowpass (created but never run by feed).  A channel is configured at creation;
+ * there is no mid-stream retune.
  * ------------------------------------------------------------------------------------------ */
 typedef struct sdrx_bfm sdrx_bfm_t;
 typedef struct sdrx_bfm_cfg {
@@ -697,9 +699,67 @@ int sdrx_bfm_get_stream(sdrx_bfm_t* h, void** hip_stream);
 /* as sdrx_decim_set_timing: brackets each feed's kernels */
 int sdrx_bfm_set_timing(sdrx_bfm_t* h, int enabled);
 int sdrx_bfm_get_timing(sdrx_bfm_t* h, double* total_ms, int64_t* feeds, int reset);
-/* the kernel that bounds the last feed: bfm_walk_kernel with a stereo channel in the handle, else bfm_fft_kernel */
+/* the kernel that bounds the last feed: bfm_walk_kernel with a stereo channel in the handle (bfm_walk_rds_kernel when one of them
+ * has RDS on), else bfm_fft_kernel */
 int sdrx_bfm_last_launch(const sdrx_bfm_t* h, char* kernel_name, int name_cap,
                          int* grid, int* block, int* lds_bytes);
+
+/* RDS of the same bank: BFMDemod::feed with m_rdsActive set (bfmdemod.cpp:169-187).  Per filtered sample, in front of that
+ * sample's pilot step:
+ *     Complex r(demod * 2.0 * std::cos(3.0 * m_pilotPLLSamples[3]), 0.0);     [3] is m_phase as the PREVIOUS sample's step found
+ *                                                                             it: 0 at first, carried across feeds, never
+ *                                                                             written in a mono channel (r = demod * 2.0)
+ *     m_interpolatorRDS.decimate(...)        create(4, in_rate, 600.0): 4 phases of 18 taps, distance (Real) in_rate / 250000.0;
+ *                                            with in_rate < 250000 the remainder goes negative, every input yields an output at
+ *                                            phase 0 (doInterpolate's clamp): reproduced, not refused
+ *     m_rdsDemod.process(cr.real(), bit)     rdsdemod.cpp:73-197, m_srate fixed at 250000
+ *     m_rdsDecoder.frameSync(bit)            rdsdecoder.cpp:50-261; a completed group is four 16-bit blocks
+ * Bits, groups, reports and the whole carried state are bit-identical to the strict-IEEE scalar reference build, with one
+ * reservation that cannot be removed by restating: the mixer calls the host libm's double cos, which is not correctly rounded.
+ * The device uses a cosine of its own whose error is argued to stay below 1 ulp and measured at 0.82 ulp (sdrangel_amd/csrc/rds_mix.hpp); glibc documents 1 ulp for
+ * its own, so the two differ by one ulp at most.  For every sample the device also evaluates r at both ends of that enclosure and
+ * counts the sample in the channel's `unsure` counter when they give another float.  A stream whose counter stays 0 has, given
+ * those two bounds, mixed exactly as the reference on any libm that keeps the documented one.  The expected rate is about 2^-28 per
+ * sample: a stream of hours at 250 kS/s will count a few.  Each such sample MAY (not must) differ from a given host's r by one
+ * float ulp; everything downstream is then no longer known to be equal, though a one-ulp change of one input of an 18-tap FIR in
+ * front of a 2.4 kHz low-pass seldom changes a bit.  Mono channels have no cosine and never count.
+ * RDSDemod's numsamples is an int: fewer than 2^31 RDS samples (2 h 23 min at 250 kS/s) per handle between resets.
+ * These calls work on a sdrx_bfm_t and carry the prefix sdrx_bfmrds_: the set of sdrx_bfm_* entry points is pinned.
+ * rds == NULL or all zeros is sdrx_bfm_create: the same kernels are launched and the outputs are the same.  A handle may mix
+ * channels with RDS on and off, mono and stereo.  The calls below return SDRX_EINVAL for a channel without RDS. */
+typedef struct sdrx_bfmrds_cfg {
+    int32_t rds_active;     /* m_rdsActive: 0 / 1 */
+} sdrx_bfmrds_cfg;
+int sdrx_bfmrds_create(sdrx_bfm_t** out, int device, int32_t n_ch, const sdrx_bfm_cfg* cfg, const sdrx_bfmrds_cfg* rds);
+/* the bits RDSDemod::process returned during the last feed, one per byte; at most n_rds / 8 + 2 (<0: error) */
+int64_t sdrx_bfmrds_read_bits(sdrx_bfm_t* h, int32_t ch, uint8_t* bits, int64_t cap);
+int sdrx_bfmrds_bits_last_dev(sdrx_bfm_t* h, int32_t ch, const uint8_t** d_bits, int64_t* n);
+/* the groups RDSDecoder::frameSync completed during the last feed, four blocks each; at most bits / 26 + 1 (<0: error) */
+int64_t sdrx_bfmrds_read_groups(sdrx_bfm_t* h, int32_t ch, uint16_t* blocks4, int64_t cap_groups);
+int sdrx_bfmrds_groups_last_dev(sdrx_bfm_t* h, int32_t ch, const uint16_t** d_blocks4, int64_t* n_groups);
+/* m_parms.subcarr_bb[0] of every RDS sample of the last feed (the 2.4 kHz low-pass's output), for inspection */
+int64_t sdrx_bfmrds_read_bb(sdrx_bfm_t* h, int32_t ch, float* subcarr_bb, int64_t cap);
+/* RDSDemod::m_report (qua is NaN until an error was counted: 0.0 / 0 * 100), RDSDecoder::m_qua and synced() */
+int sdrx_bfmrds_report(sdrx_bfm_t* h, int32_t ch, float* acc, float* qua, float* fclk, float* decoder_qua, int32_t* synced);
+/* the carried state after the last feed; floats and doubles as their bits */
+typedef struct sdrx_bfmrds_state_s {
+    uint64_t subcarr_phi, clock_offset, clock_phi, prev_clock_phi, d_cphi;      /* m_parms' doubles */
+    uint32_t xv[3], yv[3];                                                      /* m_xv[0], m_yv[0] */
+    uint32_t prev_bb, acc, prev_acc, lo_clock, prev_lo_clock;
+    int32_t  numsamples, counter, reading_frame, tot_errs[2], dbit;
+    uint32_t distance_remain;                                                   /* m_interpolatorRDSDistanceRemain */
+    uint32_t mix_phase;                                                         /* m_pilotPLLSamples[3] */
+    int32_t  n_rds;                                                             /* RDS samples of the last feed */
+    uint64_t reg, lastseen_offset_counter, bit_counter;                         /* RDSDecoder's members */
+    uint32_t block_bit_counter, wrong_blocks_counter, blocks_counter, group_good_blocks_counter;
+    uint32_t group[4];
+    int32_t  sync, presync, lastseen_offset, block_number, group_assembly_started, good_block;
+    uint32_t decoder_qua;
+    int32_t  reserved;
+} sdrx_bfmrds_state_t;
+int sdrx_bfmrds_state(sdrx_bfm_t* h, int32_t ch, sdrx_bfmrds_state_t* out);
+/* samples since creation, reset or the last call with reset != 0 whose r the enclosure does not pin (see above); <0: error */
+int64_t sdrx_bfmrds_unsure(sdrx_bfm_t* h, int32_t ch, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * AM demodulator bank: AMDemod::feed and AMDemod::processOneSample (plugins/channelrx/demodam/amdemod.cpp:101-276) in

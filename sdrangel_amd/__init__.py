@@ -174,6 +174,15 @@ def lib() -> C.CDLL:
         "sdrx_bfm_squelch_open": (C.c_int, [vp, i32]),
         "sdrx_bfm_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_bfm_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float), vp, C.POINTER(i32), vp]),
+        "sdrx_bfmrds_create": (C.c_int, [pp, C.c_int, i32, vp, vp]),
+        "sdrx_bfmrds_read_bits": (i64, [vp, i32, vp, i64]),
+        "sdrx_bfmrds_bits_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_bfmrds_read_groups": (i64, [vp, i32, vp, i64]),
+        "sdrx_bfmrds_groups_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_bfmrds_read_bb": (i64, [vp, i32, vp, i64]),
+        "sdrx_bfmrds_report": (C.c_int, [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)]),
+        "sdrx_bfmrds_state": (C.c_int, [vp, i32, vp]),
+        "sdrx_bfmrds_unsure": (i64, [vp, i32, C.c_int]),
         "sdrx_am_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_am_destroy": (C.c_int, [vp]),
         "sdrx_am_reset": (C.c_int, [vp]),
@@ -911,6 +920,25 @@ class BfmCfg(C.Structure):
                 ("audio_stereo", C.c_int32), ("lsb_stereo", C.c_int32), ("show_pilot", C.c_int32)]
 
 
+class BfmRdsCfg(C.Structure):
+    """sdrx_bfmrds_cfg: m_rdsActive of one BFMDemod"""
+    _fields_ = [("rds_active", C.c_int32)]
+
+
+class BfmRdsState(C.Structure):
+    """sdrx_bfmrds_state_t: RDSDemod's and RDSDecoder's carried state, floats and doubles as their bits"""
+    _fields_ = [("subcarr_phi", C.c_uint64), ("clock_offset", C.c_uint64), ("clock_phi", C.c_uint64), ("prev_clock_phi", C.c_uint64),
+                ("d_cphi", C.c_uint64), ("xv", C.c_uint32 * 3), ("yv", C.c_uint32 * 3), ("prev_bb", C.c_uint32), ("acc", C.c_uint32),
+                ("prev_acc", C.c_uint32), ("lo_clock", C.c_uint32), ("prev_lo_clock", C.c_uint32), ("numsamples", C.c_int32),
+                ("counter", C.c_int32), ("reading_frame", C.c_int32), ("tot_errs", C.c_int32 * 2), ("dbit", C.c_int32),
+                ("distance_remain", C.c_uint32), ("mix_phase", C.c_uint32), ("n_rds", C.c_int32), ("reg", C.c_uint64),
+                ("lastseen_offset_counter", C.c_uint64), ("bit_counter", C.c_uint64), ("block_bit_counter", C.c_uint32),
+                ("wrong_blocks_counter", C.c_uint32), ("blocks_counter", C.c_uint32), ("group_good_blocks_counter", C.c_uint32),
+                ("group", C.c_uint32 * 4), ("sync", C.c_int32), ("presync", C.c_int32), ("lastseen_offset", C.c_int32),
+                ("block_number", C.c_int32), ("group_assembly_started", C.c_int32), ("good_block", C.c_int32),
+                ("decoder_qua", C.c_uint32), ("reserved", C.c_int32)]
+
+
 class AmCfg(C.Structure):
     """sdrx_am_cfg: one AMDemod in envelope mode (in_rate, nco_freq = -frequencyOffset, audio_rate, AMDemodSettings)"""
     _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
@@ -1036,6 +1064,69 @@ class BfmBank(_DemodBank):
     """N broadcast-FM stereo demodulators (BFMDemod::feed without RDS): int16 I/Q at the channelizer's output rate in; qint16 l, r
     audio and the Samples of the sink stream out."""
     _prefix, _cfg = "bfm", BfmCfg
+
+    def __init__(self, cfgs, device: int = 0, rds=None):
+        """rds: per channel whether RDS is on (m_rdsActive); None is sdrx_bfm_create"""
+        if rds is None:
+            super().__init__(cfgs, device)
+            return
+        self.n_ch = len(cfgs)
+        if len(rds) != self.n_ch:
+            raise ValueError("one rds entry per channel")
+        arr = (self._cfg * self.n_ch)(*cfgs)
+        flags = (BfmRdsCfg * self.n_ch)(*[BfmRdsCfg(int(v)) for v in rds])
+        self._h = C.c_void_p()
+        _check(lib().sdrx_bfmrds_create(C.byref(self._h), device, self.n_ch, arr, flags), "sdrx_bfmrds_create")
+        self.cfgs = list(cfgs)
+
+    def _rds(self, name: str, *args):
+        """sdrx_bfmrds_<name>: the RDS calls carry a prefix of their own"""
+        fn = getattr(lib(), "sdrx_bfmrds_" + name)
+        rc = fn(self._h, *args)
+        if rc < 0:
+            raise SdrxError(f"sdrx_bfmrds_{name} rc={rc}: {lib().sdrx_last_error().decode()}")
+        return rc
+
+    def _rds_read(self, name: str, ch: int, dtype, width: int, cap: int) -> np.ndarray:
+        out = np.empty((max(cap, 1), width) if width > 1 else max(cap, 1), dtype)
+        return out[:self._rds(name, ch, out.ctypes.data, cap)].copy()
+
+    def rds_bits_last_dev(self, ch: int):
+        p, n = C.c_void_p(), C.c_int64()
+        self._rds("bits_last_dev", ch, C.byref(p), C.byref(n))
+        return p.value or 0, n.value
+
+    def rds_groups_last_dev(self, ch: int):
+        p, n = C.c_void_p(), C.c_int64()
+        self._rds("groups_last_dev", ch, C.byref(p), C.byref(n))
+        return p.value or 0, n.value
+
+    def rds_bits(self, ch: int) -> np.ndarray:
+        """the bits RDSDemod::process returned during the last feed"""
+        return self._rds_read("read_bits", ch, np.uint8, 1, self.rds_bits_last_dev(ch)[1])
+
+    def rds_groups(self, ch: int) -> np.ndarray:
+        """the groups RDSDecoder::frameSync completed during the last feed, [n, 4] blocks"""
+        return self._rds_read("read_groups", ch, np.uint16, 4, self.rds_groups_last_dev(ch)[1])
+
+    def rds_bb(self, ch: int) -> np.ndarray:
+        """m_parms.subcarr_bb[0] of every RDS sample of the last feed"""
+        return self._rds_read("read_bb", ch, np.float32, 1, self.rds_state(ch).n_rds)
+
+    def rds_report(self, ch: int):
+        """(m_report.acc, m_report.qua, m_report.fclk, RDSDecoder::m_qua, synced())"""
+        a, q, f, dq, sy = C.c_float(), C.c_float(), C.c_float(), C.c_float(), C.c_int32()
+        self._rds("report", ch, C.byref(a), C.byref(q), C.byref(f), C.byref(dq), C.byref(sy))
+        return a.value, q.value, f.value, dq.value, bool(sy.value)
+
+    def rds_state(self, ch: int) -> BfmRdsState:
+        st = BfmRdsState()
+        self._rds("state", ch, C.byref(st))
+        return st
+
+    def rds_unsure(self, ch: int, reset: bool = False) -> int:
+        """samples whose mixer product the cosine's enclosure does not pin (include/sdrx.h)"""
+        return self._rds("unsure", ch, int(reset))
 
     def read(self, ch: int, cap: int | None = None) -> np.ndarray:
         """the last feed's audio as an [n, 2] array of (l, r)"""

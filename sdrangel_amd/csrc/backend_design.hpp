@@ -50,14 +50,14 @@ struct InterpTables {
     std::vector<double> args;             // per channel: rate, cutoff, taps per phase
     std::vector<float> all;               // the tables back to back
     std::vector<int> off, ntaps;          // per channel: float offset into `all`, taps per phase
-    void add(double rate, double cutoff, double tpp)
+    void add(double rate, double cutoff, double tpp, int phase_steps = 16)   // one phase count per table set
     {
         size_t p = 0;
         while (p < off.size() && !(args[3 * p] == rate && args[3 * p + 1] == cutoff && args[3 * p + 2] == tpp)) p++;
         if (p < off.size()) { off.push_back(off[p]); ntaps.push_back(ntaps[p]); }
         else {
             std::vector<float> poly; int nt = 0;
-            design_interp(16, rate, cutoff, tpp, poly, &nt);
+            design_interp(phase_steps, rate, cutoff, tpp, poly, &nt);
             off.push_back((int)all.size()); ntaps.push_back(nt);
             all.insert(all.end(), poly.begin(), poly.end());
         }

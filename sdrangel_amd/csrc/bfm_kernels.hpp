@@ -18,6 +18,7 @@
 #include "fm_front.hpp"
 #include "wave_walk.hpp"
 #include "bfm_pll.hpp"
+#include "bfm_rds.hpp"
 
 namespace sdrx {
 
@@ -48,6 +49,35 @@ struct BfmBufs {                        // per channel device pointers (per feed
     float2* mix;                        // per audio sample: (ci.real(), sampleStereo)
     uint32_t* sink;                     // packed Samples of m_sampleBuffer
     short2* pairs;                      // l, r
+};
+
+// RDS (m_rdsActive): a second pair of tables next to BfmChan / BfmBufs, which a handle without RDS never allocates
+constexpr int RDS_PHASES = 4;           // m_interpolatorRDS.create(4, in_rate, 600.0)
+constexpr int RDS_XV_FRONT = 4;         // m_xv values kept in front of a feed's (three are read)
+
+struct BfmRdsChan {
+    // --- config
+    int active;                         // m_rdsActive
+    int ntaps, taps_off;                // taps per phase (18); float offset into the RDS taps table: [phase][ntaps]
+    float step;                         // m_interpolatorRDSDistance = (Real) in_rate / 250000.0
+    // --- state
+    float distance;                     // m_interpolatorRDSDistanceRemain
+    float mix_phase;                    // m_pilotPLLSamples[3]: m_phase at the entry of the last pilot step
+    RdsDemodState d;
+    RdsDecoderState k;
+    unsigned long long unsure;          // samples whose r the cosine's enclosure does not pin (rds_mix.hpp), since the last reset of it
+    // --- per feed
+    int n_rds, n_bits, n_groups, pad_;
+};
+
+struct BfmRdsBufs {                     // per channel device pointers (all null for a channel without RDS)
+    float* ph;                          // per filtered sample of a stereo channel: m_phase as its pilot step found it
+    float* rin;                         // [WFM_HIST carried | 512 * n_blocks] r.real(): the input of m_interpolatorRDS
+    uint2* sched;                       // per RDS sample: {index of the completing input, bits(distance)}
+    float* xv;                          // [RDS_XV_FRONT carried | n_rds] m_xv[0][2] of every RDS sample
+    float* bb;                          // m_parms.subcarr_bb[0] of every RDS sample
+    uint8_t* bits;                      // the bits RDSDemod::process returned
+    uint16_t* groups;                   // four blocks per group RDSDecoder::frameSync completed
 };
 
 __device__ __forceinline__ uint32_t bfm_sink_sample(float v)                // Sample(v * SDR_RX_SCALEF, 0.0)
@@ -228,6 +258,46 @@ void bfm_walk_kernel(BfmChan* __restrict__ ch, const BfmBufs* __restrict__ bufs,
     if (lane == 0) s.ps = st;
 }
 
+// The same walk for a handle with RDS on in a stereo channel: those channels also keep m_phase as every step finds it (what
+// processPhase stores into m_pilotPLLSamples[3], phaselock.h:179) for the 57 kHz mixer.  A kernel of its own, not a template
+// flag on the one above: with the body shared through an inlined function the compiler scheduled the RDS-off walk differently
+// and it ran 3.4 % slower, so the walk of a handle without RDS stays the source it was, line for line.
+__global__ __launch_bounds__(64 * BFM_WALK_WAVES)
+void bfm_walk_rds_kernel(BfmChan* __restrict__ ch, const BfmBufs* __restrict__ bufs, int n_ch,
+                         const BfmRdsChan* __restrict__ rds, const BfmRdsBufs* __restrict__ rbufs)
+{
+    const int c = __builtin_amdgcn_readfirstlane(blockIdx.x * BFM_WALK_WAVES + (int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    if (c >= n_ch) return;
+    BfmChan& s = ch[c];
+    if (!s.stereo) return;
+    const int n = s.w.n_dem;
+    if (n <= 0) return;
+    const BfmPllCfg k = s.pk;
+    BfmPllState st = s.ps;
+    const float* __restrict__ dem = bufs[c].w.dem + WFM_HIST;
+    float2* __restrict__ psc = bufs[c].psc;
+    unsigned int* __restrict__ ph = rds[c].active ? reinterpret_cast<unsigned int*>(rbufs[c].ph) : nullptr;
+    float next = lane < n ? walk_global_load(dem + lane) : 0.0f;
+    for (int base = 0; base < n; base += 64) {
+        const float cur = next;
+        if (base + 64 + lane < n) next = walk_global_load(dem + base + 64 + lane);
+        const int cnt = min(64, n - base);
+        float2 mine = make_float2(0.0f, 0.0f);
+        float entry = 0.0f;
+        for (int j = 0; j < cnt; j++) {
+            float sn, cs;
+            if (lane == j) entry = st.phase;
+            bfm_pll_step(k, st, walk_lane_value(cur, j), &sn, &cs, (BfmPllProbe*)nullptr);
+            if (lane == j) mine = make_float2(sn, cs);
+        }
+        if (base + lane < n) {
+            walk_global_store(psc + base + lane, mine);
+            if (ph) walk_global_store(ph + base + lane, (unsigned int)__float_as_int(entry));
+        }
+    }
+    if (lane == 0) s.ps = st;
+}
+
 // ---- 5. per filtered sample of a stereo channel: m_pilotPLLSamples[1], [2] -> the input of m_interpolatorStereo, and the sink
 // stream's Sample when m_showPilot is set
 __global__ __launch_bounds__(256)
@@ -316,6 +386,146 @@ void bfm_deemph_kernel(BfmChan* __restrict__ ch, const BfmBufs* __restrict__ buf
         }
     }
     if (lane == 0) { s.y1x = yx; s.y1y = yy; }
+}
+
+// ---- 7a. RDS, per channel with m_rdsActive (bfmdemod.cpp:169-187).  The schedule of m_interpolatorRDS: wfm_sched_walk_body's
+// recurrence on the RDS distance.  With in_rate < 250000 the distance goes negative and stays there; d - 1.0 then rounds, as the
+// reference's does (one float operation either way), every input emits, and the FIR clamps the negative phase to 0.
+__global__ void bfm_rds_sched_kernel(const BfmChan* __restrict__ ch, BfmRdsChan* __restrict__ rds, const BfmRdsBufs* __restrict__ rbufs, int n_ch)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_ch) return;
+    BfmRdsChan& r = rds[c];
+    if (!r.active) return;
+    const int n = ch[c].w.n_dem;
+    const float step = r.step;
+    uint2* __restrict__ p = rbufs[c].sched;
+    float d = r.distance;
+    int k = -1, cnt = 0;
+    for (;;) {
+        const float m = fmaxf(floorf(d), 1.0f);
+        const int kn = k + (int)m;
+        if (kn >= n) break;
+        k = kn; d -= m;
+        p[cnt++] = make_uint2((uint32_t)k, __float_as_uint(d));
+        d += step;
+    }
+    r.distance = d - (float)(n - 1 - k);
+    r.n_rds = cnt;
+}
+
+// the mixer, per filtered sample: stereo channels through rds_mix with the phase the PREVIOUS sample's pilot step found (the
+// carried one for a feed's first sample); mono channels never write m_pilotPLLSamples[3], cos(0.0) = 1 and r = demod * 2.0
+__global__ __launch_bounds__(256)
+void bfm_rds_mix_kernel(const BfmChan* __restrict__ ch, BfmRdsChan* __restrict__ rds, const BfmBufs* __restrict__ bufs,
+                        const BfmRdsBufs* __restrict__ rbufs)
+{
+    const int c = blockIdx.y;
+    BfmRdsChan& r = rds[c];
+    if (!r.active) return;
+    const BfmChan& s = ch[c];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= s.w.n_dem) return;
+    const BfmRdsBufs& rb = rbufs[c];
+    const float demod = bufs[c].w.dem[WFM_HIST + j];
+    float v;
+    if (s.stereo) {
+        const float phase = j ? rb.ph[j - 1] : r.mix_phase;
+        bool unsure;
+        v = rds_mix(demod, phase, &unsure);
+        if (unsure) atomicAdd(&r.unsure, 1ull);
+    } else {
+        v = demod + demod;
+    }
+    rb.rin[WFM_HIST + j] = v;
+}
+
+// m_interpolatorRDS's FIR on the real part (interpolator.h:183-194, real accumulator, taps in that order, mul and add
+// separate), one lane per RDS sample, and the sample's m_xv[0][2] = input / 4.491730007e+03
+__global__ __launch_bounds__(256)
+void bfm_rds_fir_kernel(const BfmRdsChan* __restrict__ rds, const BfmRdsBufs* __restrict__ rbufs, const float* __restrict__ taps)
+{
+    const int c = blockIdx.y;
+    const BfmRdsChan& r = rds[c];
+    if (!r.active) return;
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= r.n_rds) return;
+    const BfmRdsBufs& rb = rbufs[c];
+    const uint2 e = rb.sched[o];
+    int ph = (int)floorf(__uint_as_float(e.y) * (float)RDS_PHASES);
+    if (ph < 0) ph = 0;                                     // doInterpolate's clamp
+    const float* __restrict__ t = taps + r.taps_off + ph * r.ntaps;
+    rb.xv[RDS_XV_FRONT + o] = rds_xv(wfm_fir_acc(t, r.ntaps, rb.rin + WFM_HIST + (int)e.x));
+}
+
+// RDSDemod::process and RDSDecoder::frameSync, one wave per channel staged like the pilot walk: lane j holds the FIR half of
+// the filter for step j (three m_xv values, read with the carried front), every lane runs the same step, lane j keeps step j's
+// subcarr_bb.  Bits and groups leave from lane 0 as they come.  The state stays in registers for the feed.
+__global__ __launch_bounds__(64 * BFM_WALK_WAVES)
+void bfm_rds_walk_kernel(BfmRdsChan* __restrict__ rds, const BfmRdsBufs* __restrict__ rbufs, int n_ch)
+{
+    const int c = __builtin_amdgcn_readfirstlane(blockIdx.x * BFM_WALK_WAVES + (int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    if (c >= n_ch) return;
+    BfmRdsChan& r = rds[c];
+    if (!r.active) return;
+    const int n = r.n_rds;
+    int n_bits = 0, n_groups = 0;
+    if (n > 0) {
+        RdsDemodState d = r.d;
+        RdsDecoderState k = r.k;
+        const float* __restrict__ xv = rbufs[c].xv + RDS_XV_FRONT;
+        unsigned int* __restrict__ bb = reinterpret_cast<unsigned int*>(rbufs[c].bb);
+        uint8_t* __restrict__ bits = rbufs[c].bits;
+        uint16_t* __restrict__ groups = rbufs[c].groups;
+        for (int base = 0; base < n; base += 64) {
+            float fir = 0.0f;
+            if (base + lane < n) {
+                const float* x = xv + base + lane;
+                fir = rds_fir_part(walk_global_load(x - 2), walk_global_load(x - 1), walk_global_load(x));
+            }
+            const int cnt = min(64, n - base);
+            float mine = 0.0f;
+            for (int j = 0; j < cnt; j++) {
+                bool bit = false;
+                const bool got = rds_demod_step(d, walk_lane_value(fir, j), &bit, (RdsProbe*)nullptr);
+                if (lane == j) mine = d.yv[2];
+                if (got) {
+                    if (lane == 0) bits[n_bits] = bit ? 1 : 0;
+                    n_bits++;
+                    if (rds_frame_sync(k, bit, (RdsProbe*)nullptr)) {
+                        if (lane < 4) groups[4 * n_groups + lane] = (uint16_t)(lane == 0 ? k.group0 : lane == 1 ? k.group1 : lane == 2 ? k.group2 : k.group3);
+                        n_groups++;
+                    }
+                }
+            }
+            if (base + lane < n) walk_global_store(bb + base + lane, (unsigned int)__float_as_int(mine));
+        }
+        if (lane == 0) {
+            const float* last = xv + n - 3;
+            d.xv[0] = last[0]; d.xv[1] = last[1]; d.xv[2] = last[2];
+            r.d = d; r.k = k;
+        }
+    }
+    if (lane == 0) { r.n_bits = n_bits; r.n_groups = n_groups; }
+}
+
+// the RDS resampler's window, the m_xv front and the mixer's phase for the next feed (one workgroup per channel, after
+// everything else of RDS)
+__global__ __launch_bounds__(WFM_HIST)
+void bfm_rds_carry_kernel(const BfmChan* __restrict__ ch, BfmRdsChan* __restrict__ rds, const BfmRdsBufs* __restrict__ rbufs)
+{
+    const int c = blockIdx.x, tid = threadIdx.x;
+    BfmRdsChan& r = rds[c];
+    if (!r.active) return;
+    const BfmRdsBufs& rb = rbufs[c];
+    const int n_dem = ch[c].w.n_dem, n = r.n_rds;
+    const float keep = rb.rin[n_dem + tid];                 // the last WFM_HIST of [carried | new]
+    float kx = 0.0f;
+    if (tid < RDS_XV_FRONT) kx = rb.xv[n + tid];
+    __syncthreads();
+    rb.rin[tid] = keep;
+    if (tid < RDS_XV_FRONT) rb.xv[tid] = kx;
+    if (tid == 0 && n_dem > 0 && ch[c].stereo) r.mix_phase = rb.ph[n_dem - 1];
 }
 
 // ---- 8. carry: the front's (ovlbuf, mono resampler window, NCO phase, pending count), the stereo resampler's window,

@@ -26,6 +26,8 @@ struct BfmHost {
     int cur = 0;
     int64_t cap_in = 0;
     int pending = 0;              // host mirror of WfmChan::pending (a function of the feed lengths only)
+    DevBuf rds_arena;             // rds_work()'s layout for rds_cap samples; channels with RDS on only
+    int64_t rds_cap = 0;
 };
 
 // One channel's work arena for feeds of up to cap_in samples.  tail's slot 0 (ovlbuf) and the fronts of dem and st (the two
@@ -55,6 +57,22 @@ void work(Carver& k, int64_t cap_in, BfmBufs& u)
     u.pairs = k.take<short2>(n_s + 8);
 }
 
+// RDS's arena of one channel.  Provable per-feed bounds: one RDS sample per filtered sample at most (Interpolator::decimate
+// emits once per input or not at all); biphase runs at most once per eighth RDS sample, so bits <= n_rds / 8 + 2; a group
+// needs 26 bits at least, so groups <= bits / 26 + 1.
+void rds_work(Carver& k, int64_t cap_in, BfmRdsBufs& u)
+{
+    const size_t n_blk = (size_t)(cap_in + WFM_H) / WFM_H + 1;
+    const size_t n_s = n_blk * WFM_H, n_bits = n_s / 8 + 2, n_groups = n_bits / 26 + 1;
+    u.ph = k.take<float>(n_s);
+    u.rin = k.take_kept<float>(WFM_HIST + n_s + WFM_HIST, WFM_HIST);
+    u.sched = k.take<uint2>(n_s + 8);
+    u.xv = k.take_kept<float>(RDS_XV_FRONT + n_s + RDS_XV_FRONT, RDS_XV_FRONT);
+    u.bb = k.take<float>(n_s);
+    u.bits = k.take<uint8_t>(n_bits);
+    u.groups = k.take<uint16_t>(4 * n_groups);
+}
+
 } // namespace
 
 struct sdrx_bfm {
@@ -72,6 +90,14 @@ struct sdrx_bfm {
     InterpTables taps;
     std::vector<float> filters_all;
     bool any_dyadic = false, any_stereo = false;
+    // RDS (sdrx_bfmrds_create): nothing of it exists in a handle without a channel that has it on
+    bool any_rds = false, any_rds_stereo = false;
+    std::vector<BfmRdsChan> h_rds;          // configuration and the state of a fresh handle
+    BfmRdsChan* d_rds = nullptr;
+    BfmRdsBufs* d_rbufs = nullptr;
+    BfmRdsBufs* h_rbufs = nullptr;          // pinned, as h_bufs
+    float* d_rds_taps = nullptr;
+    InterpTables rds_taps;
 };
 
 static int bad(const char* field, const char* need)
@@ -108,7 +134,9 @@ static int upload_fresh_state(sdrx_bfm* b)
         for (int i = 0; i < 2; i++) SDRX_HIP(hipMemsetAsync(h.pend[i], 0, WFM_H * 4, b->core.stream));
         int rc = demod_clear_kept<BfmBufs>(h.arena, h.cap_in, b->core.stream, work); if (rc) return rc;
         h.pending = 0; h.cur = 0;
+        if (h.rds_arena.p) { rc = demod_clear_kept<BfmRdsBufs>(h.rds_arena, h.rds_cap, b->core.stream, rds_work); if (rc) return rc; }
     }
+    if (b->any_rds) SDRX_HIP(hipMemcpyAsync(b->d_rds, b->h_rds.data(), (size_t)b->n_ch * sizeof(BfmRdsChan), hipMemcpyHostToDevice, b->core.stream));
     SDRX_HIP(hipStreamSynchronize(b->core.stream));
     return SDRX_OK;
 }
@@ -121,7 +149,7 @@ int sdrx_bfm_destroy(sdrx_bfm_t* b)
     (void)hipSetDevice(b->core.device);
     if (b->core.stream) (void)hipStreamSynchronize(b->core.stream);
     for (auto& h : b->ch) {
-        h.arena.release(); h.stage_in.release();
+        h.arena.release(); h.stage_in.release(); h.rds_arena.release();
         for (int i = 0; i < 2; i++) if (h.pend[i]) (void)hipFree(h.pend[i]);
     }
     if (b->d_chan) (void)hipFree(b->d_chan);
@@ -134,16 +162,22 @@ int sdrx_bfm_destroy(sdrx_bfm_t* b)
     if (b->d_taps) (void)hipFree(b->d_taps);
     if (b->d_filters) (void)hipFree(b->d_filters);
     if (b->d_utbl) (void)hipFree(b->d_utbl);
+    if (b->d_rds) (void)hipFree(b->d_rds);
+    if (b->d_rbufs) (void)hipFree(b->d_rbufs);
+    if (b->h_rbufs) (void)hipHostFree(b->h_rbufs);
+    if (b->d_rds_taps) (void)hipFree(b->d_rds_taps);
     b->core.close();
     delete b;
     return SDRX_OK;
 }
 
-int sdrx_bfm_create(sdrx_bfm_t** out, int device, int32_t n_ch, const sdrx_bfm_cfg* cfg)
+static int create_common(sdrx_bfm_t** out, int device, int32_t n_ch, const sdrx_bfm_cfg* cfg, const sdrx_bfmrds_cfg* rds)
 {
     if (!out) { set_error("sdrx_bfm_create: null out"); return SDRX_EINVAL; }
     *out = nullptr;
     int rc = validate(n_ch, cfg); if (rc) return rc;
+    for (int c = 0; rds && c < n_ch; c++)
+        if (rds[c].rds_active != 0 && rds[c].rds_active != 1) return bad("rds_active", "0 or 1");
     sdrx_bfm* b = new (std::nothrow) sdrx_bfm;
     if (!b) return SDRX_ENOMEM;
     rc = b->core.open(device);
@@ -202,10 +236,42 @@ int sdrx_bfm_create(sdrx_bfm_t** out, int device, int32_t n_ch, const sdrx_bfm_c
     SDRX_HIP_ELSE(hipEventRecord(b->bufs_ev, b->core.stream), sdrx_bfm_destroy(b));
     SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->prod_ev, hipEventDisableTiming), sdrx_bfm_destroy(b));
     SDRX_HIP_ELSE(hipEventCreateWithFlags(&b->cons_ev, hipEventDisableTiming), sdrx_bfm_destroy(b));
+    for (int c = 0; rds && c < n_ch; c++) if (rds[c].rds_active) b->any_rds = true;
+    if (b->any_rds) {
+        b->h_rds.resize((size_t)n_ch);
+        for (int c = 0; c < n_ch; c++) {
+            BfmRdsChan& r = b->h_rds[(size_t)c];
+            std::memset(&r, 0, sizeof r);
+            // m_interpolatorRDS.create(4, in_rate, 600.0): one table per rate (channels without RDS share in the bookkeeping only)
+            b->rds_taps.add((double)cfg[c].in_rate, 600.0, 4.5, RDS_PHASES);
+            r.active = rds[c].rds_active;
+            r.ntaps = b->rds_taps.ntaps[(size_t)c]; r.taps_off = b->rds_taps.off[(size_t)c];
+            r.step = (float)((double)(float)cfg[c].in_rate / 250000.0);          // (Real) in_rate / 250000.0
+            r.distance = r.step;
+            rds_demod_fresh(&r.d); rds_decoder_fresh(&r.k);
+            if (r.ntaps > WFM_HIST) { set_error("sdrx_bfmrds_create: resampler window does not fit"); sdrx_bfm_destroy(b); return SDRX_EINVAL; }
+            if (r.active && cfg[c].audio_stereo) b->any_rds_stereo = true;
+        }
+        rc = design_upload(&b->d_rds_taps, b->rds_taps.all);
+        if (rc) { sdrx_bfm_destroy(b); return rc; }
+        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_rds), (size_t)n_ch * sizeof(BfmRdsChan)), sdrx_bfm_destroy(b));
+        SDRX_HIP_ELSE(hipMalloc(reinterpret_cast<void**>(&b->d_rbufs), (size_t)n_ch * sizeof(BfmRdsBufs)), sdrx_bfm_destroy(b));
+        SDRX_HIP_ELSE(hipHostMalloc(reinterpret_cast<void**>(&b->h_rbufs), (size_t)n_ch * sizeof(BfmRdsBufs), hipHostMallocDefault), sdrx_bfm_destroy(b));
+    }
     rc = upload_fresh_state(b);
     if (rc) { sdrx_bfm_destroy(b); return rc; }
     *out = b;
     return SDRX_OK;
+}
+
+int sdrx_bfm_create(sdrx_bfm_t** out, int device, int32_t n_ch, const sdrx_bfm_cfg* cfg)
+{
+    return create_common(out, device, n_ch, cfg, nullptr);
+}
+
+int sdrx_bfmrds_create(sdrx_bfm_t** out, int device, int32_t n_ch, const sdrx_bfm_cfg* cfg, const sdrx_bfmrds_cfg* rds)
+{
+    return create_common(out, device, n_ch, cfg, rds);
 }
 
 int sdrx_bfm_reset(sdrx_bfm_t* b)
@@ -230,8 +296,13 @@ static int feed_common(sdrx_bfm* b, const int16_t* const* d_iq, const int64_t* n
         // every audio sample after the first of a feed consumes >= floor(step) demodulated samples
         const int64_t per_out = std::max<int64_t>(1, (int64_t)std::floor(b->h_chan[(size_t)c].w.step));
         max_out = std::max(max_out, std::min<int64_t>(nb * WFM_H, nb * WFM_H / per_out + 4));
+        if (b->any_rds && b->h_rds[(size_t)c].active) {
+            rc = demod_grow_arena<BfmRdsBufs>(h.rds_arena, h.rds_cap, std::max<int64_t>(n_per_ch[c], 1), b->core.stream, rds_work); if (rc) return rc;
+        }
     }
     SDRX_HIP(hipEventSynchronize(b->bufs_ev));            // previous feed's copy has read the table
+    for (int c = 0; b->any_rds && c < b->n_ch; c++)
+        b->h_rbufs[c] = demod_place<BfmRdsBufs>(b->ch[(size_t)c].rds_arena.p, b->ch[(size_t)c].rds_cap, rds_work);
     for (int c = 0; c < b->n_ch; c++) {
         BfmHost& h = b->ch[(size_t)c];
         BfmBufs& u = b->h_bufs[c];
@@ -243,6 +314,7 @@ static int feed_common(sdrx_bfm* b, const int16_t* const* d_iq, const int64_t* n
         u.w.n_in = n_per_ch[c];
     }
     rc = b->core.timer.begin(b->core.stream); if (rc) return rc;
+    if (b->any_rds) SDRX_HIP(hipMemcpyAsync(b->d_rbufs, b->h_rbufs, (size_t)b->n_ch * sizeof(BfmRdsBufs), hipMemcpyHostToDevice, b->core.stream));
     rc = demod_upload_bufs(b->d_bufs, b->h_bufs, b->n_ch, b->bufs_ev, b->core.stream); if (rc) return rc;
     const unsigned nc = (unsigned)b->n_ch, gc = (nc + 63) / 64, nblk = (unsigned)max_blocks;
     const unsigned gw = (nc + BFM_WALK_WAVES - 1) / BFM_WALK_WAVES, go = (unsigned)((max_out + 255) / 256);
@@ -256,6 +328,10 @@ static int feed_common(sdrx_bfm* b, const int16_t* const* d_iq, const int64_t* n
     // lanes whose channel the closed form took exit at once (prep's off-grid guard can hand a channel back)
     hipLaunchKernelGGL(bfm_sched_walk_kernel, dim3(gc), dim3(64), 0, st, b->d_chan, b->d_bufs, b->n_ch);
     SDRX_HIP(hipGetLastError());
+    if (b->any_rds) {
+        hipLaunchKernelGGL(bfm_rds_sched_kernel, dim3(gc), dim3(64), 0, st, b->d_chan, b->d_rds, b->d_rbufs, b->n_ch);
+        SDRX_HIP(hipGetLastError());
+    }
     rc = demod_stream_after(st, producer, b->prod_ev); if (rc) return rc;
     if (nblk) {
         hipLaunchKernelGGL(bfm_fft_kernel, dim3(nblk, nc), dim3(WFM_FFT / 8), 0, st, b->d_chan, b->d_bufs, b->d_filters, b->d_utbl, b->d_nco);
@@ -276,9 +352,10 @@ static int feed_common(sdrx_bfm* b, const int16_t* const* d_iq, const int64_t* n
         hipLaunchKernelGGL(bfm_discri_kernel, dim3(nblk, nc), dim3(256), 0, st, b->d_chan, b->d_bufs);
         SDRX_HIP(hipGetLastError());
         if (b->any_stereo) {
-            hipLaunchKernelGGL(bfm_walk_kernel, dim3(gw), dim3(64 * BFM_WALK_WAVES), 0, st, b->d_chan, b->d_bufs, b->n_ch);
+            if (b->any_rds_stereo) hipLaunchKernelGGL(bfm_walk_rds_kernel, dim3(gw), dim3(64 * BFM_WALK_WAVES), 0, st, b->d_chan, b->d_bufs, b->n_ch, b->d_rds, b->d_rbufs);
+            else hipLaunchKernelGGL(bfm_walk_kernel, dim3(gw), dim3(64 * BFM_WALK_WAVES), 0, st, b->d_chan, b->d_bufs, b->n_ch);
             SDRX_HIP(hipGetLastError());
-            b->core.note_launch("bfm_walk_kernel", (int)gw, 64 * BFM_WALK_WAVES, 0);
+            b->core.note_launch(b->any_rds_stereo ? "bfm_walk_rds_kernel" : "bfm_walk_kernel", (int)gw, 64 * BFM_WALK_WAVES, 0);
             hipLaunchKernelGGL(bfm_post_kernel, dim3(2 * nblk, nc), dim3(256), 0, st, b->d_chan, b->d_bufs);
             SDRX_HIP(hipGetLastError());
         } else {
@@ -287,6 +364,19 @@ static int feed_common(sdrx_bfm* b, const int16_t* const* d_iq, const int64_t* n
         hipLaunchKernelGGL(bfm_fir_kernel, dim3(go, nc), dim3(256), 0, st, b->d_chan, b->d_bufs, b->d_taps);
         SDRX_HIP(hipGetLastError());
         hipLaunchKernelGGL(bfm_deemph_kernel, dim3(gw), dim3(64 * BFM_WALK_WAVES), 0, st, b->d_chan, b->d_bufs, b->n_ch);
+        SDRX_HIP(hipGetLastError());
+    }
+    if (b->any_rds) {
+        // behind the pilot walk (the mixer's phases) and in front of the carry kernel (n_dem, the windows)
+        if (nblk) {
+            hipLaunchKernelGGL(bfm_rds_mix_kernel, dim3(2 * nblk, nc), dim3(256), 0, st, b->d_chan, b->d_rds, b->d_bufs, b->d_rbufs);
+            SDRX_HIP(hipGetLastError());
+            hipLaunchKernelGGL(bfm_rds_fir_kernel, dim3(2 * nblk, nc), dim3(256), 0, st, b->d_rds, b->d_rbufs, b->d_rds_taps);
+            SDRX_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(bfm_rds_walk_kernel, dim3(gw), dim3(64 * BFM_WALK_WAVES), 0, st, b->d_rds, b->d_rbufs, b->n_ch);
+        SDRX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(bfm_rds_carry_kernel, dim3(nc), dim3(WFM_HIST), 0, st, b->d_chan, b->d_rds, b->d_rbufs);
         SDRX_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(bfm_carry_kernel, dim3(nc), dim3(WFM_H), 0, st, b->d_chan, b->d_bufs);
@@ -422,6 +512,116 @@ int sdrx_bfm_get_design(sdrx_bfm_t* b, int32_t c, int32_t* ntaps_per_phase, floa
     if (lock_delay) *lock_delay = s.pk.lock_delay;
     if (rc2) { rc2[0] = s.rc_b0; rc2[1] = s.rc_a1; }
     return SDRX_OK;
+}
+
+// ---- RDS
+static int rds_fetch(sdrx_bfm* b, int32_t c, const char* who, BfmRdsChan* r)
+{
+    if (!b || c < 0 || c >= b->n_ch) { set_error(std::string(who) + ": bad argument"); return SDRX_EINVAL; }
+    if (!b->any_rds || !b->h_rds[(size_t)c].active) { set_error(std::string(who) + ": the channel was created without RDS"); return SDRX_EINVAL; }
+    return demod_fetch_state(b->core, b->d_rds, c, r);
+}
+
+static BfmRdsBufs rds_place(sdrx_bfm* b, int32_t c) { return demod_place<BfmRdsBufs>(b->ch[(size_t)c].rds_arena.p, b->ch[(size_t)c].rds_cap, rds_work); }
+
+int64_t sdrx_bfmrds_read_bits(sdrx_bfm_t* b, int32_t c, uint8_t* bits, int64_t cap)
+{
+    BfmRdsChan r;
+    if (cap < 0 || (cap > 0 && !bits)) { set_error("sdrx_bfmrds_read_bits: bad argument"); return SDRX_EINVAL; }
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_read_bits", &r); if (rc) return rc;
+    const int64_t n = std::min<int64_t>(r.n_bits, cap);
+    if (n == 0) return 0;
+    SDRX_HIP(hipMemcpy(bits, rds_place(b, c).bits, (size_t)n, hipMemcpyDeviceToHost));
+    return n;
+}
+
+int sdrx_bfmrds_bits_last_dev(sdrx_bfm_t* b, int32_t c, const uint8_t** d_bits, int64_t* n)
+{
+    BfmRdsChan r;
+    if (!d_bits || !n) { set_error("sdrx_bfmrds_bits_last_dev: bad argument"); return SDRX_EINVAL; }
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_bits_last_dev", &r); if (rc) return rc;
+    *d_bits = rds_place(b, c).bits; *n = r.n_bits;
+    return SDRX_OK;
+}
+
+int64_t sdrx_bfmrds_read_groups(sdrx_bfm_t* b, int32_t c, uint16_t* blocks4, int64_t cap_groups)
+{
+    BfmRdsChan r;
+    if (cap_groups < 0 || (cap_groups > 0 && !blocks4)) { set_error("sdrx_bfmrds_read_groups: bad argument"); return SDRX_EINVAL; }
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_read_groups", &r); if (rc) return rc;
+    const int64_t n = std::min<int64_t>(r.n_groups, cap_groups);
+    if (n == 0) return 0;
+    SDRX_HIP(hipMemcpy(blocks4, rds_place(b, c).groups, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return n;
+}
+
+int sdrx_bfmrds_groups_last_dev(sdrx_bfm_t* b, int32_t c, const uint16_t** d_blocks4, int64_t* n_groups)
+{
+    BfmRdsChan r;
+    if (!d_blocks4 || !n_groups) { set_error("sdrx_bfmrds_groups_last_dev: bad argument"); return SDRX_EINVAL; }
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_groups_last_dev", &r); if (rc) return rc;
+    *d_blocks4 = rds_place(b, c).groups; *n_groups = r.n_groups;
+    return SDRX_OK;
+}
+
+int64_t sdrx_bfmrds_read_bb(sdrx_bfm_t* b, int32_t c, float* subcarr_bb, int64_t cap)
+{
+    BfmRdsChan r;
+    if (cap < 0 || (cap > 0 && !subcarr_bb)) { set_error("sdrx_bfmrds_read_bb: bad argument"); return SDRX_EINVAL; }
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_read_bb", &r); if (rc) return rc;
+    const int64_t n = std::min<int64_t>(r.n_rds, cap);
+    if (n == 0) return 0;
+    SDRX_HIP(hipMemcpy(subcarr_bb, rds_place(b, c).bb, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return n;
+}
+
+int sdrx_bfmrds_report(sdrx_bfm_t* b, int32_t c, float* acc, float* qua, float* fclk, float* decoder_qua, int32_t* synced)
+{
+    BfmRdsChan r;
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_report", &r); if (rc) return rc;
+    if (acc) *acc = r.d.rep_acc;
+    if (qua) *qua = r.d.rep_qua;
+    if (fclk) *fclk = r.d.rep_fclk;
+    if (decoder_qua) *decoder_qua = r.k.qua;
+    if (synced) *synced = r.k.sync;
+    return SDRX_OK;
+}
+
+int sdrx_bfmrds_state(sdrx_bfm_t* b, int32_t c, sdrx_bfmrds_state_t* o)
+{
+    BfmRdsChan r;
+    if (!o) { set_error("sdrx_bfmrds_state: bad argument"); return SDRX_EINVAL; }
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_state", &r); if (rc) return rc;
+    auto fb = [](float v) { uint32_t i; std::memcpy(&i, &v, 4); return i; };
+    auto db = [](double v) { uint64_t i; std::memcpy(&i, &v, 8); return i; };
+    std::memset(o, 0, sizeof *o);
+    o->subcarr_phi = db(r.d.subcarr_phi); o->clock_offset = db(r.d.clock_offset); o->clock_phi = db(r.d.clock_phi);
+    o->prev_clock_phi = db(r.d.prev_clock_phi); o->d_cphi = db(r.d.d_cphi);
+    for (int i = 0; i < 3; i++) { o->xv[i] = fb(r.d.xv[i]); o->yv[i] = fb(r.d.yv[i]); }
+    o->prev_bb = fb(r.d.prev_bb); o->acc = fb(r.d.acc); o->prev_acc = fb(r.d.prev_acc);
+    o->lo_clock = fb(r.d.lo_clock); o->prev_lo_clock = fb(r.d.prev_lo_clock);
+    o->numsamples = r.d.numsamples; o->counter = r.d.counter; o->reading_frame = r.d.reading_frame;
+    o->tot_errs[0] = r.d.tot_errs0; o->tot_errs[1] = r.d.tot_errs1; o->dbit = r.d.dbit;
+    o->distance_remain = fb(r.distance); o->mix_phase = fb(r.mix_phase);
+    o->n_rds = r.n_rds;
+    o->reg = r.k.reg; o->lastseen_offset_counter = r.k.lastseenOffsetCounter; o->bit_counter = r.k.bitCounter;
+    o->block_bit_counter = r.k.blockBitCounter; o->wrong_blocks_counter = r.k.wrongBlocksCounter; o->blocks_counter = r.k.blocksCounter;
+    o->group_good_blocks_counter = r.k.groupGoodBlocksCounter;
+    o->group[0] = r.k.group0; o->group[1] = r.k.group1; o->group[2] = r.k.group2; o->group[3] = r.k.group3;
+    o->sync = r.k.sync; o->presync = r.k.presync; o->lastseen_offset = r.k.lastseenOffset; o->block_number = r.k.blockNumber;
+    o->group_assembly_started = r.k.groupAssemblyStarted; o->good_block = r.k.goodBlock; o->decoder_qua = fb(r.k.qua);
+    return SDRX_OK;
+}
+
+int64_t sdrx_bfmrds_unsure(sdrx_bfm_t* b, int32_t c, int reset)
+{
+    BfmRdsChan r;
+    int rc = rds_fetch(b, c, "sdrx_bfmrds_unsure", &r); if (rc) return rc;
+    if (reset) {
+        SDRX_HIP(hipMemsetAsync(reinterpret_cast<char*>(b->d_rds + c) + offsetof(BfmRdsChan, unsure), 0, sizeof(unsigned long long), b->core.stream));
+        SDRX_HIP(hipStreamSynchronize(b->core.stream));
+    }
+    return (int64_t)r.unsure;
 }
 
 int sdrx_bfm_sync(sdrx_bfm_t* b) { return b ? b->core.sync() : SDRX_EINVAL; }

@@ -16,6 +16,15 @@ What the figures are for:
 Also prints the single-thread time of the CPU restatement (tests/bfm_oracle.c) for one channel's second: a baseline, not a target.
 
     python tools/bfm_rate.py [--out profiles/bfm_rate.txt]
+
+--rds measures RDS instead (sdrx_bfmrds_*): the stereo handle with RDS off and with RDS on in every channel take turns on the same
+256 streams, which then carry a 57 kHz RDS subcarrier (tests/bfm_rds_cases.py), next to the mono handle.  The RF filter is 200 kHz
+wide so that the subcarrier passes.
+  rds share       RDS on minus RDS off: the mixer, the RDS resampler and its schedule, the RDS walk (bfm_rds_walk_kernel), the
+                  phases the pilot walk stores
+  per step        the RDS share over one channel's RDS samples (250 000 a second), next to the pilot walk's share over its steps
+
+    python tools/bfm_rate.py --rds [--in-rate 384000] [--out profiles/bfm_rds_rate.txt]
 """
 import argparse
 import json
@@ -40,8 +49,11 @@ def main():
     ap.add_argument("--feeds", type=int, default=8)
     ap.add_argument("--distinct", type=int, default=8, help="distinct streams synthesised; the channels cycle through them")
     ap.add_argument("--no-baseline", action="store_true", help="skip the ChannelAnalyzer walk and the CPU oracle")
+    ap.add_argument("--rds", action="store_true", help="RDS on against RDS off (see above)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.rds:
+        return rds_main(args)
     n_ch, feeds, in_rate = args.channels, max(args.feeds, 5), args.in_rate
     n = in_rate                                              # one second
     rf, af = 80000.0, 15000.0
@@ -112,6 +124,62 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             f.write("# tools/bfm_rate.py: %d channels x 1 s at %d S/s -> 48 kS/s, device resident, the handles taking turns, median of %d feeds "
+                    "after 2 warm-up rounds (HIP events around each feed's kernels)\n" % (n_ch, in_rate, feeds))
+            for key, v in res.items():
+                f.write(f"{key}: {v}\n")
+
+
+def rds_main(args):
+    from tests import bfm_rds_cases as rc
+    n_ch, feeds, in_rate = args.channels, max(args.feeds, 5), args.in_rate
+    n = in_rate
+    rf, af = 200000.0 if in_rate >= 250000 else 0.75 * in_rate, 15000.0
+    dev = []
+    for c in range(min(args.distinct, n_ch)):
+        x = rc.signal({"kind": "mpx", "rds": 4000.0, "rds_phi": 1.5707963267948966, "fs": 400.0 + 100.0 * c, "sum": 8000.0, "diff": 4000.0, "amp": 6000.0},
+                      n, in_rate, 900 + c)
+        dev.append(torch.from_numpy(x).cuda())
+    torch.cuda.synchronize()
+    k = len(dev)
+    ptrs, cnts = [dev[c % k].data_ptr() for c in range(n_ch)], [n] * n_ch
+
+    def bfm(stereo, rds):
+        cfgs = [sa.BfmCfg(in_rate=in_rate, nco_freq=0, audio_rate=48000, rf_bandwidth=rf, af_bandwidth=af, volume=2.0, squelch_db=-60.0,
+                          audio_stereo=stereo, lsb_stereo=0, show_pilot=0) for _ in range(n_ch)]
+        return sa.BfmBank(cfgs, rds=[1] * n_ch) if rds else sa.BfmBank(cfgs)
+    handles = {"stereo": bfm(1, 0), "stereo_rds": bfm(1, 1), "mono": bfm(0, 0)}
+    for _ in range(2):
+        for h in handles.values():
+            h.feed_dev(ptrs, cnts)
+    for h in handles.values():
+        h.sync(); h.set_timing(True)
+    times = {name: [] for name in handles}
+    n_rds = 0
+    for _ in range(feeds):
+        for name, h in handles.items():
+            h.feed_dev(ptrs, cnts)
+            ms, cnt = h.get_timing(reset=True)
+            assert cnt == 1
+            times[name].append(ms)
+        n_rds = handles["stereo_rds"].rds_state(0).n_rds
+    med = {name: statistics.median(t) for name, t in times.items()}
+    res = {"tool": "bfm_rate --rds", "channels": n_ch, "in_rate": in_rate, "samples_per_channel": n, "rds_samples_per_channel_and_feed": n_rds, "feeds": feeds}
+    for name, t in times.items():
+        res[f"{name}_ms_per_feed"] = round(med[name], 4)
+        res[f"{name}_ms_series"] = [round(v, 4) for v in t]
+    res["rds_share_ms"] = round(med["stereo_rds"] - med["stereo"], 4)
+    res["rds_us_per_dependent_step"] = round((med["stereo_rds"] - med["stereo"]) * 1e3 / max(n_rds, 1), 5)
+    res["walk_share_ms"] = round(med["stereo"] - med["mono"], 4)
+    res["walk_us_per_dependent_step"] = round((med["stereo"] - med["mono"]) * 1e3 / n, 5)
+    h = handles["stereo_rds"]
+    res["bits_in_the_last_feed"] = int(h.rds_bits(0).size)
+    res["groups_in_the_last_feed"] = int(h.rds_groups(0).shape[0])
+    res["channels_synced"] = sum(int(h.rds_report(c)[4]) for c in range(n_ch))
+    res["unsure_samples_all_channels"] = sum(h.rds_unsure(c) for c in range(n_ch))
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("# tools/bfm_rate.py --rds: %d channels x 1 s at %d S/s, device resident, RDS off / RDS on / mono taking turns, median of %d feeds "
                     "after 2 warm-up rounds (HIP events around each feed's kernels)\n" % (n_ch, in_rate, feeds))
             for key, v in res.items():
                 f.write(f"{key}: {v}\n")
