@@ -8,6 +8,8 @@
         ->  one WAV file per carrier (standard library `wave`)
 
     python examples/filesource_to_am.py [out_dir]          # writes a synthetic recording, replays it, saves the audio
+    python examples/filesource_to_am.py [out_dir] --sync dsb|usb|lsb     # the same with synchronous AM (m_pll): prefilter -> PLL ->
+                                                           # sideband filter -> AGC in place of the envelope; prints the PLL lock per carrier
 
 Everything numeric runs on the MI355X through the C ABI (include/sdrx.h); this script is host glue only."""
 import os
@@ -51,7 +53,10 @@ def demod_cfgs(bank):
     return cfgs
 
 
-def main(out_dir):
+SYNC_OPS = {"dsb": 0, "usb": 1, "lsb": 2}
+
+
+def main(out_dir, sync=None):
     os.makedirs(out_dir, exist_ok=True)
     rec = os.path.join(out_dir, "synthetic_am.sdriq")
     n = synth_recording(rec)
@@ -61,7 +66,9 @@ def main(out_dir):
 
     fifo = sa.SampleSinkFifo(FS // 4)
     bank = sa.ChannelizerBank(FS, [REQ_RATE] * len(CARRIERS), CARRIERS)
-    am = sa.AmDemodBank(demod_cfgs(bank))
+    # SSBFilter as an AMDemod constructed at this audio rate with the default bandwidth has it
+    options = None if sync is None else [sa.AmSyncCfg(pll=1, sync_op=SYNC_OPS[sync], ssb_design_rate=AUDIO_RATE, ssb_design_bw=RF_BW)] * len(CARRIERS)
+    am = sa.AmDemodBank(demod_cfgs(bank), sync=options)
 
     audio = [[] for _ in CARRIERS]
     spans = []
@@ -89,9 +96,17 @@ def main(out_dir):
         f_peak = np.argmax(spec) * AUDIO_RATE / (2 * (spec.size - 1))
         print(f"carrier {c}: {fc:+8d} Hz  {pcm.size} samples at {AUDIO_RATE} S/s, squelch {'open' if am.squelch_open(c) else 'closed'}, "
               f"dominant tone {f_peak:7.1f} Hz (sent {500 + 400 * c} Hz) -> {p}")
+        if sync is not None:
+            locked, freq = am.pll(c)
+            print(f"carrier {c}: sync {sync}, PLL {'locked' if locked else 'not locked'}, loop frequency {freq * AUDIO_RATE / (2 * np.pi):+8.2f} Hz")
     print(f"{n} input samples replayed from {rec}")
-    return {"recording": rec, "wav": paths, "spans": spans}
+    return {"recording": rec, "wav": paths, "spans": spans, "pll": None if sync is None else [am.pll(c) for c in range(len(CARRIERS))]}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "examples_out")
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out_dir", nargs="?", default="examples_out")
+    ap.add_argument("--sync", choices=sorted(SYNC_OPS), default=None, help="synchronous AM with that sideband operation")
+    a = ap.parse_args()
+    main(a.out_dir, a.sync)

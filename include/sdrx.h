@@ -762,8 +762,9 @@ int sdrx_bfmrds_state(sdrx_bfm_t* h, int32_t ch, sdrx_bfmrds_state_t* out);
 int64_t sdrx_bfmrds_unsure(sdrx_bfm_t* h, int32_t ch, int reset);
 
 /* ------------------------------------------------------------------------------------------
- * AM demodulator bank: AMDemod::feed and AMDemod::processOneSample (plugins/channelrx/demodam/amdemod.cpp:101-276) in
- * envelope mode (m_pll = false, the default), N channels per handle, each fed with int16 I/Q at the channelizer's output rate:
+ * AM demodulator bank: AMDemod::feed and AMDemod::processOneSample (plugins/channelrx/demodam/amdemod.cpp:101-276), N channels
+ * per handle, each fed with int16 I/Q at the channelizer's output rate.  In envelope mode (m_pll = false, the default;
+ * synchronous AM: sdrx_am_create_ex, below):
  *     c = Complex(re, im) * m_nco.nextIQ();  m_interpolator.decimate(&dist, c, &ci)        as sdrx_backend_* (filt_mode 0)
  *     per ci: magsq = re*re + im*im (re = ci.re / 32768.0f); m_movingAverage(magsq) (MovingAverageUtil<Real, double, 16>);
  *             level sums; m_squelchDelayLine.write(magsq); squelch counter against m_magsq, cap rate / 10, open at rate / 20
@@ -777,8 +778,8 @@ int64_t sdrx_bfmrds_unsure(sdrx_bfm_t* h, int32_t ch, int reset);
  *   - the delay line's contents start at 0.  DoubleBufferFIFO allocates with new T[] and does not clear, so a squelch that
  *     is above its level from the very first output opens at audio index rate / 20 - 1 and reads one slot that was never
  *     written; with 0 there the root is 0, the AGC is not fed and that sample is 0
- *   - left out: m_pll / sync-AM, the interpolating branch (audio_rate > in_rate: SDRX_EINVAL), AudioFifo, and mid-stream
- *     retune -- a channel is configured at creation
+ *   - left out: the interpolating branch (audio_rate > in_rate: SDRX_EINVAL), AudioFifo, and mid-stream retune or mode
+ *     change -- a channel is configured at creation
  * ------------------------------------------------------------------------------------------ */
 typedef struct sdrx_am sdrx_am_t;
 typedef struct sdrx_am_cfg {
@@ -823,6 +824,40 @@ int sdrx_am_get_timing(sdrx_am_t* h, double* total_ms, int64_t* feeds, int reset
 /* the output kernel of the last feed (Bandpass, attack, conversion): am_out_kernel, its grid, block and LDS bytes */
 int sdrx_am_last_launch(const sdrx_am_t* h, char* kernel_name, int name_cap,
                         int* grid, int* block, int* lds_bytes);
+
+/* Synchronous AM (m_pll, amdemod.cpp:191-238).  The levels, the squelch counter and m_squelchOpen are as above; an open, unmuted
+ * sample of a channel with pll != 0 then goes through
+ *     s = m_pllFilt.filter(complex(re, im))   Lowpass<std::complex<float>>, create(101, audio_rate, 200.0)
+ *     m_pll.feed(s.real(), s.imag())          PhaseLockComplex, computeCoefficients(0.05, 0.707, 1000), setSampleRate(audio_rate), order 1
+ *     cs = (re * getImag() - im * getReal(), re * getReal() + im * getImag())         the UNfiltered sample, turned
+ *     DSB: DSBFilter->runDSB(cs, &sb, false)  fftfilt((2.0f * rfBW) / audio_rate, 2048): blocks of 1024, DC bin zeroed
+ *     USB / LSB: SSBFilter->runSSB(cs, &sb, usb, false)   fftfilt(0.0f, ssb_design_bw / ssb_design_rate, 1024): blocks of 512
+ *     per output of a completed block: m_syncAMBuff[i] = z.real() + z.imag(), z = sb[i] * (float) m_syncAMAGC.feedAndGetValue(sb[i]),
+ *         MagAGC(12000, 0.1, 1e-2), threshold off, resize(audio_rate / 4, audio_rate / 8, 0.1); m_syncAMBuffIndex = 0
+ *     demod = m_syncAMBuff[m_syncAMBuffIndex++] * 4.0f;   then the optional Bandpass, the attack, the volume and the conversion
+ * as in envelope mode; m_volumeAGC is not fed.  The whole chain advances on open, unmuted samples only and stands still
+ * otherwise: the filter's ring, the loop, the block being filled, ovlbuf, the AGC history and the buffer index carry across
+ * closures and across feeds, which may end anywhere, inside a block included.  Audio is bit-identical to the strict-IEEE
+ * scalar reference build linked against a glibc whose sinf / cosf / atan2f are the ones pll_math.hpp and udpsrc_scan.hpp restate.
+ *   - SSBFilter is designed once, in AMDemod's constructor, from m_rfBandwidth and m_audioSampleRate of that moment, and never
+ *     again; only DSBFilter follows rf_bandwidth and audio_rate.  ssb_design_rate / ssb_design_bw carry those two values
+ *   - m_syncAMBuff is never initialised by the reference; here it starts at 0.0f, which is what the first B - 1 open samples
+ *     of a channel read (B the block length), as the never-written delay-line slots above
+ *   - sync == NULL, or pll == 0 in every channel, is sdrx_am_create: such a handle launches the envelope kernels and no others.
+ *     Channels of one handle may mix envelope and the three operations; an envelope channel of a mixed handle gives the audio
+ *     of sdrx_am_create bit for bit */
+typedef struct sdrx_am_sync_cfg {
+    int32_t pll;              /* m_pll */
+    int32_t sync_op;          /* m_syncAMOperation: 0 DSB, 1 USB, 2 LSB */
+    int32_t ssb_design_rate;  /* m_audioSampleRate when AMDemod was constructed; 0 = 48000 */
+    float   ssb_design_bw;    /* m_rfBandwidth then; 0 = 5000 (AMDemodSettings::resetToDefaults) */
+} sdrx_am_sync_cfg;
+int sdrx_am_create_ex(sdrx_am_t** out, int device, int32_t n_ch, const sdrx_am_cfg* cfg, const sdrx_am_sync_cfg* sync);
+/* getPllLocked() and getPllFrequency() after the last feed (an envelope channel: 0 and 0.0f) */
+int sdrx_am_pll(sdrx_am_t* h, int32_t ch, int32_t* locked, float* freq);
+/* design products of a sync channel, for inspection: the 51 folded m_pllFilt taps, the frequency-domain filter in use
+ * (filter_len complex bins as re, im pairs: 2048 for DSB, 1024 for USB / LSB; room for 2048) and m_pll's a1, a2, b0, b1, b2 */
+int sdrx_am_get_sync_design(sdrx_am_t* h, int32_t ch, float* pll_filt_taps, float* filter_iq, int32_t* filter_len, float* pll_coef5);
 
 /* ------------------------------------------------------------------------------------------
  * NFM demodulator bank: NFMDemod::feed (plugins/channelrx/demodnfm/nfmdemod.cpp:140-332), N channels per handle, each fed with

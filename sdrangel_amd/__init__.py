@@ -194,6 +194,9 @@ def lib() -> C.CDLL:
         "sdrx_am_squelch_open": (C.c_int, [vp, i32]),
         "sdrx_am_levels": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
         "sdrx_am_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, C.POINTER(i32), C.POINTER(C.c_float)]),
+        "sdrx_am_create_ex": (C.c_int, [pp, C.c_int, i32, vp, vp]),
+        "sdrx_am_pll": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(C.c_float)]),
+        "sdrx_am_get_sync_design": (C.c_int, [vp, i32, vp, vp, C.POINTER(i32), vp]),
         "sdrx_nfm_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_nfm_create_ex": (C.c_int, [pp, C.c_int, i32, vp, vp]),
         "sdrx_nfm_ctcss": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(i64)]),
@@ -946,6 +949,12 @@ class AmCfg(C.Structure):
                 ("audio_mute", C.c_int32), ("bandpass_enable", C.c_int32)]
 
 
+class AmSyncCfg(C.Structure):
+    """sdrx_am_sync_cfg: the synchronous-AM options of one AMDemod (pll = m_pll; sync_op 0 DSB, 1 USB, 2 LSB; ssb_design_rate and
+    ssb_design_bw: the audio rate and RF bandwidth SSBFilter was designed from, 0 = 48000 and 5000)"""
+    _fields_ = [("pll", C.c_int32), ("sync_op", C.c_int32), ("ssb_design_rate", C.c_int32), ("ssb_design_bw", C.c_float)]
+
+
 class NfmCfg(C.Structure):
     """sdrx_nfm_cfg: one NFMDemod, power squelch (in_rate, nco_freq = -frequencyOffset, audio_rate, NFMDemodSettings)"""
     _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
@@ -1179,8 +1188,32 @@ class BfmBank(_DemodBank):
 
 
 class AmDemodBank(_DemodBank):
-    """N AM demodulators (AMDemod::feed, envelope mode): int16 I/Q at the channelizer's output rate in, mono qint16 audio out."""
+    """N AM demodulators (AMDemod::feed): int16 I/Q at the channelizer's output rate in, mono qint16 audio out.  `sync`: one
+    AmSyncCfg per channel (synchronous AM where its pll is set), None for envelope mode everywhere."""
     _prefix, _cfg = "am", AmCfg
+
+    def __init__(self, cfgs, device: int = 0, sync=None):
+        if sync is None:
+            super().__init__(cfgs, device)
+            return
+        if len(sync) != len(cfgs):
+            raise ValueError("one AmSyncCfg per channel")
+        self.n_ch = len(cfgs)
+        self._open(device, self.n_ch, (AmCfg * self.n_ch)(*cfgs), (AmSyncCfg * self.n_ch)(*sync), create="create_ex")
+        self.cfgs = list(cfgs)
+
+    def pll(self, ch: int):
+        """(getPllLocked(), getPllFrequency()) after the last feed"""
+        k, f = C.c_int32(), C.c_float()
+        self._call("pll", ch, C.byref(k), C.byref(f))
+        return bool(k.value), f.value
+
+    def sync_design(self, ch: int):
+        """(the 51 folded m_pllFilt taps, the frequency-domain filter as re, im pairs, m_pll's a1, a2, b0, b1, b2)"""
+        taps, filt, coef = np.zeros(51, np.float32), np.zeros(2 * 2048, np.float32), np.zeros(5, np.float32)
+        n = C.c_int32()
+        self._call("get_sync_design", ch, taps.ctypes.data, filt.ctypes.data, C.byref(n), coef.ctypes.data)
+        return taps, filt[: 2 * n.value].copy(), coef
 
     def levels(self, ch: int, reset: bool = False):
         """(m_magsq, m_magsqSum, m_magsqPeak, m_magsqCount); reset: as getMagSqLevels"""

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "am_scan.hpp"
+#include "am_sync_scan.hpp"
 #include "demod_psum.hpp"
 #include "demod_wg.hpp"
 #include "dsp_device.hpp"
@@ -37,6 +38,18 @@ struct AmChan {                         // device resident: config + carried sta
     // --- per feed
     int n, n_act, n_fed;                // audio samples; open and unmuted ones; AGC feeds
     double total_next, agc_sum_next;    // written by am_psum_kernel, committed by am_carry_kernel
+    // --- synchronous AM (am_sync_kernels.hpp), behind everything the envelope kernels read
+    int sync;                           // AMS_OFF: envelope; AMS_DSB / AMS_USB / AMS_LSB: m_pll with that m_syncAMOperation
+    int s_B, s_hn;                      // filter block (flen / 2); m_syncAMAGC's history, rate / 4
+    int pf_off;                         // float offset of the 51 folded m_pllFilt taps in the tap table
+    int filt_off;                       // float2 offset of the channel's frequency-domain filter
+    PllCfg pk;                          // m_pll's configuration
+    PllState ps;                        // ... and state
+    int s_pend;                         // open samples in the filter's open block (fftfilt::inptr)
+    long long s_open;                   // open samples since creation
+    double s_total;                     // m_syncAMAGC's MovingAverage::m_sum
+    int s_nb;                           // per feed: blocks the filter completed
+    double s_total_next;                // written by am_sync_psum_kernel, committed by am_sync_carry_kernel
 };
 
 struct AmBufs {                         // per channel device pointers (per feed capacity ensured by the host)
@@ -53,6 +66,16 @@ struct AmBufs {                         // per channel device pointers (per feed
     float* dem;                         // per open sample: (r - g) / g
     int16_t* audio;
     double* blk_sum; float* blk_peak;   // per 256 samples
+    // --- synchronous AM: carried (null in an envelope channel) ...
+    const float2* xhist; float2* xhist_next;     // last 100 open (re, im): m_pllFilt's ring
+    const float2* pend; float2* pend_next;       // the open block's inputs so far
+    const float2* ovl; float2* ovl_next;         // fftfilt::ovlbuf
+    const float* phist; float* phist_next;       // last s_hn magsq of the filter's outputs
+    const float* zhist; float* zhist_next;       // last s_B zsum: what m_syncAMBuff still holds
+    // ... and per feed
+    float2* xc; float2* pf; float2* osc;         // per open sample: (re, im), m_pllFilt's output, (m_yRe, m_yIm) after feed()
+    float2* head; float2* tail;                  // per filter output: the two halves of its block's inverse transform
+    float* pw; double* sterm; double* stot;      // per filter output: magsq, moving-average term and sum
 };
 
 // ---- 1. per sample: magsq, its root, the moving-average term; per 256 samples the level partials

@@ -11,6 +11,14 @@ under the same wall-clock bracket around a synchronised feed (device idle before
 
     python tools/am_rate.py [--out profiles/r06_am_rate.txt]            one JSON line + a text report
     rocprofv3 --kernel-trace --stats -- python tools/am_rate.py --feeds 10 --no-baseline     per-kernel times (a run of its own)
+
+--sync: synchronous AM (sdrx_am_create_ex).  256 channels x 1 s at 48 kS/s in and out (a carrier 20 Hz off centre with a tone in
+either sideband), the squelch open from the first 2400 samples on: an envelope handle, a sync-DSB handle and a sync-USB handle on the
+same streams, taking turns, HIP events around each feed's kernels.  The sync chain's only serial part is the loop walk, one wave per
+channel: (sync - envelope) / open samples bounds the time of one dependent step from above (the parallel kernels of the chain are in
+it).  Next to it, in the same run, the ChannelAnalyzer bank's walk measured the same way (pll on minus pll off, tools/chana_rate.py).
+
+    python tools/am_rate.py --sync [--out profiles/am_sync_rate.txt]
 """
 import argparse
 import ctypes as C
@@ -29,6 +37,71 @@ import sdrangel_amd as sa  # noqa: E402
 from tests import am_cases as ac  # noqa: E402
 
 
+def sync_report(args):
+    from tests import am_sync_cases as sc
+    from tests import chana_pll_cases as pc
+    from tests import synth
+    n_ch, feeds, rate = args.channels, max(args.feeds, 10), 48000
+    n = rate
+    dev = []
+    for c in range(n_ch):
+        sig = {"kind": "am2", "f0": 20.0 + (c % 13), "fu": 400.0 + 5.0 * c, "fl": 650.0 + 3.0 * c, "amp": 5000.0, "noise": 10.0}
+        dev.append(torch.from_numpy(sc.signal(sig, n, rate, 900 + c)).cuda())
+    torch.cuda.synchronize()
+    ptrs, cnts = [t.data_ptr() for t in dev], [n] * n_ch
+    cfgs = [sa.AmCfg(in_rate=rate, nco_freq=0, audio_rate=rate, rf_bandwidth=5000.0, volume=0.25, squelch_db=-40.0, audio_mute=0, bandpass_enable=c % 2)
+            for c in range(n_ch)]
+    banks = {"envelope": sa.AmDemodBank(cfgs),
+             "sync_dsb": sa.AmDemodBank(cfgs, sync=[sa.AmSyncCfg(pll=1, sync_op=0)] * n_ch),
+             "sync_usb": sa.AmDemodBank(cfgs, sync=[sa.AmSyncCfg(pll=1, sync_op=1)] * n_ch)}
+    # the ChannelAnalyzer walk, as tools/chana_rate.py --pll measures it
+    cdev = [torch.from_numpy(synth.mix(n, 900 + c, 30, 8000, 1)).cuda() for c in range(n_ch)]
+    torch.cuda.synchronize()
+    cptrs = [t.data_ptr() for t in cdev]
+
+    def chana(**kw):
+        return sa.ChannelAnalyzerBank([sa.ChanaCfg(**{k: v for k, v in pc._cfg(rate, nco_freq=-2950 - (c % 97), **kw).items() if k != "psk_order"})
+                                       for c in range(n_ch)], psk_order=[1] * n_ch)
+
+    banks.update({"chana_pll_off": chana(), "chana_pll_on": chana(pll=1)})
+    feed = lambda k, b: b.feed_dev(cptrs if k.startswith("chana") else ptrs, cnts)
+    for _ in range(3):
+        for k, b in banks.items():
+            feed(k, b)
+    times = {k: [] for k in banks}
+    for b in banks.values():
+        b.sync()
+        b.set_timing(True)
+    for _ in range(feeds):
+        for k, b in banks.items():                           # taking turns
+            feed(k, b)
+            ms, cnt = b.get_timing(reset=True)
+            assert cnt == 1
+            times[k].append(ms)
+    res = {"tool": "am_rate --sync", "channels": n_ch, "rate": rate, "samples_per_channel": n, "feeds": feeds}
+    for k, t in times.items():
+        res[f"{k}_ms_per_feed"] = round(statistics.median(t), 4)
+        res[f"{k}_ms_min"] = round(min(t), 4)
+        res[f"{k}_ms_max"] = round(max(t), 4)
+    steps = n - rate // 20                                   # open samples of a steady feed: all but the first rate / 20
+    res["open_samples_per_channel_and_feed"] = steps
+    res["locked_channels_after_the_last_feed"] = {k: sum(int(banks[k].pll(c)[0]) for c in range(n_ch)) for k in ("sync_dsb", "sync_usb")}
+    for k in ("sync_dsb", "sync_usb"):
+        extra = res[f"{k}_ms_per_feed"] - res["envelope_ms_per_feed"]
+        res[f"{k}_chain_ms"] = round(extra, 4)
+        res[f"{k}_us_per_dependent_step_upper_bound"] = round(extra * 1e3 / steps, 4)
+        res[f"{k}_realtime_channels_per_feed_second"] = round(n_ch * 1000.0 / res[f"{k}_ms_per_feed"], 1)
+    csteps = banks["chana_pll_on"].last_dev(0)[1]
+    res["chana_steps_per_channel_and_feed"] = csteps
+    res["chana_walk_us_per_dependent_step"] = round((res["chana_pll_on_ms_per_feed"] - res["chana_pll_off_ms_per_feed"]) * 1e3 / max(csteps, 1), 4)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("# tools/am_rate.py --sync: %d channels x 1 s at %d S/s, device resident, median of %d feeds after 3 warm-up feeds, handles taking turns\n" % (n_ch, rate, feeds))
+            for k, v in res.items():
+                f.write(f"{k}: {v}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", type=int, default=256)
@@ -36,7 +109,10 @@ def main():
     ap.add_argument("--feeds", type=int, default=12)
     ap.add_argument("--no-baseline", action="store_true", help="skip the composition yardstick (profiling runs)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--sync", action="store_true", help="synchronous AM next to envelope mode and the ChannelAnalyzer walk")
     args = ap.parse_args()
+    if args.sync:
+        return sync_report(args)
     n_ch, feeds, in_rate = args.channels, max(args.feeds, 10), args.in_rate
     n = in_rate                                              # one second
     rf, audio_rate = 5000.0, 48000
