@@ -1351,6 +1351,69 @@ int sdrx_udpsrc_get_timing(sdrx_udpsrc_t* h, double* total_ms, int64_t* feeds, i
 int sdrx_udpsrc_last_launch(const sdrx_udpsrc_t* h, char* kernel_name, int name_cap,
                             int* grid, int* block, int* lds_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * LoRa demodulator bank: N LoRaDemod instances (plugins/channelrx/demodlora/lorademod.cpp, lorabits.h) on one device, the
+ * 16-bit build.  Input: int16 I/Q at the channelizer's output rate.  Output per feed: the Samples LoRaDemod::feed puts into
+ * m_sampleBuffer for its spectrum sink, one per decimator output, and the lines dumpRaw() prints.  Per input sample
+ * c = (re / 32768, im / 32768) * m_nco.nextIQ(); m_interpolator.decimate(&dist, c, &ci) with create(16, in_rate, m_Bandwidth /
+ * 1.9) -- the cutoff is the DOUBLE quotient of the float bandwidth and 1.9 -- and dist starting at (Real) in_rate / m_Bandwidth.
+ * Per decimator output: the dechirp by m_chirp / m_angle, the two sliding FFTs (sfft of 128, bins 0 .. 126) over ci * a and
+ * ci * conj(a), every 64th output detect()'s fetch with synch() and dumpRaw(), then m_bin += m_result and one Sample.
+ * Samples, lines and state are bit for bit those of the strict-IEEE scalar build of the reference.
+ *   - four places where the reference reads memory it never wrote are defined here, and identically in the recorder the
+ *     fixtures come from (tests/golden/lora_rec.cpp):
+ *       mov (new float[512]), read during the first four fetches, starts as zeros;
+ *       mag[127] and rev[127], stack floats sfft::fetch does not write, are 0 (the magnitude of the bin that never moves);
+ *       dumpRaw's char text[256], which interleave6 reads up to five characters past the last symbol, starts as zeros;
+ *       m_count, an int, is kept in 64 bits and movpoint is (count >> 6) & 3: the reference's value while that is defined.
+ *   - left out: the 24-bit build, and a mid-stream retune or bandwidth change -- a channel is configured at creation, a new
+ *     configuration is a new handle.  bandwidth > in_rate (the interpolating branch) is SDRX_EINVAL.
+ *   - at most one line ends per 71 fetches (4544 Samples): that bounds the text of a feed.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_lora sdrx_lora_t;
+typedef struct sdrx_lora_cfg {
+    int32_t in_rate;              /* channelizer output rate (m_sampleRate) */
+    int32_t nco_freq;             /* m_nco.setFreq(nco_freq, in_rate): LoRaDemod passes -frequencyOffset */
+    int32_t bandwidth;            /* m_Bandwidth: LoRaDemodSettings::bandwidths = 7813, 15625, 20833, 31250, 62500; any value in 1 .. in_rate is accepted */
+} sdrx_lora_cfg;
+typedef struct sdrx_lora_state_t {
+    int32_t tune, time, result, bin;  /* m_tune, m_time, m_result, m_bin after the last feed */
+    int64_t count;                /* m_count in 64 bits: decimator outputs since creation or reset */
+    int64_t lines;                /* lines dumpRaw printed since creation or reset */
+} sdrx_lora_state_t;
+int sdrx_lora_create(sdrx_lora_t** out, int device, int32_t n_ch, const sdrx_lora_cfg* cfg);
+int sdrx_lora_destroy(sdrx_lora_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_lora_reset(sdrx_lora_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to LoRaDemod::feed) */
+int sdrx_lora_feed(sdrx_lora_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_lora_feed_dev(sdrx_lora_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_lora_feed_bank(sdrx_lora_t* h, sdrx_chan_bank_t* bank);
+/* the m_sampleBuffer of the last feed for channel ch, {re, im} per Sample; returns the number of Samples written (<0: error) */
+int64_t sdrx_lora_read(sdrx_lora_t* h, int32_t ch, int16_t* samples_iq, int64_t cap_samples);
+/* device-side view of the same (valid until the next feed) */
+int sdrx_lora_last_dev(sdrx_lora_t* h, int32_t ch, const int16_t** d_samples_iq, int64_t* n);
+/* the lines dumpRaw printed during the last feed, '\n' after each, no terminating 0; returns the byte count, < 0 on error or
+ * if cap is too small for them */
+int64_t sdrx_lora_read_text(sdrx_lora_t* h, int32_t ch, char* buf, int64_t cap);
+int sdrx_lora_state(sdrx_lora_t* h, int32_t ch, sdrx_lora_state_t* s);
+/* design products, for inspection (any pointer may be NULL): polyphase taps [16][ntaps], NCO increment, sfft's vrot[128] as
+ * (re, im) pairs and its k2, the dechirp table [256] as (re, im) pairs indexed by m_angle, the Sample table [128] as (re, im)
+ * pairs indexed by m_bin */
+int sdrx_lora_get_design(sdrx_lora_t* h, int32_t ch, int32_t* ntaps_per_phase, float* taps, int32_t taps_cap, int32_t* nco_inc,
+                         float* vrot_iq, float* k2, float* chirp_iq, int16_t* sample_iq);
+int sdrx_lora_sync(sdrx_lora_t* h);
+int sdrx_lora_set_stream(sdrx_lora_t* h, void* hip_stream);
+int sdrx_lora_get_stream(sdrx_lora_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_lora_set_timing(sdrx_lora_t* h, int enabled);
+int sdrx_lora_get_timing(sdrx_lora_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the walk of the last feed: lora_walk_kernel, its grid, block and LDS bytes */
+int sdrx_lora_last_launch(const sdrx_lora_t* h, char* kernel_name, int name_cap,
+                          int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,17 @@ def lib() -> C.CDLL:
         "sdrx_bfmrds_report": (C.c_int, [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)]),
         "sdrx_bfmrds_state": (C.c_int, [vp, i32, vp]),
         "sdrx_bfmrds_unsure": (i64, [vp, i32, C.c_int]),
+        "sdrx_lora_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_lora_destroy": (C.c_int, [vp]),
+        "sdrx_lora_reset": (C.c_int, [vp]),
+        "sdrx_lora_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_lora_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_lora_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_lora_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_lora_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_lora_read_text": (i64, [vp, i32, vp, i64]),
+        "sdrx_lora_state": (C.c_int, [vp, i32, vp]),
+        "sdrx_lora_get_design": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, C.POINTER(i32), vp, C.POINTER(C.c_float), vp, vp]),
         "sdrx_am_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_am_destroy": (C.c_int, [vp]),
         "sdrx_am_reset": (C.c_int, [vp]),
@@ -310,7 +321,7 @@ def lib() -> C.CDLL:
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
                 "wfm": five + ("get_stream",), "bfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
-                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "lora": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
         for name in names:
@@ -942,6 +953,16 @@ class BfmRdsState(C.Structure):
                 ("decoder_qua", C.c_uint32), ("reserved", C.c_int32)]
 
 
+class LoraCfg(C.Structure):
+    """sdrx_lora_cfg: one LoRaDemod (in_rate, nco_freq = -frequencyOffset, bandwidth = m_Bandwidth)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("bandwidth", C.c_int32)]
+
+
+class LoraState(C.Structure):
+    """sdrx_lora_state_t: m_tune, m_time, m_result, m_bin, the 64-bit m_count and the lines printed so far"""
+    _fields_ = [("tune", C.c_int32), ("time", C.c_int32), ("result", C.c_int32), ("bin", C.c_int32), ("count", C.c_int64), ("lines", C.c_int64)]
+
+
 class AmCfg(C.Structure):
     """sdrx_am_cfg: one AMDemod in envelope mode (in_rate, nco_freq = -frequencyOffset, audio_rate, AMDemodSettings)"""
     _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("audio_rate", C.c_int32),
@@ -1224,6 +1245,47 @@ class AmDemodBank(_DemodBank):
     def design(self, ch: int):
         """(taps per phase, taps [16 * ntaps], the 151 folded Bandpass taps, NCO increment, squelch level)"""
         return self._design(ch, np.zeros(151, np.float32))
+
+
+class LoraDemodBank(_DemodBank):
+    """N LoRa demodulators (LoRaDemod::feed): int16 I/Q at the channelizer's output rate in; the Samples of m_sampleBuffer and
+    the lines dumpRaw prints out."""
+    _prefix, _cfg = "lora", LoraCfg
+
+    def read(self, ch: int, cap: int | None = None) -> np.ndarray:
+        """the Samples of the last feed, as an [n, 2] array of (re, im)"""
+        if cap is None:
+            cap = self.last_dev(ch)[1]
+        out = np.empty((max(cap, 1), 2), np.int16)
+        n = self._fn("read")(self._h, ch, out.ctypes.data, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_lora_read rc={n}: {lib().sdrx_last_error().decode()}")
+        return out[:n].copy()
+
+    def read_text(self, ch: int, cap: int | None = None) -> str:
+        """the lines dumpRaw printed during the last feed, a newline after each; cap: the buffer's size (None: large enough)"""
+        if cap is None:
+            cap = 256 * (self.last_dev(ch)[1] // 4544 + 2)
+        buf = C.create_string_buffer(max(cap, 1))
+        n = self._fn("read_text")(self._h, ch, buf, cap)
+        if n < 0:
+            raise SdrxError(f"sdrx_lora_read_text rc={n}: {lib().sdrx_last_error().decode()}")
+        return buf.raw[:n].decode("latin-1")
+
+    def state(self, ch: int) -> LoraState:
+        st = LoraState()
+        self._call("state", ch, C.byref(st))
+        return st
+
+    def design(self, ch: int):
+        """(taps per phase, taps [16 * ntaps], NCO increment, vrot as 256 floats, k2, the dechirp table as 512 floats, the Sample
+        table as [128, 2] int16)"""
+        nt, inc, k2 = C.c_int32(), C.c_int32(), C.c_float()
+        taps, vrot, chirp = np.zeros(16 * 128, np.float32), np.zeros(256, np.float32), np.zeros(512, np.float32)
+        sample = np.zeros((128, 2), np.int16)
+        self._call("get_design", ch, C.byref(nt), taps.ctypes.data, taps.size, C.byref(inc), vrot.ctypes.data, C.byref(k2), chirp.ctypes.data,
+                   sample.ctypes.data)
+        return nt.value, taps[: 16 * nt.value].copy(), inc.value, vrot, k2.value, chirp, sample
 
 
 class NfmDemodBank(_DemodBank):

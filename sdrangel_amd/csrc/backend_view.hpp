@@ -10,6 +10,9 @@ struct BackendView {
     const int* n_out;       // their count, written on the device by the feed's last kernel
 };
 int backend_view(sdrx_backend_t* b, int32_t ch, BackendView* v);
+// sdrx_backend_create with the Interpolator's cutoff of channel c as the double cutoff[c] in place of cfg[c].interp_cutoff:
+// for a caller whose reference passes Interpolator::create a double that no float holds (LoRaDemod: m_Bandwidth / 1.9).
+int backend_create_cutoff(sdrx_backend_t** out, int device, int32_t n_ch, const sdrx_backend_cfg* cfg, const double* cutoff);
 // hip_stream == nullptr: back to the back-end's own stream.  Waits for the work queued so far.
 int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream);
 // A back-end that has not been fed yet: channel ch resamples with this distance step (UDPSrc divides by a float rate) and its

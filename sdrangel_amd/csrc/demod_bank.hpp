@@ -1,5 +1,5 @@
 // The host skeleton of a demodulator bank whose front is a channel back-end (sdrx_am.hip, sdrx_nfm.hip, sdrx_ssb.hip,
-// sdrx_udpsrc.hip): the handle's members, create / destroy / reset, capacity growth, the per-feed pointer table, the three
+// sdrx_udpsrc.hip, sdrx_lora.hip): the handle's members, create / destroy / reset, capacity growth, the per-feed pointer table, the three
 // feed entry points and the getters that only fetch one channel's state.  A family F supplies what is its own:
 //   Handle, Cfg, Chan, Bufs      the opaque C type (struct sdrx_x : DemodBank<F> {}), its configuration, the device-resident
 //                                channel state and the per-channel pointer table of its kernel header
@@ -14,7 +14,8 @@
 //   outputs_bound(k, n_in)       most outputs channel k's feed of n_in inputs can have: sizes the grids
 //   launch(b, nc, gx)            the kernel sequence with its note_launch; gx blocks of 256 cover the bound
 //   front_made(front, n, cfg)    runs on a fresh front before it is fed
-// DemodDefaults has work_extra, bp_taps, fresh and front_made for a family without them.  Both layouts run twice through
+//   cutoff(k, f)                 the Interpolator's cutoff as the double the reference passes to create()
+// DemodDefaults has work_extra, bp_taps, fresh, front_made and cutoff for a family without them.  Both layouts run twice through
 // demod_carve.hpp, counting and placing, so an arena's size and its pointers come from one description.  DESIGN.md 4.11.
 #pragma once
 #include "sdrx_common.hpp"
@@ -34,6 +35,8 @@ struct DemodDefaults {
     static constexpr int bp_taps = 0;
     template <class Chan, class Bufs> static void fresh(const Chan&, Bufs&) {}      // all zeros
     template <class Cfg> static int front_made(sdrx_backend_t*, int, const Cfg*) { return SDRX_OK; }
+    // what Interpolator::create gets as its cutoff: the float of the front's configuration, widened
+    template <class Cfg> static double cutoff(const Cfg&, const sdrx_backend_cfg& f) { return (double)f.interp_cutoff; }
 };
 
 // every output after the first two of a stream consumes >= floor(step) inputs
@@ -125,7 +128,9 @@ struct DemodBank {
 
     static int make_front(H* b)
     {
-        int rc = sdrx_backend_create(&b->front, b->core.device, b->n_ch, b->be_cfg.data()); if (rc) return rc;
+        std::vector<double> cut((size_t)b->n_ch);
+        for (int c = 0; c < b->n_ch; c++) cut[(size_t)c] = F::cutoff(b->cfg[(size_t)c], b->be_cfg[(size_t)c]);
+        int rc = backend_create_cutoff(&b->front, b->core.device, b->n_ch, b->be_cfg.data(), cut.data()); if (rc) return rc;
         rc = F::front_made(b->front, b->n_ch, b->cfg.data()); if (rc) return rc;
         return backend_set_stream(b->front, b->core.stream);
     }

@@ -108,7 +108,8 @@ int sdrx_backend_destroy(sdrx_backend_t* b)
     return SDRX_OK;
 }
 
-int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sdrx_backend_cfg* cfg)
+// sdrx_backend_create with, where `cutoff` is not null, cutoff[c] in place of (double) cfg[c].interp_cutoff (backend_create_cutoff)
+static int backend_create_impl(sdrx_backend_t** out, int device, int32_t n_ch, const sdrx_backend_cfg* cfg, const double* cutoff)
 {
     if (!out) { set_error("sdrx_backend_create: null out"); return SDRX_EINVAL; }
     *out = nullptr;
@@ -146,7 +147,7 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
         const sdrx_backend_cfg& k = cfg[c];
         ChanHost& h = b->ch[(size_t)c];
         h.cfg = k;
-        b->taps.add((double)k.in_rate, (double)k.interp_cutoff, (double)k.taps_per_phase);
+        b->taps.add((double)k.in_rate, cutoff ? cutoff[c] : (double)k.interp_cutoff, (double)k.taps_per_phase);
         const int flen = k.filt_mode >= 4 ? BE_FFT_MAX : BE_FFT;          // runDSB / runAsym: "double the FFT size used for SSB"
         // fftfilt::create_filter / create_dsb_filter / create_asym_filter.  which: 0 = filter, 1 = filterOpp (runAsym only:
         // low pass at f1 = the opposite band's width)
@@ -204,6 +205,11 @@ int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sd
     SDRX_HIP_ELSE(hipMemcpy(b->d_chan, b->h_chan.data(), (size_t)n_ch * sizeof(BeChan), hipMemcpyHostToDevice), sdrx_backend_destroy(b));
     *out = b;
     return SDRX_OK;
+}
+
+int sdrx_backend_create(sdrx_backend_t** out, int device, int32_t n_ch, const sdrx_backend_cfg* cfg)
+{
+    return backend_create_impl(out, device, n_ch, cfg, nullptr);
 }
 
 // producer != nullptr: the input samples are being written on that stream.  The schedule kernel (needs the counts only) is
@@ -372,6 +378,12 @@ int backend_view(sdrx_backend_t* b, int32_t c, BackendView* v)
     v->out = h.cfg.discri ? static_cast<const void*>(u.real_out) : static_cast<const void*>(u.cplx_out);
     v->n_out = reinterpret_cast<const int*>(reinterpret_cast<const char*>(b->d_chan + c) + offsetof(BeChan, n_out));
     return SDRX_OK;
+}
+
+int backend_create_cutoff(sdrx_backend_t** out, int device, int32_t n_ch, const sdrx_backend_cfg* cfg, const double* cutoff)
+{
+    if (n_ch > 0 && !cutoff) { set_error("backend_create_cutoff: bad argument"); return SDRX_EINVAL; }
+    return backend_create_impl(out, device, n_ch, cfg, cutoff);
 }
 
 int backend_set_stream(sdrx_backend_t* b, hipStream_t hip_stream)
