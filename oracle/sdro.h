@@ -67,6 +67,10 @@ typedef struct sdro_backend sdro_backend;
  * decimate with distance += in_rate/out_rate  (nfmdemod.cpp:150-160, 453-476). */
 sdro_backend* sdro_backend_new(float nco_freq, float in_rate, float out_rate,
                                int32_t phase_steps, float cutoff, float taps_per_phase);
+/* the same with the cutoff as a double, the distance starting at `distance` and stepping by `step` (LoRaDemod: cutoff
+ * (float) bandwidth / 1.9, distance = step = (float) in_rate / (float) bandwidth; lorademod.cpp:38-70, 266-283) */
+sdro_backend* sdro_backend_new_at(float nco_freq, double in_rate, int32_t phase_steps, double cutoff,
+                                  double taps_per_phase, float distance, float step);
 void    sdro_backend_free(sdro_backend*);
 int64_t sdro_backend_feed(sdro_backend*, const int16_t* iq, int64_t n_cplx, float* out_iq);
 int32_t sdro_backend_ntaps(const sdro_backend*);                         /* taps per phase */

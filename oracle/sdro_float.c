@@ -128,6 +128,20 @@ sdro_backend* sdro_backend_new(float nco_freq, float in_rate, float out_rate, in
     b->step = in_rate / out_rate;                               /* (Real) inRate / (Real) outRate */
     return b;
 }
+/* the same front with the cutoff kept as a double and the distance started where the caller says: LoRaDemod's constructor
+ * (lorademod.cpp:38-70) creates the Interpolator from m_Bandwidth / 1.9, a float divided by a double, and starts
+ * m_sampleDistanceRemain one step in */
+sdro_backend* sdro_backend_new_at(float nco_freq, double in_rate, int32_t phase_steps, double cutoff, double tpp, float distance, float step)
+{
+    nco_init();
+    sdro_backend* b = (sdro_backend*)calloc(1, sizeof *b);
+    b->nco_inc = sdro_nco_inc(nco_freq, (float)in_rate);
+    b->nco_phase = 0;
+    interp_create(&b->ip, phase_steps, in_rate, cutoff, tpp);
+    b->distance = distance;
+    b->step = step;
+    return b;
+}
 void sdro_backend_free(sdro_backend* b) { if (b) { interp_free(&b->ip); free(b); } }
 int32_t sdro_backend_ntaps(const sdro_backend* b) { return b->ip.ntaps; }
 const float* sdro_backend_taps(const sdro_backend* b) { return b->ip.taps; }

@@ -3,6 +3,10 @@ lorabits.h included from the reference tree; Qt headers of the build image for q
 tests/golden/lora_golden.npz for the cases of tests/lora_cases.py.
 
     python tests/golden/make_golden_lora.py [--ref /root/reference]
+    python tests/golden/make_golden_lora.py --random        writes tests/golden/lora_random_golden.npz instead: for the 100 random
+        cases and the named ones of tests/lora_cases.py the recorder's sha256 of the input and of all Samples, the text, the last
+        feed's state and the events -- what ties tests/lora_oracle.cpp to the reference where there is none.  The maker asserts
+        on the recorder's counters what the random cases have to reach (lora_cases.assert_coverage)
 
 Per case the fixture keeps the sha256 of the input (the generator is tests/lora_cases.py's, seeded), per feed the Sample count, the
 Samples, the text dumpRaw printed and the state (m_tune, m_time, m_result, m_bin, m_count, lines so far), the recorder's event
@@ -105,15 +109,44 @@ def float_cutoff_taps(in_rate: int, bw: int) -> bool:
     return not np.array_equal(design(exact), design(float(np.float32(exact))))
 
 
+def digest(lc, r: dict, x: np.ndarray) -> dict:
+    """what lora_random_golden.npz keeps of one recording"""
+    return {"in_sha256": lc.sha(x), "samples_sha256": lc.sha(np.concatenate(r["feeds"]).astype(np.int16)), "text": "".join(r["texts"]),
+            "state": r["state"][-1, :6].copy(), "events": r["state"][-1, 6:].copy()}
+
+
+def main_random(exe: str, out: str):
+    """the recorder's digests of the random cases and of the named ones (tests/lora_cases.py: random_cases(), NAMED), so that
+    tests/lora_oracle.cpp stays tied to the reference where there is none"""
+    from tests import lora_cases as lc
+    cases = lc.random_cases() + lc.NAMED
+    ds = []
+    for c in cases:
+        x = lc.inputs(c)
+        ds.append(digest(lc, record(exe, c, x), x))
+    n_random = len(cases) - len(lc.NAMED)
+    counters = [dict(zip(STATE + EVENTS, (int(v) for v in np.concatenate([d["state"], d["events"]])))) for d in ds]
+    lc.assert_coverage(cases[:n_random], counters[:n_random], [d["text"] for d in ds[:n_random]], probes=False)
+    text, text_bytes = pack_texts([d["text"] for d in ds])
+    np.savez_compressed(out, names=np.array([c["name"] for c in cases]), in_sha256=np.array([d["in_sha256"] for d in ds]),
+                        samples_sha256=np.array([d["samples_sha256"] for d in ds]), text=text, text_bytes=text_bytes,
+                        state=np.array([d["state"] for d in ds], np.int64), events=np.array([d["events"] for d in ds], np.int64))
+    print(f"wrote {out}: {len(cases)} cases, {os.path.getsize(out)} bytes")
+
+
 def main():
     from tests import lora_cases as lc
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--out", default=os.path.join(HERE, "lora_golden.npz"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--random", action="store_true", help="write lora_random_golden.npz: the recorder's digests of the random and the named cases")
     args = ap.parse_args()
     if not available(args.ref):
         sys.exit("reference tree or Qt headers not found")
     exe = build_recorder(args.ref)
+    if args.random:
+        return main_random(exe, args.out or os.path.join(HERE, "lora_random_golden.npz"))
+    args.out = args.out or os.path.join(HERE, "lora_golden.npz")
     arrays, up, plain, short = {}, 0, 0, 0
     for c in lc.CASES:
         name, ex = c["name"], c["expect"]

@@ -7,7 +7,9 @@
 //       them as the device carries it, the text slots are a feed's own, sized by lora_lines_bound.  Every fetch must give the
 //       recorded values and the feeds' lines together the recorded text.  Prints "ok <fetches> <lines> <feeds>" or the first mismatch.
 //   lora_check angle
-//       lora_angle against the running sums of m_chirp / m_angle over three periods; prints "ok <steps>"
+//       lora_angle against the running sums of m_chirp / m_angle over three periods; then lora_angle, lora_is_fetch and
+//       lora_movpoint over 1024 consecutive counts around each of 2^31, 2^32, 2^33 and 2^40 against their values at the count
+//       mod 512 and mod 256; prints "ok <steps> <large counts checked>"
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +47,16 @@ static int angle()
         // the period is 512 however far the stream has come
         if (lora_angle(g + (1ll << 40)) != ang) { std::printf("angle mismatch at %lld + 2^40\n", g); return 1; }
     }
-    std::printf("ok %lld\n", steps);
+    // the closed forms at large stream counts: 1024 consecutive counts around 2^31, 2^32, 2^33 and 2^40 against their values at
+    // g mod 512 (m_angle's period) and c mod 256 (a fetch every 64, movpoint's period of 4 fetches)
+    long long checked = 0;
+    for (int e : { 31, 32, 33, 40 })
+        for (long long v = (1ll << e) - 512; v < (1ll << e) + 512; v++, checked++) {
+            if (lora_angle(v) != lora_angle(v & 511)) { std::printf("angle mismatch at %lld against %lld\n", v, v & 511); return 1; }
+            if (lora_is_fetch(v) != lora_is_fetch(v & 255)) { std::printf("is_fetch mismatch at %lld\n", v); return 1; }
+            if (lora_movpoint(v) != lora_movpoint(v & 255)) { std::printf("movpoint mismatch at %lld\n", v); return 1; }
+        }
+    std::printf("ok %lld %lld\n", steps, checked);
     return 0;
 }
 

@@ -65,6 +65,8 @@ def test_the_trace_has_a_lock_a_dump_and_closed_fetches():
 def test_angle_closed_form(check):
     out = subprocess.run([check, "angle"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
+    # the running sums over three periods, and the three closed forms around 2^31, 2^32, 2^33 and 2^40
+    assert [int(v) for v in out.stdout.split()[1:3]] == [3 * 512 + 7, 4 * 1024], out.stdout
 
 
 def test_fetch_step_is_clean_under_the_host_sanitizers(trace):
