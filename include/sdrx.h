@@ -1414,6 +1414,112 @@ int sdrx_lora_get_timing(sdrx_lora_t* h, double* total_ms, int64_t* feeds, int r
 int sdrx_lora_last_launch(const sdrx_lora_t* h, char* kernel_name, int name_cap,
                           int* grid, int* block, int* lds_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * ATV demodulator bank: N ATVDemod instances (plugins/channelrx/demodatv/atvdemod.cpp, atvdemod.h) on one device, the 16-bit
+ * build.  Input: int16 I/Q at the channelizer's output rate.  Output per feed: the frames the screen was asked to render, the
+ * screen as it stands, the scope stream and the state.  Per input sample c = (re, im) unscaled, times m_nco.nextIQ() exactly
+ * when nco_freq is not 0 (the reference skips the mix at offset 0, and the oscillator at phase 0 is not (1, 0): its sine is a
+ * rounded cos(pi / 2)); demod(c): FM1 / FM2 on the normalised sample and the 2 / 6 before it, FM3 phaseDiscriminatorDelta(c) +
+ * 0.5, AM sqrt(magSq) / SDR_RX_SCALEF normalised by the extrema of the line before; inversion, clamp, the scope Sample, the grey
+ * level, then processClassic or processHSkip (standard 5).  The screen is what TVScreen is to the demodulator
+ * (sdrgui/gui/glshadertvarray.cpp:294-328): rows x cols bytes of grey and a current row.  Frames, events, screen, scope and
+ * state are bit for bit those of the strict-IEEE scalar build of the reference.
+ *   - pinned where the reference leaves it open or relies on x86, identically in tests/atv_oracle.cpp:
+ *       m_intAvgColIndex, which the constructor does not initialise, starts at 0;
+ *       the screen counts as initialised and starts as zeros; its current row is null until the first selectRow in range, so
+ *         pixels before that are dropped, and a selectRow out of range makes it null again;
+ *       a float that no int holds, NaN included, converts to INT_MIN: the grey level of a NaN is 0, and the scope Sample
+ *         converts through int32 and keeps the low 16 bits (1.0f gives -32768, NaN gives 0).  FM1 / FM2 reach NaN on a (0, 0) sample;
+ *       a NaN in the state (m_fltAmpLineAverage, m_fltBufferI / Q) is x86-64's default NaN 0xffc00000, the bits 0 / 0 gives there
+ *         and SSE arithmetic hands on unchanged.
+ *       m_DSBFilterBuffer makes the filtered stream lag by 1023 samples, with zeros first: demod reads slot index - 1 of a buffer
+ *         refilled every 1024th call.  FM3 takes the UNFILTERED sample even with the filter on.  Both are kept.  With the filter
+ *         on, FM1 / FM2 therefore see (0, 0) for the first 1023 samples and reach NaN there.
+ *   - the "decimator" (decimator_enable): its step tvRate / in_rate is <= 1 and its distance starts at 0 and never reaches 1, so
+ *     every input emits and the negative phase clamps to 0: a 72-tap FIR at the input rate, the phase-0 row of
+ *     create(24, tvRate, rf_bw / 2.2f, 3.0), summed in doInterpolate's order.
+ *   - left out: modulations USB and LSB (SimplePhaseLock and SecondOrderRecursiveFilter, the BFO), refused by create with
+ *     SDRX_EINVAL and a text; m_objMagSqAverage (GUI only); a mid-stream reconfiguration (a new configuration is a new handle);
+ *     EXTENDED_DIRECT_SAMPLE and the 24-bit build.  m_interpolatorDistanceRemain is not part of the state: no output depends on it.
+ *   - a vsync can be re-armed by one sample above the level and fired by the next one below it, so a feed can render every
+ *     second sample: the first frames_cap renders of a feed keep a snapshot, later ones are counted and listed only.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_atv sdrx_atv_t;
+typedef struct sdrx_atv_cfg {
+    int32_t in_rate;              /* channelizer output rate (m_intSampleRate) */
+    int32_t nco_freq;             /* m_nco.setFreq(nco_freq, in_rate): ATVDemod passes -frequencyOffset; 0: no mix */
+    int32_t modulation;           /* ATVModulation: 0 FM1, 1 FM2, 2 FM3, 3 AM; 4 USB and 5 LSB are refused */
+    float   rf_bw, rf_opp_bw;     /* m_fltRFBandwidth, m_fltRFOppBandwidth: read by the FFT filter and the decimator only */
+    int32_t fft_filtering;        /* m_blnFFTFiltering */
+    int32_t decimator_enable;     /* m_blndecimatorEnable */
+    float   fm_deviation;         /* m_fmDeviation */
+    float   line_duration;        /* m_fltLineDuration, seconds */
+    float   top_duration;         /* m_fltTopDuration, seconds */
+    float   frames_per_s;         /* m_fltFramePerS */
+    int32_t standard;             /* ATVStd: 0 PAL625, 1 PAL525, 2 405, 3 ShortInterleaved, 4 Short, 5 HSkip */
+    int32_t n_lines;              /* m_intNumberOfLines */
+    float   level_synchro_top;    /* m_fltVoltLevelSynchroTop */
+    float   level_black;          /* m_fltVoltLevelSynchroBlack, < 1 */
+    int32_t hsync, vsync, invert_video;
+    int32_t scope;                /* m_intVideoTabIndex == 1 with a scope sink present */
+    int32_t frames_cap;           /* >= 1: renders of one feed that keep a snapshot of the screen */
+} sdrx_atv_cfg;
+typedef struct sdrx_atv_state_t { /* the PROCESSING block of atvdemod.h after the last feed; floats as their bits */
+    int32_t image_index, synchro_points, synchro_detected, vertical_synchro_detected;
+    int32_t col_index, sample_index, row_index, line_index, avg_col_index;
+    int32_t screen_row;           /* the screen's current row, -1: null */
+    uint32_t amp_line_average, eff_min, eff_max, amp_min, amp_max, amp_delta;
+    uint32_t buffer_i[6], buffer_q[6];    /* m_fltBufferI, m_fltBufferQ */
+} sdrx_atv_state_t;
+typedef struct sdrx_atv_design_t { /* applySettings' and applyStandard's integers */
+    int32_t samples_per_line, samples_per_top, samples_per_line_signals, samples_per_hsync;
+    int32_t sync_lines, black_lines, eq_lines, interleaved;
+    int32_t tv_rate;              /* m_intTVSampleRate */
+    int32_t cols, rows;           /* resizeTVScreen's arguments */
+    int32_t nco_inc;
+} sdrx_atv_design_t;
+int sdrx_atv_create(sdrx_atv_t** out, int device, int32_t n_ch, const sdrx_atv_cfg* cfg);
+int sdrx_atv_destroy(sdrx_atv_t* h);
+/* the state of a fresh handle with the same configuration, the screens zeroed */
+int sdrx_atv_reset(sdrx_atv_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to ATVDemod::feed) */
+int sdrx_atv_feed(sdrx_atv_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_atv_feed_dev(sdrx_atv_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_atv_feed_bank(sdrx_atv_t* h, sdrx_chan_bank_t* bank);
+/* renderImage calls of the last feed into *n_events (may be NULL); returns how many of them kept a snapshot (<0: error) */
+int64_t sdrx_atv_frames(sdrx_atv_t* h, int32_t ch, int64_t* n_events);
+/* for each render of the last feed the index, within the feed, of the input sample at which it happened; returns the count written */
+int64_t sdrx_atv_read_events(sdrx_atv_t* h, int32_t ch, int32_t* index, int64_t cap);
+/* the screen (rows x cols bytes of grey, row after row) as it stood at render k of the last feed, k < sdrx_atv_frames();
+ * returns rows * cols (<0: error, cap too small included) */
+int64_t sdrx_atv_read_frame(sdrx_atv_t* h, int32_t ch, int64_t k, uint8_t* buf, int64_t cap);
+/* the screen after the last feed */
+int64_t sdrx_atv_read_screen(sdrx_atv_t* h, int32_t ch, uint8_t* buf, int64_t cap);
+/* device-side views (valid until the next feed): the stored frames, `pitch` bytes apart, and the screen.  d_frames is the snapshot
+ * arena of the last feed, NULL before the first feed, never the live screen: with n_stored 0 nothing in it is a frame */
+int sdrx_atv_frames_last_dev(sdrx_atv_t* h, int32_t ch, const uint8_t** d_frames, int64_t* n_stored, int64_t* pitch);
+int sdrx_atv_screen_last_dev(sdrx_atv_t* h, int32_t ch, const uint8_t** d_screen, int32_t* rows, int32_t* cols);
+/* the real parts of the Samples (re, 0) of m_scopeSampleBuffer of the last feed, one per input with `scope` set, none without */
+int64_t sdrx_atv_read(sdrx_atv_t* h, int32_t ch, int16_t* scope_re, int64_t cap_samples);
+int sdrx_atv_last_dev(sdrx_atv_t* h, int32_t ch, const int16_t** d_scope_re, int64_t* n);
+int sdrx_atv_state(sdrx_atv_t* h, int32_t ch, sdrx_atv_state_t* s);
+int sdrx_atv_get_design(sdrx_atv_t* h, int32_t ch, sdrx_atv_design_t* d);
+/* the rest of the design products, for inspection (any pointer may be NULL): the decimator's FIR, the phase-0 row of
+ * m_interpolator.create(24, tvRate, rf_bw / 2.2f, 3.0), *ntaps of them (72; 0 without the decimator), and m_DSBFilter's filter and
+ * filterOpp as 2048 (re, im) pairs each.  Returns 2048 with the FFT filter, 0 without (the arrays are then left alone), < 0 on error */
+int sdrx_atv_get_filters(sdrx_atv_t* h, int32_t ch, int32_t* ntaps, float* taps, int32_t taps_cap, float* filter_iq, float* filter_opp_iq);
+int sdrx_atv_sync(sdrx_atv_t* h);
+int sdrx_atv_set_stream(sdrx_atv_t* h, void* hip_stream);
+int sdrx_atv_get_stream(sdrx_atv_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_atv_set_timing(sdrx_atv_t* h, int enabled);
+int sdrx_atv_get_timing(sdrx_atv_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the walk of the last feed: atv_walk_kernel, its grid, block and LDS bytes */
+int sdrx_atv_last_launch(const sdrx_atv_t* h, char* kernel_name, int name_cap,
+                         int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,6 +293,23 @@ def lib() -> C.CDLL:
         "sdrx_chan24_bank_read": (i64, [vp, i32, vp, i64]),
         "sdrx_firbank_create": (C.c_int, [pp, C.c_int, i32, vp]),
         "sdrx_firbank_destroy": (C.c_int, [vp]),
+        "sdrx_atv_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_atv_destroy": (C.c_int, [vp]),
+        "sdrx_atv_reset": (C.c_int, [vp]),
+        "sdrx_atv_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_atv_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_atv_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_atv_frames": (i64, [vp, i32, C.POINTER(i64)]),
+        "sdrx_atv_read_events": (i64, [vp, i32, vp, i64]),
+        "sdrx_atv_read_frame": (i64, [vp, i32, i64, vp, i64]),
+        "sdrx_atv_read_screen": (i64, [vp, i32, vp, i64]),
+        "sdrx_atv_frames_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64), C.POINTER(i64)]),
+        "sdrx_atv_screen_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i32), C.POINTER(i32)]),
+        "sdrx_atv_read": (i64, [vp, i32, vp, i64]),
+        "sdrx_atv_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_atv_state": (C.c_int, [vp, i32, vp]),
+        "sdrx_atv_get_design": (C.c_int, [vp, i32, vp]),
+        "sdrx_atv_get_filters": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, vp]),
         "sdrx_firbank_feed": (C.c_int, [vp, vp, vp, vp]),
         "sdrx_firbank_get_taps": (C.c_int, [vp, i32, vp, i32]),
         "sdrx_sdriq_parse_header": (C.c_int, [vp, C.c_uint64, vp]),
@@ -321,7 +338,7 @@ def lib() -> C.CDLL:
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
                 "wfm": five + ("get_stream",), "bfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
-                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "lora": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "lora": five + ("get_stream",), "atv": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
         for name in names:
@@ -1245,6 +1262,96 @@ class AmDemodBank(_DemodBank):
     def design(self, ch: int):
         """(taps per phase, taps [16 * ntaps], the 151 folded Bandpass taps, NCO increment, squelch level)"""
         return self._design(ch, np.zeros(151, np.float32))
+
+
+class AtvCfg(C.Structure):
+    """sdrx_atv_cfg: one ATVDemod (in_rate, nco_freq = -frequencyOffset, the arguments of configureRF and configure, frames_cap)"""
+    _fields_ = [("in_rate", C.c_int32), ("nco_freq", C.c_int32), ("modulation", C.c_int32), ("rf_bw", C.c_float), ("rf_opp_bw", C.c_float),
+                ("fft_filtering", C.c_int32), ("decimator_enable", C.c_int32), ("fm_deviation", C.c_float), ("line_duration", C.c_float),
+                ("top_duration", C.c_float), ("frames_per_s", C.c_float), ("standard", C.c_int32), ("n_lines", C.c_int32),
+                ("level_synchro_top", C.c_float), ("level_black", C.c_float), ("hsync", C.c_int32), ("vsync", C.c_int32),
+                ("invert_video", C.c_int32), ("scope", C.c_int32), ("frames_cap", C.c_int32)]
+
+
+class AtvState(C.Structure):
+    """sdrx_atv_state_t: the PROCESSING block of atvdemod.h, floats as their bits"""
+    _fields_ = [("image_index", C.c_int32), ("synchro_points", C.c_int32), ("synchro_detected", C.c_int32),
+                ("vertical_synchro_detected", C.c_int32), ("col_index", C.c_int32), ("sample_index", C.c_int32), ("row_index", C.c_int32),
+                ("line_index", C.c_int32), ("avg_col_index", C.c_int32), ("screen_row", C.c_int32), ("amp_line_average", C.c_uint32),
+                ("eff_min", C.c_uint32), ("eff_max", C.c_uint32), ("amp_min", C.c_uint32), ("amp_max", C.c_uint32), ("amp_delta", C.c_uint32),
+                ("buffer_i", C.c_uint32 * 6), ("buffer_q", C.c_uint32 * 6)]
+
+
+class AtvDesign(C.Structure):
+    """sdrx_atv_design_t: applySettings' and applyStandard's integers"""
+    _fields_ = [(k, C.c_int32) for k in ("samples_per_line", "samples_per_top", "samples_per_line_signals", "samples_per_hsync", "sync_lines",
+                                         "black_lines", "eq_lines", "interleaved", "tv_rate", "cols", "rows", "nco_inc")]
+
+
+class ATVBank(_DemodBank):
+    """N ATV demodulators (ATVDemod::feed): int16 I/Q at the channelizer's output rate in; the frames the screen was asked to render,
+    the screen, the scope stream (read(), int16 real parts) and the state out."""
+    _prefix, _cfg = "atv", AtvCfg
+
+    def _count(self, name: str, *args) -> int:
+        n = self._fn(name)(self._h, *args)
+        if n < 0:
+            raise SdrxError(f"sdrx_atv_{name} rc={n}: {lib().sdrx_last_error().decode()}")
+        return n
+
+    def design(self, ch: int) -> AtvDesign:
+        d = AtvDesign()
+        self._call("get_design", ch, C.byref(d))
+        return d
+
+    def filters(self, ch: int):
+        """(the decimator's phase-0 taps, m_DSBFilter's filter and filterOpp as 4096 floats each); empty arrays where the stage is off"""
+        nt = C.c_int32()
+        taps, f, fo = np.zeros(128, np.float32), np.zeros(4096, np.float32), np.zeros(4096, np.float32)
+        n = self._count("get_filters", ch, C.byref(nt), taps.ctypes.data, taps.size, f.ctypes.data, fo.ctypes.data)
+        return taps[:nt.value].copy(), f[:2 * n].copy(), fo[:2 * n].copy()
+
+    def state(self, ch: int) -> AtvState:
+        st = AtvState()
+        self._call("state", ch, C.byref(st))
+        return st
+
+    def frames(self, ch: int):
+        """(frames of the last feed that kept a snapshot, renderImage calls of the last feed)"""
+        n = C.c_int64()
+        return self._count("frames", ch, C.byref(n)), n.value
+
+    def events(self, ch: int) -> np.ndarray:
+        """for each render of the last feed the index of its input sample within the feed"""
+        cap = self.frames(ch)[1]
+        out = np.empty(max(cap, 1), np.int32)
+        return out[:self._count("read_events", ch, out.ctypes.data, cap)].copy()
+
+    def _image(self, ch: int, name: str, *args) -> np.ndarray:
+        d = self.design(ch)
+        out = np.empty((d.rows, d.cols), np.uint8)
+        self._count(name, ch, *args, out.ctypes.data, out.size)
+        return out
+
+    def frame(self, ch: int, k: int) -> np.ndarray:
+        """the screen as it stood at render k of the last feed: [rows, cols] grey levels"""
+        return self._image(ch, "read_frame", k)
+
+    def screen(self, ch: int) -> np.ndarray:
+        """the screen after the last feed"""
+        return self._image(ch, "read_screen")
+
+    def frames_last_dev(self, ch: int):
+        """(device pointer, stored frames, bytes from one to the next)"""
+        p, n, pitch = C.c_void_p(), C.c_int64(), C.c_int64()
+        self._call("frames_last_dev", ch, C.byref(p), C.byref(n), C.byref(pitch))
+        return p.value or 0, n.value, pitch.value
+
+    def screen_last_dev(self, ch: int):
+        """(device pointer, rows, cols)"""
+        p, r, c = C.c_void_p(), C.c_int32(), C.c_int32()
+        self._call("screen_last_dev", ch, C.byref(p), C.byref(r), C.byref(c))
+        return p.value or 0, r.value, c.value
 
 
 class LoraDemodBank(_DemodBank):

@@ -41,6 +41,7 @@ struct BeChan {                         // device resident: config + carried sta
     int bypass;                         // 1: no Interpolator, every NCO-mixed sample goes into the fftfilt blocks (backend_set_front)
     int ncof;                           // 1: the oscillator is NCOF (ncof.h): a float phase and a float increment
     float ncof_inc;                     // NCOF::setFreq: (freq * 4096) / rate
+    int nomix;                          // 1: no oscillator at all, the sample itself goes on (backend_set_nomix: ATVDemod at offset 0)
     // --- state
     int nco_phase;                      // phase after the last consumed input sample
     float ncof_phase;                   // NCOF::m_phase after the last consumed input sample
@@ -313,6 +314,7 @@ void be_mix_kernel(const BeChan* __restrict__ ch, const BeBufs* __restrict__ buf
         const float o_r = tbl[p], o_i = -tbl[(p + BE_NCO_N / 4) & (BE_NCO_N - 1)];
         const float a = (float)(int16_t)(v & 0xffffu), q = (float)(int16_t)(v >> 16);
         float2 m; m.x = a * o_r - q * o_i; m.y = a * o_i + q * o_r;         // std::complex<float> operator*=
+        if (s.nomix) { m.x = a; m.y = q; }                  // the table's sine at phase 0 is cos(pi / 2) rounded, not 0: (0, q) would not survive the product
         b.mixed[i] = m;
         if (s.bypass && j >= 0) {                           // processOneSample(c): straight into the filter's block
             b.res[s.pending + j] = m;

@@ -22,5 +22,9 @@ int backend_start_at(sdrx_backend_t* b, int32_t ch, float step, float distance);
 // input, as ChannelAnalyzer does with m_useInterpolator off) and / or with NCOF, the oscillator with a float phase and a float
 // increment (ncof.h), in place of NCO.
 int backend_set_front(sdrx_backend_t* b, int32_t ch, int bypass, int ncof);
+// A back-end that has not been fed yet: channel ch runs without an oscillator, the int16 sample itself is what the NCO mix
+// would have produced.  ATVDemod::feed skips the mix when the offset is 0, and NCO::nextIQ at phase 0 is (1, -cos(pi / 2)) with
+// the cosine rounded to 6.1e-17, so the product is not the sample where its real or imaginary part is 0.
+int backend_set_nomix(sdrx_backend_t* b, int32_t ch);
 
 } // namespace sdrx

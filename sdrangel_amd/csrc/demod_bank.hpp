@@ -1,5 +1,5 @@
 // The host skeleton of a demodulator bank whose front is a channel back-end (sdrx_am.hip, sdrx_nfm.hip, sdrx_ssb.hip,
-// sdrx_udpsrc.hip, sdrx_lora.hip): the handle's members, create / destroy / reset, capacity growth, the per-feed pointer table, the three
+// sdrx_udpsrc.hip, sdrx_lora.hip, sdrx_atv.hip): the handle's members, create / destroy / reset, capacity growth, the per-feed pointer table, the three
 // feed entry points and the getters that only fetch one channel's state.  A family F supplies what is its own:
 //   Handle, Cfg, Chan, Bufs      the opaque C type (struct sdrx_x : DemodBank<F> {}), its configuration, the device-resident
 //                                channel state and the per-channel pointer table of its kernel header

@@ -407,6 +407,17 @@ int backend_set_front(sdrx_backend_t* b, int32_t c, int bypass, int ncof)
     return SDRX_OK;
 }
 
+int backend_set_nomix(sdrx_backend_t* b, int32_t c)
+{
+    if (!b || c < 0 || c >= b->n_ch) { set_error("backend_set_nomix: bad argument"); return SDRX_EINVAL; }
+    SDRX_HIP(hipSetDevice(b->core.device));
+    SDRX_HIP(hipStreamSynchronize(b->core.stream));
+    BeChan& s = b->h_chan[(size_t)c];                       // the config part and a fresh state
+    s.nomix = 1;
+    SDRX_HIP(hipMemcpy(b->d_chan + c, &s, sizeof s, hipMemcpyHostToDevice));
+    return SDRX_OK;
+}
+
 int backend_start_at(sdrx_backend_t* b, int32_t c, float step, float distance)
 {
     if (!b || c < 0 || c >= b->n_ch || !(step >= 1.0f) || !(distance >= 0.0f)) { set_error("backend_start_at: bad argument"); return SDRX_EINVAL; }
