@@ -12,7 +12,10 @@ AM puts the level on the envelope (0.1 + 0.9 v of the amplitude), FM on the phas
 a carrier at `f0` Hz that the channel's NCO takes back to 0.
 
 The small shape: 160000 S/s, 64 lines at 25 frames/s -- 100 samples per line, 7 per top, a screen of 82 columns; the line and top
-durations are a quarter sample above the whole numbers so that no rounding of the float product decides the integers."""
+durations are a quarter sample above the whole numbers so that no rounding of the float product decides the integers.
+
+CASES all have that shape (or 40 / 3).  SHAPE_CASES, CUT_STREAMS and random_cases() below put the walk that takes a stretch of a
+line at a time (atv_fast_stretch) at other line and top lengths; the oracle's geometry counters (GEO) say what they reach."""
 from __future__ import annotations
 
 import ctypes as C
@@ -30,6 +33,7 @@ ORACLE_SRC = os.path.join(ROOT, "tests", "atv_oracle.cpp")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 CSRC = os.path.join(ROOT, "sdrangel_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "atv_golden.npz")
+RANDOM_GOLDEN = os.path.join(ROOT, "tests", "golden", "atv_random_golden.npz")     # digests: golden_random_cases()
 
 FM1, FM2, FM3, AM, USB, LSB = range(6)
 PAL625, PAL525, STD405, SHORT_I, SHORT, HSKIP = range(6)
@@ -46,6 +50,10 @@ DESIGN_FIELDS = ("samples_per_line", "samples_per_top", "samples_per_line_signal
 #: the oracle's branch counters, in the order of atv_scan.hpp's ATV_HIT_ numbers, then the most renders within one line
 HITS = ("hcorr_classic", "hcorr_hskip", "minus150", "no_hsync", "row_neg", "row_big", "col_neg", "col_big", "vsync_even", "vsync_odd",
         "half_frame", "half_frame_am", "delta_one", "hskip_render", "null_row", "max_renders_in_line")
+#: the oracle's geometry counters of processClassic (ato_geo, the GEO_ enum of tests/atv_oracle.cpp): what a walk that takes 64
+#: samples at a time can get wrong, each defined on the reference's own variables
+GEO = ("detect_held", "detect_twice_near", "points_from_far", "vsync_tie", "vsync_first_col", "vsync_last_col", "vsync_again", "col_negative",
+       "col_past_line", "line_past_frame", "row_stays", "nan_at_check", "detect_at_half")
 
 
 class Cfg(C.Structure):
@@ -271,7 +279,7 @@ def build_oracle() -> C.CDLL:
         getattr(L, name).argtypes = args
     L.ato_filters.restype = C.c_int
     L.ato_filters.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    for name in ("ato_state", "ato_design", "ato_hits"):
+    for name in ("ato_state", "ato_design", "ato_hits", "ato_geo"):
         getattr(L, name).restype = None
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
     return L
@@ -319,6 +327,11 @@ class OracleAtv:
         self.L.ato_hits(self.h, out)
         return dict(zip(HITS, (int(v) for v in out)))
 
+    def geo(self) -> dict:
+        out = (C.c_int64 * len(GEO))()
+        self.L.ato_geo(self.h, out)
+        return dict(zip(GEO, (int(v) for v in out)))
+
     def close(self):
         self.L.ato_destroy(self.h)
         self.h = None
@@ -327,7 +340,7 @@ class OracleAtv:
 def run_spans(L: C.CDLL, k: dict, spans) -> dict:
     o = OracleAtv(L, k)
     feeds = [o.feed(x) for x in spans]
-    res = {"feeds": feeds, "hits": o.hits(), "design": design_words(o.design)}
+    res = {"feeds": feeds, "hits": o.hits(), "geo": o.geo(), "design": design_words(o.design)}
     o.close()
     return res
 
@@ -354,4 +367,217 @@ def assert_coverage(hits_per_case: list[dict]):
     total = {k: (max if k == "max_renders_in_line" else sum)(h[k] for h in hits_per_case) for k in HITS}
     short = {k: (total[k], v) for k, v in COVERAGE.items() if total[k] < v}
     assert not short, f"branches the cases do not reach (have, need): {short}"
+    return total
+
+
+# ---------------------------------------------------------------- the stretch walk at other shapes (atv_fast_stretch)
+#: what SHAPE_CASES' FM classic cases have to reach, summed, on the oracle's geometry counters
+GEO_COVERAGE = {k: 1 for k in GEO}
+SHAPE_RATE = 1000000
+#: samples per line / per top: lines against the 64-sample window, tops that need the carried count, rooms under 8
+SHAPES = ((9, 1), (16, 2), (63, 5), (64, 5), (65, 5), (86, 31), (128, 9), (129, 64), (192, 70), (640, 47), (1000, 130), (100, 0),
+          (127, 9), (129, 9), (192, 63), (192, 64), (192, 65))
+
+
+def is_fm_classic(k: dict) -> bool:
+    return k["modulation"] != AM and k["standard"] != HSKIP
+
+
+def shape_cfg(spl: int, spt: int, rate: int = SHAPE_RATE, **kw) -> dict:
+    d = dict(in_rate=rate, line_duration=(spl + 0.25) / rate, top_duration=(spt + 0.25) / rate, rf_bw=0.375 * rate, rf_opp_bw=0.0625 * rate, n_lines=16)
+    d.update(kw)
+    return cfg(**d)
+
+
+def shape_video(spl: int, spt: int, mod: int, fields, **kw) -> dict:
+    return dict({"kind": "video", "spl": spl, "spt": spt, "fields": list(fields), "sigma": 40.0}, **kw)
+
+
+def _shape(name: str, seed: int, spl: int, spt: int, mod: int, frames: int = 3, sig=None, n=None, splits=None, fields=None, **kw) -> dict:
+    """a case at `spl` samples per line and `spt` per top: `frames` frames of video and a third of a line, unless sig or n say otherwise"""
+    k = shape_cfg(spl, spt, modulation=mod, **kw)
+    sig = sig if sig is not None else shape_video(spl, spt, mod, fields or [k["n_lines"]])
+    n = n if n is not None else frames * k["n_lines"] * spl + spl // 3
+    return {"name": name, "seed": seed, "n": n, "sig": sig, "cfg": k, "splits": splits or _ragged(n, seed, 5)}
+
+
+def _shape_cases() -> list[dict]:
+    out = []
+    for i, (spl, spt) in enumerate(SHAPES):                 # FM1, FM2 and FM3 in turn over the shapes; 16 to 24 lines, 3 or 4 frames
+        mod = (FM1, FM2, FM3)[i % 3]
+        lines = 16 + 2 * (i % 5)
+        frames = 3 + i % 2 if (3 + i % 2) * lines * spl < 50000 else 3
+        out.append(_shape(f"shape_{spl}_{spt}_fm{mod + 1}", 100 + i, spl, spt, mod, frames=frames, n_lines=lines))
+    C2 = {"kind": "const", "i": 3000, "q": -4000}
+    out += [
+        # the other two modulations at the shapes nearest the window and at the far count
+        _shape("shape_64_5_fm3", 120, 64, 5, FM3), _shape("shape_65_5_fm1", 121, 65, 5, FM1), _shape("shape_129_64_fm3", 122, 129, 64, FM3),
+        _shape("shape_192_70_fm1", 123, 192, 70, FM1), _shape("shape_192_64_fm3", 124, 192, 64, FM3), _shape("shape_16_2_fm3", 125, 16, 2, FM3),
+        _shape("shape_9_1_fm2", 126, 9, 1, FM2), _shape("shape_100_0_fm2", 127, 100, 0, FM2), _shape("shape_100_1_fm3", 128, 100, 1, FM3),
+        # the interleaved standards on odd and even fields
+        _shape("shape_short_i_65", 130, 65, 5, FM3, standard=SHORT_I, n_lines=17, fields=[8, 9]),
+        _shape("shape_short_i_129", 131, 129, 64, FM2, standard=SHORT_I, n_lines=20, fields=[9, 10, 11]),
+        _shape("shape_405_63", 132, 63, 5, FM1, standard=STD405, n_lines=33, fields=[16, 17]),
+        _shape("shape_525_86", 133, 86, 31, FM3, standard=PAL525, n_lines=49, fields=[24, 25]),
+        _shape("shape_625_128", 134, 128, 9, FM2, standard=PAL625, n_lines=53, fields=[26, 27]),
+        # the switches
+        _shape("shape_nohsync_65", 140, 65, 5, FM3, hsync=0, lead=23), _shape("shape_nohsync_640", 141, 640, 47, FM2, hsync=0, lead=301),
+        _shape("shape_nohsync_9", 142, 9, 1, FM1, hsync=0), _shape("shape_novsync_129", 143, 129, 64, FM3, vsync=0),
+        _shape("shape_novsync_nohsync_192", 144, 192, 65, FM1, vsync=0, hsync=0, lead=77), _shape("shape_novsync_16", 145, 16, 2, FM2, vsync=0),
+        _shape("shape_inverted_86", 146, 86, 31, FM3, invert_video=1), _shape("shape_inverted_640", 147, 640, 47, FM1, invert_video=1, frames=2),
+        _shape("shape_dev_half_128", 148, 128, 9, FM3, fm_deviation=0.5, sig=shape_video(128, 9, FM3, [16], swing=0.5)),
+        _shape("shape_dev_two_192", 149, 192, 70, FM3, fm_deviation=2.0, sig=shape_video(192, 70, FM3, [16], swing=1.6)),
+        _shape("shape_dev_two_63_fm2", 150, 63, 5, FM2, fm_deviation=2.0, sig=shape_video(63, 5, FM2, [16])),
+        # the pulse exactly spt long: the noise on the porch decides whether the detection is held
+        _shape("shape_exact_pulse_100", 151, 100, 7, FM3, sig=shape_video(100, 7, FM3, [16], sync_extra=0, sigma=300.0)),
+        _shape("shape_exact_pulse_129", 152, 129, 64, FM3, sig=shape_video(129, 64, FM3, [16], sync_extra=0, sigma=300.0)),
+        _shape("shape_exact_pulse_640", 153, 640, 47, FM2, sig=shape_video(640, 47, FM2, [16], sync_extra=0, sigma=200.0), frames=2),
+        # sync lost for more than four lines before a line 0: the correction puts the column past the line; -150 wins: under 0
+        _shape("shape_lost_past_line_65", 154, 65, 5, FM3, vsync=0, sig=shape_video(65, 5, FM3, [16], lost=[(201, 547)])),
+        _shape("shape_lost_past_line_129", 155, 129, 9, FM3, vsync=0, sig=shape_video(129, 9, FM3, [16], lost=[(401, 1089)])),
+        _shape("shape_lost_vsync_100", 156, 100, 7, FM3, sig=shape_video(100, 7, FM3, [16], lost=[(2656, 3289)]), frames=4),
+        # a lead of 40 puts the pulses of the first lines in the left half: the -150 term wins at the first line 0
+        _shape("shape_minus150_100", 157, 100, 7, FM3, sig=shape_video(100, 7, FM3, [16], lead=40)),
+        _shape("shape_minus150_192", 158, 192, 9, FM2, vsync=0, sig=shape_video(192, 9, FM2, [16], lead=40)),
+        # no vsync in the signal for more than a frame: the line index reaches the frame, the row stays
+        _shape("shape_no_broad_65", 159, 65, 5, FM3, sig=shape_video(65, 5, FM3, [16], broad=0)),
+        _shape("shape_no_broad_i_129", 160, 129, 64, FM2, standard=SHORT_I, sig=shape_video(129, 64, FM2, [16], broad=0)),
+        # (0, 0) samples inside the vsync region under FM1: a NaN sum at the check
+        _shape("shape_nan_100", 161, 100, 7, FM1, sig=shape_video(100, 7, FM1, [16], silent=[(880, 884), (2490, 2600)])),
+        _shape("shape_nan_640", 162, 640, 47, FM1, frames=2, sig=shape_video(640, 47, FM1, [16], silent=[(3000, 3001), (9400, 9500)])),
+        _shape("shape_nan_129_fm2", 163, 129, 64, FM2, sig=shape_video(129, 64, FM2, [16], silent=[(1000, 1001), (2150, 2200)])),
+        # noise under tops of 1 and 2 samples: detections a few samples apart, and a vsync wherever the sum happens to be
+        _shape("shape_noise_100_1", 164, 100, 1, FM3, sig={"kind": "noise"}, n=9000), _shape("shape_noise_100_2", 165, 100, 2, FM1, sig={"kind": "noise"}, n=9000),
+        _shape("shape_noise_9_1", 166, 9, 1, FM3, sig={"kind": "noise"}, n=6000, level_black=0.6), _shape("shape_noise_16_2", 167, 16, 2, FM2, sig={"kind": "noise"}, n=6000),
+        _shape("shape_noise_65_2", 168, 65, 2, FM3, sig={"kind": "noise"}, n=9000, level_black=0.6, level_synchro_top=0.25),
+        _shape("shape_noise_640_47", 169, 640, 47, FM3, sig={"kind": "noise"}, n=9000, level_synchro_top=0.25),
+        # the tie: constant I/Q under FM3 is exactly 0.5 from the second sample on; 3 * 86 / 4 = 64 and level_black 0.5 put the level at 16.0,
+        # which the sum equals at the first check of a line with 31 per top, passes by 0.5 with 30 and misses by 0.5 with 32
+        _shape("shape_tie_86_31", 170, 86, 31, FM3, sig=C2, n=4000, level_black=0.5),
+        _shape("shape_tie_86_30", 171, 86, 30, FM3, sig=C2, n=4000, level_black=0.5),
+        _shape("shape_tie_86_32", 172, 86, 32, FM3, sig=C2, n=4000, level_black=0.5),
+        # other inputs that are no picture
+        _shape("shape_zeros_129_fm1", 173, 129, 64, FM1, sig={"kind": "zero"}, n=5000), _shape("shape_const_640_fm2", 174, 640, 47, FM2, sig=C2, n=9000),
+        _shape("shape_clipped_192", 175, 192, 64, FM2, sig=shape_video(192, 64, FM2, [16], amp=60000.0)),
+        # the old path (AM, HSkip) on the new shapes, and the front stages
+        _shape("shape_am_129", 176, 129, 64, AM), _shape("shape_hskip_65", 177, 65, 5, FM3, standard=HSKIP, sig=shape_video(65, 5, FM3, [16], skip=True, lead=20)),
+        _shape("shape_decim_86", 178, 86, 31, FM1, decimator_enable=1), _shape("shape_fft_129", 179, 129, 64, FM3, fft_filtering=1),
+        _shape("shape_offset_640", 180, 640, 47, FM3, frames=2, nco_freq=-125000, sig=shape_video(640, 47, FM3, [16], f0=125000.0)),
+        # the true shape: PAL-625 at 10 MS/s, 64 us lines and 4.7 us tops, fields of 312 and 313 lines, about 700 lines of signal
+        _shape("shape_pal625_10ms", 181, 640, 47, FM1, rate=10000000, n_lines=625, standard=PAL625, frames_cap=2, n=700 * 640,
+               sig=shape_video(640, 47, FM1, [312, 313], sigma=60.0)),
+    ]
+    names = [c["name"] for c in out]
+    assert len(set(names)) == len(names)
+    return out
+
+
+SHAPE_CASES = _shape_cases()
+SHAPE_BY_NAME = {c["name"]: c for c in SHAPE_CASES}
+
+# ---------------------------------------------------------------- every cut of four short streams
+CUT_CHANNELS = 131                      # channel i gets the first i samples in the first feed and the rest in the second
+CUT_TAIL = (1, 7, 8, 9, 63, 64, 65)     # then every channel these, in turn: the stretch is tried from a span of 8 on
+_T = sum(CUT_TAIL)
+CUT_STREAMS = [
+    _shape("cut_100_7", 190, 100, 7, FM3, n=13 + 6 * 100 + _T, splits=[13 + 6 * 100 + _T], sig=shape_video(100, 7, FM3, [5], broad=1, lead=13, sigma=60.0)),
+    _shape("cut_129_64", 191, 129, 64, FM2, n=7 * 129 + _T, splits=[7 * 129 + _T], sig=shape_video(129, 64, FM2, [6], broad=1, sigma=60.0)),
+    _shape("cut_86_31_tie", 192, 86, 31, FM3, n=6 * 86 + _T, splits=[6 * 86 + _T], sig={"kind": "const", "i": 3000, "q": -4000}, level_black=0.5),
+    _shape("cut_65_5_nohsync", 193, 65, 5, FM1, n=29 + 6 * 65 + _T, splits=[29 + 6 * 65 + _T], hsync=0, sig=shape_video(65, 5, FM1, [4], broad=1, lead=29, sigma=60.0)),
+]
+
+
+def cut_spans(case: dict, i: int) -> list[int]:
+    """channel i's feeds of a cut stream: i samples, the rest of the body, then the tail's pieces"""
+    body = case["n"] - _T
+    assert 0 <= i <= body
+    return [i, body - i] + list(CUT_TAIL)
+
+
+# ---------------------------------------------------------------- random configurations
+RANDOM_SEED = 20261021
+RANDOM_RATES = (160000, 1000000, 2000000, 10000000)
+#: the fewest lines each standard's screen needs one row for (lines - black lines >= 1), by ATVStd
+LEAST_LINES = {PAL625: 49, PAL525: 45, STD405: 29, SHORT_I: 5, SHORT: 5, HSKIP: 2}
+
+
+def _f32(v) -> float:
+    return float(np.float32(v))
+
+
+def random_case(rng, i: int) -> dict:
+    std = int(rng.choice([PAL625, PAL525, STD405, SHORT_I, SHORT, HSKIP], p=[0.1, 0.1, 0.1, 0.25, 0.35, 0.1]))
+    mod = int(rng.choice([FM1, FM2, FM3, AM], p=[0.3, 0.3, 0.3, 0.1]))
+    spl = int(rng.integers(9, 701))
+    spt = int(rng.integers(0, spl // 3 + 1))
+    least = LEAST_LINES[std]
+    n_lines = int(rng.integers(least, max(40, least + 8) + 1))           # to 40, or eight past the least where that is above 40
+    rate = int(rng.choice(RANDOM_RATES))
+    dev = float(rng.choice([1.0, 1.0, 0.5, 2.0]))
+    half = rate // 2
+    nco = int(rng.choice([0, 0, int(rng.integers(-half // 2, half // 2)), int(rng.integers(-half // 2, half // 2)), half - 1, 1 - half, half, -half]))
+    k = shape_cfg(spl, spt, rate, modulation=mod, standard=std, n_lines=n_lines, fm_deviation=dev, nco_freq=nco,
+                  hsync=int(rng.random() < 0.8), vsync=int(rng.random() < 0.8), invert_video=int(rng.random() < 0.2),
+                  level_synchro_top=_f32(rng.uniform(-0.2, 0.25)), level_black=_f32(rng.uniform(0.02, 0.6)),
+                  decimator_enable=int(rng.random() < 0.2), fft_filtering=int(rng.random() < 0.2),
+                  rf_bw=_f32(rate * rng.uniform(0.3, 0.6)), rf_opp_bw=_f32(rate * rng.uniform(0.0, 0.3)),
+                  scope=int(rng.random() < 0.5), frames_cap=int(rng.integers(1, 4)))
+    n = min(20000, int(rng.integers(2, 5)) * n_lines * spl + int(rng.integers(0, spl)))
+    kind = str(rng.choice(["video", "video", "video", "lossy", "lossy", "noise", "const", "zero", "clipped"]))
+    if kind in ("video", "lossy", "clipped"):
+        h = n_lines // 2
+        fields = [h, n_lines - h] if std in (PAL625, PAL525, STD405, SHORT_I) else [n_lines]
+        swing = min(dev, 1.6) if mod == FM3 else 1.0        # FM1 and FM2 answer the sine of the step
+        sig = shape_video(spl, spt, mod, fields, swing=swing, sigma=float(rng.choice([0.0, 40.0, 300.0])), lead=int(rng.integers(0, spl)),
+                          sync_extra=int(rng.integers(0, 2)), skip=std == HSKIP, f0=float(-nco) if abs(nco) < half // 2 else 0.0)
+        if kind == "lossy":
+            a = int(rng.integers(0, max(1, n - spl)))
+            sig["lost"] = [(a, min(n, a + int(rng.integers(spl, 6 * spl + 1))))]
+        if kind == "clipped":
+            sig["amp"] = 60000.0
+    elif kind == "const":
+        sig = {"kind": "const", "i": int(rng.integers(-9000, 9001)), "q": int(rng.choice([0, int(rng.integers(-9000, 9001))]))}
+    else:
+        sig = {"kind": kind}
+    seed = 1000 + i
+    return {"name": f"random_{i:03d}", "seed": seed, "n": n, "sig": sig, "cfg": k, "splits": _ragged(n, seed, int(rng.integers(2, 6)))}
+
+
+def random_cases(count: int = 100) -> list[dict]:
+    """the first `count` random cases, drawn in order from one generator"""
+    rng = np.random.default_rng(RANDOM_SEED)
+    return [random_case(rng, i) for i in range(count)]
+
+
+def golden_random_cases() -> list[dict]:
+    """what tests/golden/atv_random_golden.npz records: the shape cases, the cut streams fed whole, the random cases"""
+    return SHAPE_CASES + CUT_STREAMS + random_cases()
+
+
+def load_random_golden() -> dict:
+    """atv_random_golden.npz by case name, each entry as make_golden_atv.pack_digests packs a single run"""
+    g = np.load(RANDOM_GOLDEN)
+    out, f0, e0, k0 = {}, 0, 0, 0
+    for i, name in enumerate(g["names"].tolist()):
+        f1 = f0 + int(g["feeds"][i])
+        e1, k1 = e0 + int(g["event_counts"][f0:f1].sum()), k0 + int(g["frame_counts"][f0:f1].sum())
+        out[name] = {"in_sha256": g["in_sha256"][i], "design": g["design"][i], "event_counts": g["event_counts"][f0:f1], "events": g["events"][e0:e1],
+                     "state": g["state"][f0:f1], "frame_counts": g["frame_counts"][f0:f1], "frames_sha256": g["frames_sha256"][k0:k1],
+                     "screens_sha256": g["screens_sha256"][f0:f1], "scope_sha256": g["scope_sha256"][f0:f1]}
+        f0, e0, k0 = f1, e1, k1
+    return out
+
+
+def assert_random_shares(cases):
+    """the draw stays with the stretch: half of it FM under a classic standard, a tenth with a top of a stretch or more"""
+    fm = sum(1 for c in cases if is_fm_classic(c["cfg"]))
+    far = sum(1 for c in cases if int(c["cfg"]["top_duration"] * c["cfg"]["in_rate"]) >= 64)
+    assert len(cases) == 100 and fm >= 50 and far >= 10, (len(cases), fm, far)
+    return fm, far
+
+
+def assert_geo_coverage(geo_per_case: list[dict]):
+    total = {k: sum(g[k] for g in geo_per_case) for k in GEO}
+    short = {k: (total[k], v) for k, v in GEO_COVERAGE.items() if total[k] < v}
+    assert not short, f"geometry the FM classic shape cases do not reach (have, need): {short}"
     return total

@@ -20,6 +20,8 @@
  *   ato_state(h, out)               sdrx_atv_state_t
  *   ato_design(h, out)              sdrx_atv_design_t
  *   ato_hits(h, out[ATV_N_HITS + 1])  the branch counters since creation, then the most renders within one line
+ *   ato_geo(h, out[ATO_N_GEO])      the geometry counters of processClassic since creation: what a 64-sample partition of the
+ *                                   stream can get wrong, each defined on the reference's own variables (the GEO_ enum below)
  */
 #include <climits>
 #include <cmath>
@@ -36,6 +38,24 @@ namespace {
 using namespace sdrx;                                           /* the ATV_HIT_ numbers */
 
 const float SDR_RX_SCALEF = 32768.0f;
+
+/* the geometry counters, in the order of tests/atv_cases.py's GEO; all of processClassic, a sample being one call of it */
+enum {
+    GEO_DETECT_HELD,        /* m_blnSynchroDetected true on the sample directly after one where it was true */
+    GEO_DETECT_TWICE_NEAR,  /* a detection 2 .. 63 samples after the one before */
+    GEO_POINTS_FROM_FAR,    /* a detection whose counted run (the first increment behind the last reset) began >= 64 samples earlier */
+    GEO_VSYNC_TIE,          /* a vsync check with m_fltAmpLineAverage == fltSynchroTrameLevel: it fires */
+    GEO_VSYNC_FIRST_COL,    /* the vsync fires on the sample where m_intColIndex reaches intSynchroTimeSamples */
+    GEO_VSYNC_LAST_COL,     /* the vsync fires on the last sample before a new line */
+    GEO_VSYNC_AGAIN,        /* the sum at or under the level while m_blnVerticalSynchroDetected is set: cleared, no event */
+    GEO_COL_NEGATIVE,       /* the line-0 correction leaves m_intColIndex < 0 */
+    GEO_COL_PAST_LINE,      /* ... or >= samples per line + per top */
+    GEO_LINE_PAST_FRAME,    /* the half-frame branch with vsync on: m_intLineIndex reached m_intNumberOfLines */
+    GEO_ROW_STAYS,          /* a new line with m_intRowIndex >= m_intNumberOfLines: no selectRow */
+    GEO_NAN_AT_CHECK,       /* a vsync check with a NaN sum */
+    GEO_DETECT_AT_HALF,     /* a detection with m_intColIndex == samples per line / 2: the first column where the -150 term is left out */
+    ATO_N_GEO
+};
 
 int f2i(float v)                                                /* cvttss2si */
 {
@@ -82,6 +102,8 @@ struct Ato {
     /* probes */
     int64_t hits[ATV_N_HITS];
     int64_t renders_in_line, max_renders_in_line;
+    int64_t geo[ATO_N_GEO];
+    int64_t tick, last_detection, run_start;                    /* processClassic calls; the call of the last detection, of the run's first increment (-1: none) */
 
     void selectRow(int line)
     {
@@ -150,11 +172,20 @@ struct Ato {
     {
         int intSynchroTimeSamples = (3 * m_intNumberSamplePerLine) / 4;
         float fltSynchroTrameLevel = 0.5f * ((float)intSynchroTimeSamples) * k.level_black;
-        if (fltVal < k.level_synchro_top) m_intSynchroPoints++;
-        else if (fltVal > k.level_black) m_intSynchroPoints = 0;
+        tick++;
+        if (fltVal < k.level_synchro_top) { if (run_start < 0) run_start = tick; m_intSynchroPoints++; }
+        else if (fltVal > k.level_black) { m_intSynchroPoints = 0; run_start = -1; }
         m_blnSynchroDetected = (m_intSynchroPoints == m_intNumberSamplePerTop);
         bool blnNewLine = false;
         if (m_blnSynchroDetected) {
+            if (last_detection >= 0) {
+                const int64_t gap = tick - last_detection;
+                if (gap == 1) geo[GEO_DETECT_HELD]++;
+                else if (gap <= 63) geo[GEO_DETECT_TWICE_NEAR]++;
+            }
+            if (run_start >= 0 && tick - run_start >= 64) geo[GEO_POINTS_FROM_FAR]++;
+            last_detection = tick;
+            if (m_intColIndex == m_intNumberSamplePerLine / 2) geo[GEO_DETECT_AT_HALF]++;
             if (m_intColIndex < m_intNumberSamplePerLine / 2) hits[ATV_HIT_MINUS150]++;
             m_intAvgColIndex = m_intSampleIndex - m_intColIndex - (m_intColIndex < m_intNumberSamplePerLine / 2 ? 150 : 0);
             m_intSampleIndex = 0;
@@ -169,6 +200,8 @@ struct Ato {
             if (k.hsync && (m_intLineIndex == 0)) {
                 hits[ATV_HIT_HCORR_CLASSIC]++;
                 m_intColIndex = m_intNumberSamplePerTop + m_intAvgColIndex / 4;
+                if (m_intColIndex < 0) geo[GEO_COL_NEGATIVE]++;
+                else if (m_intColIndex >= m_intNumberSamplePerLine + m_intNumberSamplePerTop) geo[GEO_COL_PAST_LINE]++;
             } else {
                 m_intColIndex = m_intNumberSamplePerTop;
             }
@@ -179,6 +212,7 @@ struct Ato {
             m_fltAmpLineAverage = 0.0f;
             m_intRowIndex += m_interleaved ? 2 : 1;
             if (m_intRowIndex < m_intNumberOfLines) selectRow(m_intRowIndex - m_intNumberOfSyncLines);
+            else geo[GEO_ROW_STAYS]++;
             m_intLineIndex++;
             renders_in_line = 0;
         }
@@ -186,7 +220,14 @@ struct Ato {
         m_intColIndex++;
         if (k.vsync && (m_intLineIndex < m_intNumberOfLines)) {
             if (m_intColIndex >= intSynchroTimeSamples) {
+                if (m_fltAmpLineAverage != m_fltAmpLineAverage) geo[GEO_NAN_AT_CHECK]++;
                 if (m_fltAmpLineAverage <= fltSynchroTrameLevel) {
+                    if (m_fltAmpLineAverage == fltSynchroTrameLevel) geo[GEO_VSYNC_TIE]++;
+                    if (m_blnVerticalSynchroDetected) geo[GEO_VSYNC_AGAIN]++;
+                    else {
+                        if (m_intColIndex == intSynchroTimeSamples) geo[GEO_VSYNC_FIRST_COL]++;
+                        if (m_intColIndex >= m_intNumberSamplePerLine + (k.hsync ? m_intNumberSamplePerTop : 0)) geo[GEO_VSYNC_LAST_COL]++;
+                    }
                     m_fltAmpLineAverage = 0.0f;
                     if (!m_blnVerticalSynchroDetected) {
                         m_blnVerticalSynchroDetected = true;
@@ -209,6 +250,7 @@ struct Ato {
         } else {
             if (m_intLineIndex >= m_intNumberOfLines / 2) {
                 hits[ATV_HIT_HALF_FRAME]++;
+                if (k.vsync) geo[GEO_LINE_PAST_FRAME]++;
                 if (m_intImageIndex % 2 == 1) {
                     renderImage();
                     if (k.modulation == ATV_AM) { hits[ATV_HIT_HALF_FRAME_AM]++; amUpdate(); }
@@ -400,6 +442,8 @@ void* ato_create(const sdrx_atv_cfg* cfg)
     h->at = 0;
     memset(h->hits, 0, sizeof h->hits);
     h->renders_in_line = h->max_renders_in_line = 0;
+    memset(h->geo, 0, sizeof h->geo);
+    h->tick = 0; h->last_detection = -1; h->run_start = -1;
     return h;
 }
 
@@ -509,6 +553,12 @@ void ato_hits(void* p, int64_t* out)
     Ato* h = (Ato*)p;
     memcpy(out, h->hits, sizeof h->hits);
     out[ATV_N_HITS] = h->max_renders_in_line;
+}
+
+void ato_geo(void* p, int64_t* out)
+{
+    Ato* h = (Ato*)p;
+    memcpy(out, h->geo, sizeof h->geo);
 }
 
 } // extern "C"

@@ -4,7 +4,11 @@ compiled where they lie, linked against QtCore) and records tests/golden/atv_gol
 stand-ins of tests/golden/atv_stubs/ come first on the include path and take the place of TVScreen, DeviceSourceAPI,
 ThreadedBasebandSampleSink, DownChannelizer and of headers ATVDemod includes without using them.
 
-    python tests/golden/make_golden_atv.py [--ref /root/reference]
+    python tests/golden/make_golden_atv.py [--ref /root/reference] [--random]
+
+--random records tests/golden/atv_random_golden.npz instead: the shape cases, the cut streams fed whole and the 100 random cases of
+tests/atv_cases.py (golden_random_cases()), digests only -- per case the sha256 of the input and the design integers, per feed the
+render events, the state's words and the sha256 of each stored frame, of the screen and of the scope stream, in arrays shared by all cases.
 
 Per case the fixture keeps the sha256 of the input (the generator is tests/atv_cases.py's, seeded), the design integers, and per
 feed the render events, the stored frames, the screen, the scope stream and the state's 28 words; frames, screens and scope as
@@ -118,15 +122,57 @@ def pack(case: dict, r: dict, x: np.ndarray) -> dict:
     return a
 
 
+def digest(a: np.ndarray) -> np.ndarray:
+    """sha256 as 32 bytes"""
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+def pack_digests(runs: list) -> dict:
+    """what the random fixture keeps of (case, feeds, design, input) tuples, every case's feeds end to end in arrays shared by all:
+    no image, no stream.  tests/atv_cases.py's load_random_golden() takes it apart again; the oracle's results pack the same way"""
+    feeds = [f for _, fs, _, _ in runs for f in fs]
+    frames = [fr for f in feeds for fr in f["frames"]]
+    return {"names": np.array([c["name"] for c, _, _, _ in runs]), "in_sha256": np.array([digest(x) for _, _, _, x in runs], np.uint8),
+            "design": np.array([d for _, _, d, _ in runs], np.int32), "feeds": np.array([len(fs) for _, fs, _, _ in runs], np.int32),
+            "event_counts": np.array([f["events"].size for f in feeds], np.int32),
+            "events": np.concatenate([f["events"] for f in feeds]).astype(np.int32),
+            "state": np.array([f["state"] for f in feeds], np.int64).astype(np.uint32),
+            "frame_counts": np.array([len(f["frames"]) for f in feeds], np.int32),
+            "frames_sha256": np.array([digest(fr) for fr in frames], np.uint8).reshape(len(frames), 32),
+            "screens_sha256": np.array([digest(f["screen"]) for f in feeds], np.uint8),
+            "scope_sha256": np.array([digest(f["scope"]) for f in feeds], np.uint8)}
+
+
+def record_random(exe: str, out: str):
+    from tests import atv_cases as ac
+    cases = ac.golden_random_cases()
+    ac.assert_random_shares(ac.random_cases())
+    runs, renders = [], 0
+    for c in cases:
+        x = ac.inputs(c)
+        r = record(exe, c, x)
+        runs.append((c, r["feeds"], r["design"], x))
+        renders += sum(f["events"].size for f in r["feeds"])
+        print(f"{c['name']}: design {r['design']}, renders per feed {[f['events'].size for f in r['feeds']]}")
+    assert renders >= len(cases)
+    np.savez_compressed(out, **pack_digests(runs))
+    print(f"wrote {out}: {len(cases)} cases, {os.path.getsize(out)} bytes")
+
+
 def main():
     from tests import atv_cases as ac
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--out", default=ac.GOLDEN)
+    ap.add_argument("--random", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not available(args.ref):
         sys.exit("reference tree, moc, Qt headers or QtCore not found")
     exe = build_recorder(args.ref)
+    if args.random:
+        return record_random(exe, args.out or ac.RANDOM_GOLDEN)
+    args.out = args.out or ac.GOLDEN
     arrays, total = {}, np.zeros(6, np.int64)
     renders, over_cap = 0, False
     for c in ac.CASES:
