@@ -6,7 +6,12 @@ subcarrier: BPSK on the pilot's third harmonic at phase `rds_phi`, deviation `rd
 blocks each, repeated for the length of the signal) with checkwords by the polynomial 0x5B9 plus the offset words,
 differentially coded, as biphase symbols at 1187.5 Hz.  `lead` samples of unmodulated carrier come first.
 
-Also the synthetic bit streams of the frameSync fixtures (framesync_streams) and the order of the recorded state words."""
+Also the synthetic bit streams of the frameSync fixtures (framesync_streams) and the order of the recorded state words.
+
+random_cases() is the draw of 40 configurations with RDS on that tests/test_bfm_rds_random_gpu.py runs against the recording
+tests/golden/bfm_rds_random_golden.npz (pack_random() is its layout, load_random_golden() reads it back in golden_case()'s).  Its
+bursting cases keep the named case's rf of 12500, so that the squelch can open inside a short case; every other case has rf of at
+least 180000 where the rate allows."""
 from __future__ import annotations
 
 import os
@@ -176,6 +181,143 @@ AUDIO_CASE = "stereo_250k"          # the one case whose audio and sink stream a
 
 def inputs(case: dict) -> np.ndarray:
     return signal(case["sig"], case["n"], case["cfg"]["in_rate"], case["seed"])
+
+
+# ---------------------------------------------------------------- random configurations, RDS on in every one
+RANDOM_SEED = 20261101
+RANDOM_GOLDEN = os.path.join(ROOT, "tests", "golden", "bfm_rds_random_golden.npz")    # tests/golden/make_golden_bfm_rds.py --random
+#: RDS steps in_rate / 250000 of 0.384, 0.8, 0.96 (below 1 the schedule is clamped: every input emits), 1, 1.152, 1.536 and 2
+RANDOM_RATES = (96000, 200000, 240000, 250000, 288000, 384000, 500000)
+#: the long cases (every LONG_EVERY-th draw): 0.42 s of their rate, past the 800th biphase call, where the reading frame is chosen
+LONG_EVERY, LONG_AT, LONG_RATES = 10, 3, (200000, 240000, 250000, 288000, 384000)
+ZERO_AT, NOISE_AT = 7, 19                           # the draws that are a `zero` and a `noise_full` signal
+#: draw indices left out because the recording of the reference had a sample whose mixer product rds_mix.hpp's enclosure does not
+#: pin (tests/golden/make_golden_bfm_rds.py --random names them); the next index takes the place
+RANDOM_SKIP = ()
+WIDE_N = 12000                                      # the wide GPU bank cycles over the cases up to this length
+
+
+def random_case(rng, j: int) -> dict:
+    """draw j; every quantity is drawn for every case, used or not, so the order of the rng calls ahead of the splits is fixed"""
+    long = j % LONG_EVERY == LONG_AT
+    in_rate = int(rng.choice(LONG_RATES if long else RANDOM_RATES))
+    audio = int(rng.choice([48000, 44100]))
+    rf = bc._f32(min(float(rng.choice([180000.0, 200000.0, 220000.0])), 0.9 * in_rate))
+    stereo, lsb = int(rng.random() < 0.7), int(rng.random() < 0.3)
+    f0 = float(rng.integers(-in_rate // 16, in_rate // 16))
+    sig = {"kind": "mpx", "f0": f0, "rds": float(rng.integers(300, 5001)), "rds_phi": float(rng.uniform(0.0, 2 * np.pi)),
+           "lead": int(rng.integers(0, 4001)), "sum": float(rng.integers(1000, 30001)), "diff": float(rng.integers(0, 15001)),
+           "fs": float(rng.integers(100, 5000)), "fd": float(rng.integers(100, 5000)), "noise": float(rng.integers(0, 50)),
+           "amp": float(rng.choice([3000.0, 8000.0, 20000.0]))}
+    n = int(rng.integers(3000, 30001))
+    bursts, lo = rng.random() < 0.2, float(rng.integers(1, 200))
+    runs = [int(v) for v in rng.integers(300, 4000, size=8)]
+    sq, feeds, extra = -60.0, int(rng.integers(2, 5)), rng.random()
+    if long:
+        n = int((0.42 + 0.02 * extra) * in_rate)
+        sig.update(sum=8000.0, diff=4000.0, amp=8000.0, noise=5.0, rds=max(sig["rds"], 2000.0), lead=min(sig["lead"], n // 8))
+        splits = sorted(int(v) for v in rng.integers(1, n, size=feeds - 1))
+        splits = [b - a for a, b in zip([0] + splits, splits + [n])]
+    else:
+        sig["lead"] = min(sig["lead"], n // 2)
+        if j == ZERO_AT or j == NOISE_AT:
+            sig = {"kind": "zero" if j == ZERO_AT else "noise_full"}
+        elif bursts:                                            # the mixer runs on demod = 0 while the squelch is closed
+            rf, sq = 12500.0, -30.0
+            sig.update(hi=12000.0, lo=lo, noise=min(sig["noise"], 5.0), runs=runs, sum=2000.0, diff=1000.0, pilot=750.0, rds=min(sig["rds"], 600.0))
+        splits = bc._random_splits(rng, n)
+    cfg = bc._cfg(in_rate, audio, nco_freq=-int(f0), rf=rf, sq=sq, stereo=stereo, lsb=lsb)
+    return {"name": f"rds_random{j}", "cfg": cfg, "sig": sig, "n": n, "seed": 5000 + j, "splits": splits, "rds": 1, "long": long}
+
+
+def random_draws(count: int = 40, skip=None):
+    """(kept cases, skipped cases): draws in order from one generator, the indices of `skip` (RANDOM_SKIP) set aside, until `count`
+    are kept"""
+    skip = RANDOM_SKIP if skip is None else skip
+    rng = np.random.default_rng(RANDOM_SEED)
+    kept, left, j = [], [], 0
+    while len(kept) < count:
+        (left if j in skip else kept).append(random_case(rng, j))
+        j += 1
+    return kept, left
+
+
+def random_cases(count: int = 40) -> list[dict]:
+    return random_draws(count)[0]
+
+
+def rds_step(case: dict) -> float:
+    return case["cfg"]["in_rate"] / 250000.0
+
+
+def _edge(b: np.ndarray, tail: bool) -> np.ndarray:
+    out = np.zeros(BB_EDGE, np.float32)
+    e = min(BB_EDGE, b.size)
+    if e:
+        out[:e] = b[-e:] if tail else b[:e]
+    return out
+
+
+def pack_random(cases, results) -> dict:
+    """The random draw's fixture from the recorder's results: per case the feeds and the input's sha256; per feed the counts of bits,
+    groups and RDS samples, subcarr_bb's sha256 and its first and last BB_EDGE values (the tail's last value last), the report and
+    the state words; all bits and all groups on end"""
+    feeds = [(c, r, i) for c, r in zip(cases, results) for i in range(len(c["splits"]))]
+    sha32 = lambda b: np.frombuffer(bytes.fromhex(sha_f32(b)), np.uint8)
+    return {"names": np.array([c["name"] for c in cases]), "feeds": np.array([len(c["splits"]) for c in cases], np.int32),
+            "in_sha256": np.array([np.frombuffer(bytes.fromhex(bc.sha(inputs(c))), np.uint8) for c in cases], np.uint8).reshape(-1, 32),
+            "bit_counts": np.array([r["bits"][i].size for _, r, i in feeds], np.int64),
+            "group_counts": np.array([r["groups"][i].shape[0] for _, r, i in feeds], np.int64),
+            "rds_counts": np.array([r["bb"][i].size for _, r, i in feeds], np.int64),
+            "bits": np.concatenate([r["bits"][i] for _, r, i in feeds]).astype(np.uint8),
+            "groups": np.concatenate([r["groups"][i].reshape(-1, 4) for _, r, i in feeds]).astype(np.uint16).reshape(-1, 4),
+            "bb_sha256": np.array([sha32(r["bb"][i]) for _, r, i in feeds], np.uint8).reshape(-1, 32),
+            "bb_head": np.array([_edge(r["bb"][i], False) for _, r, i in feeds], np.float32).reshape(-1, BB_EDGE),
+            "bb_tail": np.array([_edge(r["bb"][i], True) for _, r, i in feeds], np.float32).reshape(-1, BB_EDGE),
+            "report": np.array([r["report"][i] for _, r, i in feeds], np.uint32).reshape(-1, 5),
+            "state": np.array([r["state"][i] for _, r, i in feeds], np.uint64).reshape(-1, len(STATE_FIELDS))}
+
+
+def load_random_golden(path: str = None) -> dict:
+    """bfm_rds_random_golden.npz by case name, each entry in golden_case()'s layout (bb is None: digests and edges)"""
+    g = np.load(path or RANDOM_GOLDEN)
+    out, f0, b0, g0 = {}, 0, 0, 0
+    for k, name in enumerate(g["names"].tolist()):
+        f1 = f0 + int(g["feeds"][k])
+        nb, ng = g["bit_counts"][f0:f1], g["group_counts"][f0:f1]
+        b1, g1 = b0 + int(nb.sum()), g0 + int(ng.sum())
+        e = [min(BB_EDGE, int(v)) for v in g["rds_counts"][f0:f1]]
+        out[name] = {"bits": np.split(g["bits"][b0:b1], np.cumsum(nb)[:-1]), "groups": np.split(g["groups"][g0:g1], np.cumsum(ng)[:-1]),
+                     "n_rds": [int(v) for v in g["rds_counts"][f0:f1]], "report": g["report"][f0:f1], "state": g["state"][f0:f1],
+                     "in_sha": bytes(g["in_sha256"][k]).hex(), "bb": None, "bb_sha": [bytes(v).hex() for v in g["bb_sha256"][f0:f1]],
+                     "bb_head": g["bb_head"][f0:f1],
+                     # golden_case()'s tails hold the last e values at their end: [-e:] is read
+                     "bb_tail": np.array([np.concatenate([np.zeros(BB_EDGE - e[i], np.float32), t[:e[i]]]) for i, t in enumerate(g["bb_tail"][f0:f1])], np.float32).reshape(-1, BB_EDGE)}
+        f0, b0, g0 = f1, b1, g1
+    out["host"], out["unsure_skipped"] = str(g["host"]), int(g["unsure_skipped"])
+    return out
+
+
+def random_shares(cases, gold: dict) -> dict:
+    """the counts assert_random_shares() puts floors under, from the fixture (load_random_golden())"""
+    rf = STATE_FIELDS.index("reading_frame")
+    nbits = {c["name"]: sum(b.size for b in gold[c["name"]]["bits"]) for c in cases}
+    flipped = {c["name"]: int(gold[c["name"]]["state"][-1][rf]) == 1 for c in cases}
+    # biphase emits a bit on every other call and its counter goes round after 800: more than 400 bits, or the other frame
+    past = [c for c in cases if c["long"] and (flipped[c["name"]] or nbits[c["name"]] > 400)]
+    return {"cases": len(cases), "rates": sorted({c["cfg"]["in_rate"] for c in cases}), "clamped": sum(rds_step(c) < 1 for c in cases),
+            "with_bits": sum(v > 0 for v in nbits.values()), "long": sum(c["long"] for c in cases), "long_past_800": len(past),
+            "flipped": sum(flipped.values()), "mono": sum(not c["cfg"]["stereo"] for c in cases), "bursts": sum("runs" in c["sig"] for c in cases),
+            "kinds": sorted({c["sig"]["kind"] for c in cases}), "samples": sum(c["n"] for c in cases)}
+
+
+def assert_random_shares(cases, g) -> dict:
+    s = random_shares(cases, g)
+    assert s["cases"] == 40 and s["rates"] == sorted(RANDOM_RATES) and s["clamped"] >= 10 and s["with_bits"] >= 25, s
+    assert s["long"] == 4 and s["long_past_800"] >= 3 and s["mono"] >= 8 and s["kinds"] == ["mpx", "noise_full", "zero"], s
+    assert all(3000 <= c["n"] <= 30000 and len(c["splits"]) <= bc.MAX_FEEDS or c["long"] and 2 <= len(c["splits"]) <= 4 for c in cases)
+    assert all(c["n"] >= 0.42 * c["cfg"]["in_rate"] for c in cases if c["long"])
+    return s
 
 
 # ---------------------------------------------------------------- frameSync streams

@@ -3,11 +3,16 @@ and LowPassFilterRC (sdrbase/dsp/*.cpp compiled where they lie; Qt headers of th
 tests/golden/bfm_golden.npz for the cases of tests/bfm_cases.py.
 
     python tests/golden/make_golden_bfm.py [--ref /root/reference]
+    python tests/golden/make_golden_bfm.py --random      records tests/golden/bfm_random_golden.npz for bfm_cases.random_cases()
 
 Per case the fixture keeps the inputs (their sha256 beyond bfm_cases.IN_FULL samples), the l, r pairs of every feed, the real
 parts of the sink stream's Samples (per feed their sha256 beyond bfm_cases.SINK_FULL samples), and after every feed m_magsqSum,
 m_magsqPeak, m_magsqCount, m_squelchState, locked(), m_lock_cnt and the bits of m_pilot_level, m_freq, m_phase and both m_y1.
-`host` notes the libm the recorder ran on: the pilot loop calls its sinf and cosf and feeds back what they return."""
+`host` notes the libm the recorder ran on: the pilot loop calls its sinf and cosf and feeds back what they return.
+
+The random draw's fixture keeps digests only (bfm_cases.pack_digests): per feed the lengths and sha256 of audio and sink stream and
+the same state words, m_magsqSum and m_magsqPeak as double bits; inputs as their sha256.  It is written with fixed zip timestamps:
+the same recording gives the same bytes."""
 from __future__ import annotations
 
 import argparse
@@ -75,15 +80,45 @@ def record(exe: str, cfg: dict, iq: np.ndarray, splits) -> dict:
     return {"audio": audio, "sink": sink, "states": states}
 
 
+def save_npz(path: str, arrays: dict):
+    """np.savez_compressed with the members' timestamps fixed: the bytes depend on the arrays alone"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            with z.open(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
+                f.compress_type = zipfile.ZIP_DEFLATED
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def record_case(exe: str, case: dict, iq: np.ndarray) -> dict:
+    """record() in bfm_cases.run_oracle's layout"""
+    from tests import bfm_cases as bc
+    r = record(exe, case["cfg"], iq, case["splits"])
+    return {"audio": r["audio"], "sink": r["sink"], "states": bc.recorded_states(r["states"])}
+
+
+def record_random(exe: str, out: str):
+    from tests import bfm_cases as bc
+    cases = bc.random_cases()
+    arrays = bc.pack_digests(cases, [record_case(exe, c, bc.inputs(c)) for c in cases])
+    arrays["host"] = np.array(host_note())
+    save_npz(out, arrays)
+    print(f"wrote {out}: {len(cases)} cases, {int(arrays['feeds'].sum())} feeds on {host_note()}, {os.path.getsize(out)} bytes")
+
+
 def main():
     from tests import bfm_cases as bc
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--out", default=os.path.join(HERE, "bfm_golden.npz"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--random", action="store_true")
     args = ap.parse_args()
     if not available(args.ref):
         sys.exit("reference tree or Qt headers not found")
     exe = build_recorder(args.ref)
+    if args.random:
+        return record_random(exe, args.out or bc.RANDOM_GOLDEN)
+    args.out = args.out or os.path.join(HERE, "bfm_golden.npz")
     arrays = {"host": np.array(host_note())}
     for c in bc.CASES:
         x = bc.inputs(c)

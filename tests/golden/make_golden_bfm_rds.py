@@ -4,12 +4,18 @@ tests/golden/bfm_rds_golden.npz for the cases of tests/bfm_rds_cases.py and its 
 
     python tests/golden/make_golden_bfm_rds.py [--ref /root/reference]
     python tests/golden/make_golden_bfm_rds.py --search      looks for the long case's phase, level, lead and cuts (prints them)
+    python tests/golden/make_golden_bfm_rds.py --random      records tests/golden/bfm_rds_random_golden.npz for bfm_rds_cases.random_cases()
 
 Per case and feed the fixture keeps the bits, the groups, the RDS sample count, the report and the state words
 (bfm_rds_cases.STATE_FIELDS); subcarr_bb in full for cases up to BB_FULL samples, beyond that per feed its sha256 and the first
 and last BB_EDGE values; audio and sink stream for AUDIO_CASE.  Inputs are kept as their sha256: the generator is portable.
 The recorder also runs rds_mix.hpp on its own demod and phase: no case may have an unsure sample, and rds_mix's product must
-equal the host's on every sample (asserted here).  `host` notes the libm the recorder ran on."""
+equal the host's on every sample (asserted here).  `host` notes the libm the recorder ran on.
+
+The random draw's fixture keeps every case the long cases' way (subcarr_bb as sha256, head and tail).  A draw whose recording has an
+unsure sample is not recorded: the run stops and names the index for bfm_rds_cases.RANDOM_SKIP.  The indices already there are
+recorded too, to see that each does have such a sample; `unsure_skipped` is their number.  Fixed zip timestamps: the same recording
+gives the same bytes."""
 from __future__ import annotations
 
 import argparse
@@ -135,19 +141,66 @@ def search(exe: str):
     print("nothing found")
 
 
+def case_arrays(arrays: dict, c: dict, x: np.ndarray, r: dict, bb_full: bool):
+    """one case's bits, groups, RDS sample counts, subcarr_bb (in full or as digests and edges), report and state words"""
+    from tests import bfm_rds_cases as rc
+    from tests import bfm_cases as bc
+    name = c["name"]
+    arrays[f"{name}/in_sha256"] = np.array(bc.sha(x))
+    arrays[f"{name}/bit_counts"] = np.array([b.size for b in r["bits"]], np.int64)
+    arrays[f"{name}/bits"] = np.concatenate(r["bits"])
+    arrays[f"{name}/group_counts"] = np.array([g.shape[0] for g in r["groups"]], np.int64)
+    arrays[f"{name}/groups"] = np.concatenate(r["groups"]).reshape(-1, 4)
+    arrays[f"{name}/rds_counts"] = np.array([b.size for b in r["bb"]], np.int64)
+    if bb_full:
+        arrays[f"{name}/bb"] = np.concatenate(r["bb"])
+    else:
+        arrays[f"{name}/bb_sha256"] = np.array([rc.sha_f32(b) for b in r["bb"]])
+        arrays[f"{name}/bb_head"] = np.array([np.resize(b[:rc.BB_EDGE], rc.BB_EDGE) if b.size else np.zeros(rc.BB_EDGE, np.float32) for b in r["bb"]], np.float32)
+        arrays[f"{name}/bb_tail"] = np.array([np.resize(b[-rc.BB_EDGE:], rc.BB_EDGE) if b.size else np.zeros(rc.BB_EDGE, np.float32) for b in r["bb"]], np.float32)
+    arrays[f"{name}/report"] = np.array(r["report"], np.uint32).reshape(-1, 5)
+    arrays[f"{name}/state"] = np.array(r["state"], np.uint64).reshape(-1, len(rc.STATE_FIELDS))
+
+
+def record_random(exe: str, out: str):
+    from tests import bfm_rds_cases as rc
+    kept, left = rc.random_draws()
+    for c in left:
+        r = record(exe, c["cfg"], c["rds"], rc.inputs(c), c["splits"])
+        assert sum(r["unsure"]) > 0, (c["name"], "is in RANDOM_SKIP and has no unsure sample")
+    results = []
+    for c in kept:
+        r = record(exe, c["cfg"], c["rds"], rc.inputs(c), c["splits"])
+        if sum(r["unsure"]):
+            sys.exit(f"{c['name']} has {sum(r['unsure'])} unsure sample(s): add its index to bfm_rds_cases.RANDOM_SKIP and record again")
+        assert sum(r["differs"]) == 0, (c["name"], "rds_mix differs from the host's product", r["differs"])
+        results.append(r)
+        print(f"{c['name']}: {c['cfg']['in_rate']} S/s, {len(c['splits'])} feeds, rds samples {sum(b.size for b in r['bb'])}, "
+              f"bits {sum(b.size for b in r['bits'])}, groups {sum(g.shape[0] for g in r['groups'])}", flush=True)
+    arrays = rc.pack_random(kept, results)
+    arrays.update(host=np.array(mg.host_note()), state_fields=np.array(rc.STATE_FIELDS), unsure_skipped=np.array(len(left), np.int64))
+    mg.save_npz(out, arrays)
+    print(f"wrote {out}: {len(kept)} cases, {len(left)} skipped, {os.path.getsize(out)} bytes")
+    print(rc.random_shares(kept, rc.load_random_golden(out)))
+
+
 def main():
     from tests import bfm_rds_cases as rc
     from tests import bfm_cases as bc
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--out", default=rc.GOLDEN)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--search", action="store_true")
+    ap.add_argument("--random", action="store_true")
     args = ap.parse_args()
     if not available(args.ref):
         sys.exit("reference tree, Qt headers or QtCore not found")
     exe = build_recorder(args.ref)
     if args.search:
         return search(exe)
+    if args.random:
+        return record_random(exe, args.out or rc.RANDOM_GOLDEN)
+    args.out = args.out or rc.GOLDEN
     arrays = {"host": np.array(mg.host_note()), "state_fields": np.array(rc.STATE_FIELDS)}
     sync_col = rc.STATE_FIELDS.index("sync")
     for c in rc.CASES:
@@ -156,20 +209,7 @@ def main():
         name = c["name"]
         assert sum(r["unsure"]) == 0, (name, "unsure samples: pick another seed", r["unsure"])
         assert sum(r["differs"]) == 0, (name, "rds_mix differs from the host's product", r["differs"])
-        arrays[f"{name}/in_sha256"] = np.array(bc.sha(x))
-        arrays[f"{name}/bit_counts"] = np.array([b.size for b in r["bits"]], np.int64)
-        arrays[f"{name}/bits"] = np.concatenate(r["bits"])
-        arrays[f"{name}/group_counts"] = np.array([g.shape[0] for g in r["groups"]], np.int64)
-        arrays[f"{name}/groups"] = np.concatenate(r["groups"]).reshape(-1, 4)
-        arrays[f"{name}/rds_counts"] = np.array([b.size for b in r["bb"]], np.int64)
-        if c["n"] <= rc.BB_FULL:
-            arrays[f"{name}/bb"] = np.concatenate(r["bb"])
-        else:
-            arrays[f"{name}/bb_sha256"] = np.array([rc.sha_f32(b) for b in r["bb"]])
-            arrays[f"{name}/bb_head"] = np.array([np.resize(b[:rc.BB_EDGE], rc.BB_EDGE) if b.size else np.zeros(rc.BB_EDGE, np.float32) for b in r["bb"]], np.float32)
-            arrays[f"{name}/bb_tail"] = np.array([np.resize(b[-rc.BB_EDGE:], rc.BB_EDGE) if b.size else np.zeros(rc.BB_EDGE, np.float32) for b in r["bb"]], np.float32)
-        arrays[f"{name}/report"] = np.array(r["report"], np.uint32).reshape(-1, 5)
-        arrays[f"{name}/state"] = np.array(r["state"], np.uint64).reshape(-1, len(rc.STATE_FIELDS))
+        case_arrays(arrays, c, x, r, bb_full=c["n"] <= rc.BB_FULL)
         if name == rc.CR_CASE:                       # what RDSDemod::process was given: the CPU test drives bfm_rds.hpp with it
             arrays[f"{name}/cr"] = np.concatenate(r["cr"])
         if name == rc.AUDIO_CASE:

@@ -1,10 +1,19 @@
 """CPU: tests/bfm_oracle.c against the recording of the reference's own classes (tests/golden/bfm_golden.npz, made by
 tests/golden/make_golden_bfm.py): audio, sink stream and state after every feed, bit for bit; the generator still gives the
-recorded inputs; the case set drives the pilot loop through every branch of its step."""
+recorded inputs; the case set drives the pilot loop through every branch of its step.
+
+The 100 random configurations of bfm_cases.random_cases() (audio rates other than 48000, steps at and just above 1, both resampler
+schedules; tests/test_bfm_random_gpu.py runs them on the GPU): the oracle packed as the recorder's results were against the digests
+of tests/golden/bfm_random_golden.npz anywhere, and feed by feed in full against the rebuilt recorder where the reference is (`ref`)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from tests import bfm_cases as bc
+
+REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
@@ -85,3 +94,68 @@ def test_what_the_named_cases_are_there_for(gold, runs):
 def test_fixture_size(gold):
     import os
     assert os.path.getsize(bc.GOLDEN) <= 547302
+
+
+# ---------------------------------------------------------------- the random draw
+RCASES = bc.random_cases()
+RIDS = [c["name"] for c in RCASES]
+
+
+@pytest.fixture(scope="module")
+def rgold():
+    return bc.load_random_golden()
+
+
+@pytest.fixture(scope="module")
+def rruns(oracle):
+    """every random case through the oracle with its own cuts, once"""
+    return [bc.run_oracle(oracle, c) for c in RCASES]
+
+
+def test_the_random_recording_has_every_case(rgold):
+    assert [k for k in rgold if k != "host"] == RIDS
+    assert rgold["host"].startswith("glibc 2.") and rgold["host"].endswith("fma=1")
+    assert os.path.getsize(bc.RANDOM_GOLDEN) < 547302
+
+
+@pytest.mark.parametrize("i", range(len(RCASES)), ids=RIDS)
+def test_oracle_equals_the_random_recording(rruns, rgold, i):
+    """lengths and digests of audio and sink stream and every state word after every feed, m_magsqSum to the bit: the oracle's
+    results packed the way the recorder's were"""
+    case, want = RCASES[i], rgold[RCASES[i]["name"]]
+    mine = bc.pack_digests([case], [rruns[i]])
+    for key in bc.PER_CASE + bc.PER_FEED:
+        assert mine[key].shape == want[key].shape and np.array_equal(mine[key], want[key]), (case["name"], key, case)
+
+
+def test_the_random_draw_keeps_its_shares(rruns):
+    s = bc.assert_random_shares(RCASES, rruns)
+    print(s)
+    short = [c for c in RCASES if c["n"] <= bc.WIDE_N]
+    assert len(short) >= 40 and {(bc.is_dyadic(c), c["cfg"]["stereo"]) for c in short} == {(False, 0), (False, 1), (True, 0), (True, 1)}
+    assert {(c["cfg"]["in_rate"], c["cfg"]["audio_rate"]) for c in RCASES} == set(bc.RANDOM_RATES)
+    assert {c["sig"]["kind"] for c in RCASES} == {"mpx", "noise_full", "zero"}
+    assert {c["cfg"][k] for c in RCASES for k in ("af",)} == {3000.0, 15000.0, 20000.0} and {c["cfg"]["vol"] for c in RCASES} == {0.5, 2.0, 10.0, 400.0}
+    assert any(c["sig"].get("amp", 0) > 32767 for c in RCASES) and sum("runs" in c["sig"] for c in RCASES) >= 20
+    assert sum("p_on" in c["sig"] for c in RCASES) >= 15
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "sdrbase", "dsp")), reason="no reference tree here")
+def test_oracle_equals_the_rebuilt_recorder_on_the_random_draw(rruns):
+    """what proves tests/bfm_oracle.c at audio rates other than 48000: every l, r pair, every Sample of the sink stream and the state
+    after every feed of every random case against the reference's own classes"""
+    sys.path.insert(0, os.path.join(bc.ROOT, "tests", "golden"))
+    import make_golden_bfm as mg
+    if not mg.available(REF):
+        pytest.skip("Qt headers not available")
+    exe = mg.build_recorder(REF)
+    for case, got in zip(RCASES, rruns):
+        want = mg.record_case(exe, case, bc.inputs(case))
+        assert len(got["audio"]) == len(want["audio"]) == len(case["splits"]), case
+        for i in range(len(case["splits"])):
+            assert np.array_equal(got["audio"][i], want["audio"][i]), (case, "audio of feed", i)
+            assert np.array_equal(got["sink"][i], want["sink"][i]), (case, "sink stream of feed", i)
+            g, w = got["states"][i], want["states"][i]
+            assert all(g[k] == w[k] for k in ("sum", "peak", "count", "sq_state", "locked", "lock_cnt")), (case, "feed", i, g, w)
+            assert np.array_equal(g["bits"], w["bits"]), (case, "feed", i, g["bits"], w["bits"])

@@ -4,13 +4,16 @@ driven with what the reference's own RDSDemod and RDSDecoder were given (tests/g
   - RDSDemod::process + frameSync on the recorded resampler output of one case: subcarr_bb of every sample, bits, report and
     the whole state equal the recording bit for bit;
   - frameSync on the long case's recorded bits: the groups of the reference's own run through NO_SYNC, presync and sync;
-  - the probe: every branch of the clock recovery, of biphase and of frameSync is taken over these inputs."""
+  - the probe: every branch of the clock recovery, of biphase and of frameSync is taken over these inputs.
+Also the random draw of bfm_rds_cases.random_cases() as tests/golden/bfm_rds_random_golden.npz recorded it (tests/test_bfm_rds_random_gpu.py
+runs it on the GPU): the generator still gives the recorded inputs, the draw keeps its shares, at most two draws were set aside."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import bfm_cases as bc
 from tests import bfm_rds_cases as rc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,3 +134,43 @@ def test_every_branch_was_taken(exe, gold, tmp_path):
     print(total)
     never = [k for k, v in total.items() if v == 0]
     assert not never and len(total) == 24, never
+
+
+# ---------------------------------------------------------------- the random draw
+@pytest.fixture(scope="module")
+def rgold():
+    return rc.load_random_golden()
+
+
+def test_the_random_recording_has_every_case_and_its_inputs(rgold):
+    cases = rc.random_cases()
+    assert [k for k in rgold if k not in ("host", "unsure_skipped")] == [c["name"] for c in cases]
+    assert rgold["host"].startswith("glibc 2.") and rgold["host"].endswith("fma=1")
+    assert os.path.getsize(rc.RANDOM_GOLDEN) < 547302
+    for c in cases:
+        want = rgold[c["name"]]
+        assert bc.sha(rc.inputs(c)) == want["in_sha"], c
+        assert len(want["n_rds"]) == len(c["splits"]) == len(want["bits"]) == len(want["groups"]) == len(want["state"]), c
+        assert int(want["state"][-1][rc.STATE_FIELDS.index("numsamples")]) == sum(want["n_rds"]), c
+
+
+def test_the_random_draw_keeps_its_shares(rgold):
+    cases = rc.random_cases()
+    s = rc.assert_random_shares(cases, rgold)
+    print(s)
+    assert all(c["rds"] == 1 and c["cfg"]["audio_rate"] in (48000, 44100) for c in cases) and {c["cfg"]["audio_rate"] for c in cases} == {48000, 44100}
+    assert all(c["cfg"]["rf"] >= min(180000.0, np.float32(0.9 * c["cfg"]["in_rate"])) for c in cases if "runs" not in c["sig"])
+    assert all(300 <= c["sig"]["rds"] <= 5000 and 0 <= c["sig"]["rds_phi"] < 2 * np.pi and 0 <= c["sig"]["lead"] <= 4000 for c in cases if c["sig"]["kind"] == "mpx")
+    # every input emits on the clamped schedule, fewer above it
+    for c in cases:
+        n_rds, blocks = sum(rgold[c["name"]]["n_rds"]), c["n"] // 512 * 512
+        assert n_rds == blocks if rc.rds_step(c) <= 1 else blocks / rc.rds_step(c) - 2 <= n_rds <= blocks / rc.rds_step(c) + 2, (c, n_rds)
+    short = [c for c in cases if c["n"] <= rc.WIDE_N]
+    assert len(short) >= 10 and any(rc.rds_step(c) < 1 for c in short) and any(rc.rds_step(c) > 1 for c in short)
+
+
+def test_at_most_two_draws_were_set_aside(rgold):
+    """a cap, not a measurement: a sample the enclosure of rds_mix.hpp does not pin comes about once in 2^27"""
+    assert len(rc.RANDOM_SKIP) <= 2 and rgold["unsure_skipped"] == len(rc.RANDOM_SKIP)
+    kept, left = rc.random_draws()
+    assert len(kept) == 40 and [c["name"] for c in left] == [f"rds_random{j}" for j in sorted(rc.RANDOM_SKIP)]
