@@ -355,16 +355,17 @@ int64_t sdro_fftfilt_run(sdro_fftfilt* f, int32_t mode, const float* in, int64_t
         gfft_run(&f->g, f->data, 0);
         if (mode == 0) {                                   /* runFilt (:261-283) */
             for (int i = 0; i < f->flen; i++) f->data[i] = c_mul(f->data[i], f->filter[i]);
-        } else if (mode == 1 || mode == 2) {               /* runSSB (:285-325), getDC = true */
-            f->data[0] = c_mul(f->data[0], f->filter[0]);
-            if (mode == 1) for (int i = 1; i < h; i++) { f->data[i] = c_mul(f->data[i], f->filter[i]); f->data[h + i].r = 0; f->data[h + i].i = 0; }
+        } else if (mode == 1 || mode == 2 || mode == 6 || mode == 7) {     /* runSSB (:285-325), getDC = true; 6, 7: false */
+            if (mode >= 6) { f->data[0].r = 0; f->data[0].i = 0; } else f->data[0] = c_mul(f->data[0], f->filter[0]);
+            if (mode == 1 || mode == 6) for (int i = 1; i < h; i++) { f->data[i] = c_mul(f->data[i], f->filter[i]); f->data[h + i].r = 0; f->data[h + i].i = 0; }
             else           for (int i = 1; i < h; i++) { f->data[i].r = 0; f->data[i].i = 0; f->data[h + i] = c_mul(f->data[h + i], f->filter[h + i]); }
         } else if (mode == 4 || mode == 5) {               /* runAsym (:363-402): DC always kept, bin flen2 left as it is */
             f->data[0] = c_mul(f->data[0], f->filter[0]);
             if (mode == 4) for (int i = 1; i < h; i++) { f->data[i] = c_mul(f->data[i], f->filter[i]); f->data[h + i] = c_mul(f->data[h + i], f->filter_opp[h + i]); }
             else           for (int i = 1; i < h; i++) { f->data[i] = c_mul(f->data[i], f->filter_opp[i]); f->data[h + i] = c_mul(f->data[h + i], f->filter[h + i]); }
-        } else {                                           /* runDSB (:327-361), getDC = true */
+        } else {                                           /* runDSB (:327-361), getDC = true; 8: false */
             for (int i = 0; i < h; i++) { f->data[i] = c_mul(f->data[i], f->filter[i]); f->data[h + i] = c_mul(f->data[h + i], f->filter[h + i]); }
+            if (mode == 8) { f->data[0].r = 0; f->data[0].i = 0; }
         }
         gfft_run(&f->g, f->data, 1);
         for (int i = 0; i < h; i++) {

@@ -8,7 +8,8 @@
 // (ssb_rate, ssb_bw) and never redesigned; DSBFilter follows rf_bw and audio_rate, as in the reference.
 //
 //   am_sync_rec <input.bin> <output.bin> [trace.bin]     commands on stdin, one per line:
-//     new in_rate nco_freq audio_rate rf_bw volume squelch_db mute bandpass sync_op ssb_rate ssb_bw      a fresh demodulator
+//     new in_rate nco_freq audio_rate rf_bw volume squelch_db mute bandpass sync_op ssb_rate ssb_bw [pll]    a fresh demodulator; pll 0 (the
+//                                          default is 1) takes the envelope branch with m_volumeAGC, as am_rec.cpp
 //     feed n                               the next n Samples of input.bin (int16 I, Q)
 //     end                                  level accumulators, squelch and loop state
 //     design                               the design products
@@ -50,6 +51,8 @@ struct Demod {
     DoubleBufferFIFO<Real> delayLine;
     MovingAverageUtil<Real, double, 16> movingAverage;
     MagAGC syncAMAGC;
+    SimpleAGC<4800> volumeAGC;
+    bool usePll;
     Bandpass<Real> bandpass;
     Lowpass<std::complex<float> > pllFilt;
     PhaseLockComplex pll;
@@ -66,9 +69,9 @@ struct Demod {
     FILE* traceSb;
 
     Demod(int inRate, int ncoFreq, int audioRateArg, Real rfBw, Real vol, Real squelchDb, bool muted, bool bp, int op, int ssbRate, Real ssbBw,
-          FILE* tr, FILE* trSb) :
+          bool pllOn, FILE* tr, FILE* trSb) :
         volume(vol), audioRate(audioRateArg), squelchCount(0), mute(muted), bandpassEnable(bp), squelchOpen(false), syncOp(op),
-        delayLine(9600), syncAMAGC(12000, 0.1, 1e-2), magsq(0.0), magsqSum(0.0), magsqPeak(0.0), magsqCount(0),
+        delayLine(9600), syncAMAGC(12000, 0.1, 1e-2), volumeAGC(0.003), usePll(pllOn), magsq(0.0), magsqSum(0.0), magsqPeak(0.0), magsqCount(0),
         opens(0), reopenings(0), opensAtReopen(-1), bad(0), largest(0.0), everOpen(false), wasOpen(false), trace(tr), traceSb(trSb)
     {
         // the constructor, at the audio rate and bandwidth of that moment
@@ -92,6 +95,7 @@ struct Demod {
         DSBFilter->create_dsb_filter((2.0f * rfBw) / (float) audioRate);
         pllFilt.create(101, audioRate, 200.0);
         syncAMAGC.resize(audioRate / 4, audioRate / 8, 0.1);
+        volumeAGC.resizeNew(audioRate / 10, 0.003);
         pll.setSampleRate(audioRate);
         squelchLevel = pow(10.0, squelchDb / 10.0);
     }
@@ -116,6 +120,11 @@ struct Demod {
         wasOpen = squelchOpen;
         if (squelchOpen && !mute) {
             Real demod;
+            if (!usePll) {
+                demod = sqrt(delayLine.readBack(audioRate / 20));
+                volumeAGC.feed(demod);
+                demod = (demod - volumeAGC.getValue()) / volumeAGC.getValue();
+            } else {
             std::complex<float> s(re, im);
             s = pllFilt.filter(s);
             pll.feed(s.real(), s.imag());
@@ -139,13 +148,14 @@ struct Demod {
             syncAMBuffIndex = syncAMBuffIndex < 2 * 1024 ? syncAMBuffIndex : 0;
             demod = syncAMBuff[syncAMBuffIndex++] * 4.0f;
             if (trace) { const float t[7] = { re, im, s.real(), s.imag(), pll.getReal(), pll.getImag(), demod }; std::fwrite(t, 4, 7, trace); }
+            opens++;
+            }
             if (bandpassEnable) { demod = bandpass.filter(demod); demod /= 301.0f; }
             Real attack = (squelchCount - 0.05f * audioRate) / (0.05f * audioRate);
             Real v = demod * StepFunctions::smootherstep(attack) * (audioRate / 24) * volume;
             if (!(std::fabs(v) < 32767.0f)) bad++;         // the conversion of such a value is undefined
             else if (std::fabs(v) > largest) largest = std::fabs(v);
             sample = v;
-            opens++;
         } else {
             sample = 0;
         }
@@ -188,10 +198,10 @@ int main(int argc, char** argv)
         char cmd[16] = "";
         if (std::sscanf(line, "%15s", cmd) != 1) continue;
         if (!std::strcmp(cmd, "new")) {
-            int inRate, ncoFreq, audioRate, mute, bp, op, ssbRate; float rf, vol, sq, ssbBw;
-            if (std::sscanf(line, "%*s %d %d %d %f %f %f %d %d %d %d %f", &inRate, &ncoFreq, &audioRate, &rf, &vol, &sq, &mute, &bp, &op, &ssbRate, &ssbBw) != 11) return 3;
+            int inRate, ncoFreq, audioRate, mute, bp, op, ssbRate, pllOn = 1; float rf, vol, sq, ssbBw;
+            if (std::sscanf(line, "%*s %d %d %d %f %f %f %d %d %d %d %f %d", &inRate, &ncoFreq, &audioRate, &rf, &vol, &sq, &mute, &bp, &op, &ssbRate, &ssbBw, &pllOn) < 11) return 3;
             delete d;
-            d = new Demod(inRate, ncoFreq, audioRate, rf, vol, sq, mute != 0, bp != 0, op, ssbRate, ssbBw, tr, trSb);
+            d = new Demod(inRate, ncoFreq, audioRate, rf, vol, sq, mute != 0, bp != 0, op, ssbRate, ssbBw, pllOn != 0, tr, trSb);
         } else if (!std::strcmp(cmd, "feed") && d) {
             long n;
             if (std::sscanf(line, "%*s %ld", &n) != 1) return 3;

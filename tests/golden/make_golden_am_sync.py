@@ -2,7 +2,7 @@
 Bandpass, MovingAverageUtil, DoubleBufferFIFO and StepFunctions (the .cpp files compiled where they lie, the rest are headers; Qt
 headers of the build image for qint16 & co.) and records tests/golden/am_sync_golden.npz for the cases of tests/am_sync_cases.py.
 
-    python tests/golden/make_golden_am_sync.py [--ref /root/reference]
+    python tests/golden/make_golden_am_sync.py [--ref /root/reference] [--random]
 
 Per case the fixture keeps the sha256 of the input (the generator is tests/am_sync_cases.py's, seeded), the audio count and the
 audio of every feed, and after every feed m_magsq, m_magsqSum, m_magsqPeak, m_magsqCount, the squelch state, getPllLocked() and
@@ -13,7 +13,13 @@ recorder's per-sample trace, for tests/test_am_sync_host.py.
 The maker asserts on the recording itself that the cases do what they are for: at least one ends locked and one unlocked; every
 sample before the conversion is finite and strictly inside the int16 range; a case that claims a reopening, a saturation branch, a
 never-open squelch or feeds on block edges has it; the host step reproduces every recorded oscillator value; the two SSBFilter
-designs give different audio."""
+designs give different audio.
+
+--random records tests/am_sync_cases.random_cases(), envelope channels included (the recorder's pll argument), into
+tests/golden/am_sync_random_golden.npz: per case the input digest, per feed the audio count and the sha256 of the audio, the
+levels and the state after every feed, the final `opens`, and once a `host` string as tests/golden/bfm_random_golden.npz has one.
+It stores digests, not audio; tests/test_am_sync_oracle.py compares the oracle with it case by case, and with the rebuilt recorder
+in full where the reference tree is present."""
 from __future__ import annotations
 
 import argparse
@@ -64,7 +70,8 @@ def record(exe: str, case: dict, iq: np.ndarray) -> dict:
     f32 = lambda v: "%.9g" % float(np.float32(v))
     ssb_rate, ssb_bw = sync[2] or 48000, sync[3] or 5000.0
     cmds = ["new %d %d %d %s %s %s %d %d %d %d %s" % (cfg[0], cfg[1], cfg[2], f32(cfg[3]), f32(cfg[4]), f32(cfg[5]), int(cfg[6]), int(cfg[7]),
-                                                      int(sync[1]), int(ssb_rate), f32(ssb_bw)), "design"]
+                                                      int(sync[1]), int(ssb_rate), f32(ssb_bw)) + " %d" % int(sync[0]),
+            "design"]
     for m in splits:
         cmds += [f"feed {int(m)}", "end"]
     subprocess.run([exe, fin, fout, ftr], input="\n".join(cmds) + "\n", text=True, check=True, timeout=600)
@@ -87,14 +94,48 @@ def record(exe: str, case: dict, iq: np.ndarray) -> dict:
             "taps": taps, "filt": filt, "coef": coef, "trace": ftr}
 
 
+def host_note() -> str:
+    import platform
+    try:
+        flags = next(l for l in open("/proc/cpuinfo") if l.startswith("flags")).split()
+    except (OSError, StopIteration):
+        flags = []
+    return f"{' '.join(platform.libc_ver())} {platform.machine()} fma={int('fma' in flags)}"
+
+
+def random_arrays(exe: str, cases: list) -> dict:
+    """what --random keeps of every case"""
+    from tests import am_sync_cases as sc
+    arrays = {"host": np.array(host_note())}
+    for c in cases:
+        x = sc.inputs(c)
+        r = record(exe, c, x)
+        name = c["name"]
+        arrays[f"{name}/in_sha256"] = np.array(sc.sha(x))
+        arrays[f"{name}/counts"] = np.array([f.size for f in r["feeds"]], np.int64)
+        arrays[f"{name}/audio_sha256"] = np.array([sc.sha(f) for f in r["feeds"]])
+        arrays[f"{name}/levels"] = r["levels"]
+        arrays[f"{name}/state"] = r["state"][:, :5]
+        arrays[f"{name}/opens"] = r["opens"][-1:]
+    return arrays
+
+
 def main():
     from tests import am_sync_cases as sc
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--out", default=os.path.join(HERE, "am_sync_golden.npz"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--random", action="store_true")
     args = ap.parse_args()
     if not available(args.ref):
         sys.exit("reference tree or Qt headers not found")
+    if args.random:
+        out = args.out or os.path.join(HERE, "am_sync_random_golden.npz")
+        cases = sc.random_cases()
+        np.savez_compressed(out, **random_arrays(build_recorder(args.ref), cases))
+        print(f"wrote {out}: {len(cases)} cases on {host_note()}, {os.path.getsize(out)} bytes")
+        return
+    args.out = args.out or os.path.join(HERE, "am_sync_golden.npz")
     exe, chk = build_recorder(args.ref), build_check()
     arrays, ends_locked, ends_unlocked, sat_cases = {}, 0, 0, 0
     audio_of = {}

@@ -2,7 +2,11 @@
 sequence, the loop step the device walk shares with the ChannelAnalyzer bank, the AGC terms as a rounded prefix sum, the delay
 selection, and every carry across feeds that end anywhere) on the host, against what the reference recorded per open sample
 (tests/golden/am_sync_golden.npz, the `trace` case): tests/am_sync_check.cpp.  Built with plain g++, and once more with the address
-and undefined-behaviour sanitizers; the stand-alone program alone runs under them."""
+and undefined-behaviour sanitizers; the stand-alone program alone runs under them.
+
+Two more traces come from tests/am_oracle.c (amo_trace, the recorder's layout), which tests/test_am_sync_oracle.py ties to the
+reference: USB at 1000 S/s, where the AGC history (250) is shorter than a block, and DSB at 48000 S/s, where it is 12000 -- the
+two regimes tests/test_am_sync_random_gpu.py takes the device to."""
 import os
 import subprocess
 import tempfile
@@ -80,3 +84,61 @@ def test_cut_is_clean_under_the_host_sanitizers(trace):
     exe = _build("am_sync_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     out = _chain(exe, trace, 3)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
+
+
+# ---------------------------------------------------------------- traces from the oracle
+#: indices into am_sync_cases.random_cases(): the forced USB case at 1000 S/s (hn < B) and the forced DSB case at 48000 S/s
+ORACLE_TRACES = {"usb_1000": 1, "dsb_48000": 6}
+
+
+@pytest.fixture(scope="module")
+def oracle_traces():
+    L = sc.build_oracle()
+    cases = sc.random_cases(max(ORACLE_TRACES.values()) + 1)
+    out = {}
+    for key, index in ORACLE_TRACES.items():
+        case = cases[index]
+        d = tempfile.mkdtemp()
+        tr, sb = os.path.join(d, "trace.bin"), os.path.join(d, "trace.bin.sb")
+        run = sc.run_oracle(L, case, trace=(tr, sb))
+        out[key] = (case, run, tr, sb)
+    return out
+
+
+def _chain_of(exe, case, tr, sb, seed):
+    return subprocess.run([exe, "chain", str(case["cfg"][2]), str(1 + case["sync"][1]), str(seed), tr, sb], capture_output=True, text=True, timeout=300)
+
+
+def _assert_chain(out, case, run):
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
+    samples, blocks, feeds = (int(v) for v in out.stdout.split()[1:4])
+    B = sc.block(case["sync"][1])
+    assert samples == run["sync_probe"]["open"] and blocks == samples // B == run["sync_probe"]["blocks"] >= 9 and feeds > 9, out.stdout
+
+
+@pytest.mark.parametrize("key", list(ORACLE_TRACES))
+@pytest.mark.parametrize("seed", [1, 20261021])
+def test_cut_equals_the_oracle_trace_across_random_feeds(check, oracle_traces, key, seed):
+    case, run, tr, sb = oracle_traces[key]
+    hn, B = sc.agc_len(case["cfg"][2]), sc.block(case["sync"][1])
+    assert (hn < B) if key == "usb_1000" else (hn > 8 * B)
+    assert run["sync_probe"]["reopenings"] >= 1 and run["sync_probe"]["wrapped"] > 0          # the chain stood still once; the history wrapped
+    _assert_chain(_chain_of(check, case, tr, sb, seed), case, run)
+
+
+@pytest.mark.parametrize("key", list(ORACLE_TRACES))
+def test_the_step_reproduces_the_oracle_trace(check, oracle_traces, key):
+    case, run, tr, _ = oracle_traces[key]
+    out = subprocess.run([check, "probe", str(case["cfg"][2]), tr], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("probe "), out.stdout + out.stderr
+    n, sat_hi, sat_lo, up, down, bad, locked, freq = (int(v) for v in out.stdout.split()[1:])
+    sp = run["sync_probe"]
+    assert bad == 0 and n == sp["open"] and [sat_hi, sat_lo, up, down] == [sp["sat_hi"], sp["sat_lo"], sp["lock_up"], sp["lock_down"]], out.stdout
+    assert [locked, freq] == list(run["state"][-1, 3:5])
+
+
+def test_cut_is_clean_under_the_host_sanitizers_on_the_oracle_traces(oracle_traces):
+    exe = _build("am_sync_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    for key in ORACLE_TRACES:
+        case, run, tr, sb = oracle_traces[key]
+        _assert_chain(_chain_of(exe, case, tr, sb, 3), case, run)
