@@ -1520,6 +1520,120 @@ int sdrx_atv_get_timing(sdrx_atv_t* h, double* total_ms, int64_t* feeds, int res
 int sdrx_atv_last_launch(const sdrx_atv_t* h, char* kernel_name, int name_cap,
                          int* grid, int* block, int* lds_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * DATV receiver bank: the sample-rate half of N DATVDemod instances (plugins/channelrx/demoddatv/datvdemod.cpp with leansdr's
+ * sdr.h) on one device, the 16-bit build.  Input: int16 I/Q at the channelizer's output rate.  Per input sample
+ * Complex(re, im) * m_objNCO.nextIQ() with setFreq(-centre_frequency, msps), m_objRFFilter->runFilt (fftfilt(.., 1024) with
+ * create_filter(-+ rf_bandwidth / 2 / msps)), and on its 512-sample blocks cstln_receiver<f32>::run with the configured sampler,
+ * a chunk of 128 samples whenever 128 + readahead are there.  Output per feed: what p_symbols (soft symbols), p_sampled (one
+ * constellation point per chunk with a symbol) and p_freq / p_ss / p_mer (one measurement per meas_decimation samples) have
+ * received once the scheduler has run dry, and the receiver's state.  Everything from p_symbols on (deconvolution, mpeg_sync, the
+ * deinterleaver, Reed-Solomon, the derandomizer, the player) stays with the host.  Symbols, points, measurements and state are bit
+ * for bit those of the strict-IEEE scalar build of the reference.
+ *   - samples that do not fill a chunk, and a partial 512-block of the filter, stay in the channel: a feed of 1 sample is legal and
+ *     usually returns nothing.  The output does not depend on how the stream is cut into feeds.
+ *   - the tables are design, built on the host at create: trig16 (65536 (cos, sin), one copy per handle), one cstln_lut<256> per
+ *     distinct (modulation, fec, hard_metric) in the handle, the RRC coefficients per channel.  Their sinf / cosf are
+ *     pll_math.hpp's restatement of glibc's (also inside filtergen::root_raised_cosine, whose sqrt / sin / cos of floats are the
+ *     float overloads), their atan2f is udp_atan2f (glibc 2.35's), sqrtf is IEEE: the design does not follow the machine's libm.
+ *   - a measurement holds freq_tap and the three estimates as the device left them; ss = sqrtf(est_insp) and
+ *     mer = est_ep ? 10 * logf(est_sp / est_ep) / logf(10) : 0 are computed inside sdrx_datv_read_meas, on the host: logf of the
+ *     quotient by the calling process's libm, logf(10) as the constant the library's compiler folded it to (as the reference's is): logf
+ *     is the one routine of the loop that is not correctly rounded everywhere, and it feeds nothing back.
+ *   - casts.  trig16::expi(float a) is (uint16_t)(int16_t)(int32_t) a and cstln_lut::lookup casts through s8 behind its halving
+ *     loop.  x86-64 converts a float that no int32 holds, NaN included, to INT_MIN, the device saturates; both agree for
+ *     |a| < 2^31.  The bank converts as x86-64 does for EVERY float, so nothing hangs on the range; the loop stays inside it
+ *     anyway: phase is reduced by fmodf(phase, 65536) after every chunk and moves by 128 freqw + at most 128 * 0.04 * 32768 inside
+ *     one, and freqw is held within 65536 / omega / n / 2 of 0 unless allow_drift is set.  With allow_drift freqw is a sum of
+ *     phase_error * freq_beta terms, |.| <= 32768 * 0.0012 each, so it takes more than 4 * 10^5 symbols of one sign to pass
+ *     2^31 / 128 = 2^24, where -(phase + freqw) would leave the int32 range within a chunk; beyond that the reference's own behaviour
+ *     is "undefined" (math.h) and the bank's is x86-64's.  lookup's halving loop is cut after 300 rounds, which no finite value
+ *     needs; the reference spins forever on an infinity.
+ *   - refused by create with SDRX_EINVAL and a text: notch_filters > 0 (auto_notch); 16APSK / 32APSK at a code rate
+ *     make_dvbs2_constellation has no radii for; rolloff <= 0 with the RRC sampler (its order divides by it); an RRC with more
+ *     than 4096 coefficients or more than 64 taps per symbol (ceil(ncoeffs / rrc_steps)): the walk keeps shifted_coeffs in LDS and
+ *     gives a tap to a lane (the reference itself stops at 128 + readahead > 16384, BUF_BASEBAND); a meas_decimation under 64;
+ *     rates that are not positive, symbol_rate > sample_rate.
+ *   - left out: r_cnr (cfg.cnr is never set), m_objMagSqAverage (GUI only), the constellation screen, EXTENDED_DIRECT_SAMPLE, the
+ *     24-bit build, a mid-stream reconfiguration (a new configuration is a new handle).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sdrx_datv sdrx_datv_t;
+typedef struct sdrx_datv_cfg {
+    int32_t msps;                 /* channelizer output rate (intMsps): the NCO's and the RF filter's */
+    int32_t sample_rate;          /* Fs (intSampleRate; DATVDemod sets it to msps) */
+    int32_t centre_frequency;     /* m_objNCO.setFreq(-centre_frequency, msps) */
+    int32_t rf_bandwidth;         /* create_filter(-rf_bandwidth / 2 / msps, +rf_bandwidth / 2 / msps) */
+    int32_t symbol_rate;          /* Fm */
+    int32_t modulation;           /* DATVModulation: 0 BPSK, 1 QPSK, 2 8PSK, 3 16APSK, 4 32APSK, 5 64APSKe, 6 16QAM, 7 64QAM, 8 256QAM */
+    int32_t fec;                  /* leansdr::code_rate: 0 1/2, 1 2/3, 2 4/6, 3 3/4, 4 5/6, 5 7/8, 6 4/5, 7 8/9, 8 9/10 */
+    int32_t standard;             /* dvb_version: 0 DVB-S, 1 DVB-S2 (a warning in the reference, nothing else before p_symbols) */
+    int32_t sampler;              /* dvb_sampler: 0 nearest, 1 linear, 2 RRC */
+    float   rolloff;              /* fltRollOff, 0 .. 1 */
+    int32_t excursion;            /* intExcursion: rrc_rej, dB */
+    int32_t hard_metric;          /* cstln->harden() */
+    int32_t viterbi;              /* pll_adjustment /= 6 */
+    int32_t allow_drift;
+    int32_t notch_filters;        /* must be 0 */
+    float   finfo;                /* Finfo, Hz: meas_decimation = max(1, (int)(Fs / finfo)); 0: the reference's 5 */
+} sdrx_datv_cfg;
+typedef struct sdrx_datv_state_t { /* cstln_receiver's and fir_sampler's members after the last feed; floats as their bits */
+    uint32_t mu, phase, freqw, agc_gain;
+    uint32_t est_insp, est_sp, est_ep;
+    uint32_t meas_count;
+    int32_t update_freq_phase;
+    uint32_t hist_p[3][2], hist_c[3][2];   /* hist[k].p and hist[k].c as (re, im) */
+    int32_t held;                 /* filtered samples held back: fewer than 128 + readahead */
+    int64_t chunks;               /* chunks run since creation or reset */
+    int64_t n_in;                 /* filtered samples the receiver was given since creation or reset */
+    int64_t n_symbols;            /* soft symbols written since creation or reset */
+} sdrx_datv_state_t;
+typedef struct sdrx_datv_design_t {
+    float   omega, min_omega, max_omega, min_freqw, max_freqw, freq_beta;
+    int32_t meas_decimation, rrc_steps, ncoeffs, readahead, nsymbols;
+    int32_t nco_inc;
+} sdrx_datv_design_t;
+typedef struct sdrx_datv_meas_t { /* freq_out, ss_out, mer_out and the three estimates behind them */
+    float freq, ss, mer;
+    float est_insp, est_sp, est_ep;
+} sdrx_datv_meas_t;
+int sdrx_datv_create(sdrx_datv_t** out, int device, int32_t n_ch, const sdrx_datv_cfg* cfg);
+int sdrx_datv_destroy(sdrx_datv_t* h);
+/* the state of a fresh handle with the same configuration */
+int sdrx_datv_reset(sdrx_datv_t* h);
+/* iq[c] / n_per_ch[c]: channel c's new samples (what DownChannelizer handed to DATVDemod::feed) */
+int sdrx_datv_feed(sdrx_datv_t* h, const int16_t* const* iq, const int64_t* n_per_ch);
+/* same on device pointers (4-byte aligned), asynchronous on the handle's stream */
+int sdrx_datv_feed_dev(sdrx_datv_t* h, const int16_t* const* d_iq, const int64_t* n_per_ch);
+/* hand-over from a channel bank without a host round trip, ordered on the device like sdrx_backend_feed_bank */
+int sdrx_datv_feed_bank(sdrx_datv_t* h, sdrx_chan_bank_t* bank);
+/* the soft symbols of the last feed: softsymbol::cost and ::symbol, either array may be NULL; returns the count written (<0: error) */
+int64_t sdrx_datv_read(sdrx_datv_t* h, int32_t ch, int16_t* cost, uint8_t* symbol, int64_t cap);
+/* the constellation points of the last feed as (re, im) pairs: one per chunk that had a symbol; returns the count of pairs */
+int64_t sdrx_datv_read_points(sdrx_datv_t* h, int32_t ch, float* iq, int64_t cap);
+/* the measurements of the last feed; ss and mer are computed here, on the host */
+int64_t sdrx_datv_read_meas(sdrx_datv_t* h, int32_t ch, sdrx_datv_meas_t* out, int64_t cap);
+/* device-side views (valid until the next feed); any pointer may be NULL.  d_meas points at records of four floats: freq_tap,
+ * est_insp, est_sp, est_ep */
+int sdrx_datv_last_dev(sdrx_datv_t* h, int32_t ch, const int16_t** d_cost, const uint8_t** d_symbol, int64_t* n);
+int sdrx_datv_points_last_dev(sdrx_datv_t* h, int32_t ch, const float** d_iq, int64_t* n);
+int sdrx_datv_meas_last_dev(sdrx_datv_t* h, int32_t ch, const float** d_meas, int64_t* n);
+int sdrx_datv_state(sdrx_datv_t* h, int32_t ch, sdrx_datv_state_t* s);
+int sdrx_datv_get_design(sdrx_datv_t* h, int32_t ch, sdrx_datv_design_t* d);
+/* the design's tables, for inspection (any pointer may be NULL): the RRC coefficients (returns their count, 0 without the RRC
+ * sampler; at most coeffs_cap are written), trig16 as 65536 (cos, sin) pairs, the constellation table as 65536 records of 8 bytes
+ * -- int16 cost, int16 phase_error, uint8 symbol, three zero bytes; record I * 256 + Q is lut[(u8) I][(u8) Q] -- and symbols[] as
+ * 256 (re, im) pairs of int8, nsymbols of them set.  <0: error */
+int sdrx_datv_get_tables(sdrx_datv_t* h, int32_t ch, float* coeffs, int32_t coeffs_cap, float* trig_iq, void* lut, int8_t* symbols);
+int sdrx_datv_sync(sdrx_datv_t* h);
+int sdrx_datv_set_stream(sdrx_datv_t* h, void* hip_stream);
+int sdrx_datv_get_stream(sdrx_datv_t* h, void** hip_stream);
+/* as sdrx_decim_set_timing: brackets each feed's kernels, the front's included */
+int sdrx_datv_set_timing(sdrx_datv_t* h, int enabled);
+int sdrx_datv_get_timing(sdrx_datv_t* h, double* total_ms, int64_t* feeds, int reset);
+/* the walk of the last feed: datv_walk_kernel, its grid, block and LDS bytes */
+int sdrx_datv_last_launch(const sdrx_datv_t* h, char* kernel_name, int name_cap,
+                          int* grid, int* block, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

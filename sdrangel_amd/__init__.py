@@ -310,6 +310,21 @@ def lib() -> C.CDLL:
         "sdrx_atv_state": (C.c_int, [vp, i32, vp]),
         "sdrx_atv_get_design": (C.c_int, [vp, i32, vp]),
         "sdrx_atv_get_filters": (C.c_int, [vp, i32, C.POINTER(i32), vp, i32, vp, vp]),
+        "sdrx_datv_create": (C.c_int, [pp, C.c_int, i32, vp]),
+        "sdrx_datv_destroy": (C.c_int, [vp]),
+        "sdrx_datv_reset": (C.c_int, [vp]),
+        "sdrx_datv_feed": (C.c_int, [vp, vp, vp]),
+        "sdrx_datv_feed_dev": (C.c_int, [vp, vp, vp]),
+        "sdrx_datv_feed_bank": (C.c_int, [vp, vp]),
+        "sdrx_datv_read": (i64, [vp, i32, vp, vp, i64]),
+        "sdrx_datv_read_points": (i64, [vp, i32, vp, i64]),
+        "sdrx_datv_read_meas": (i64, [vp, i32, vp, i64]),
+        "sdrx_datv_last_dev": (C.c_int, [vp, i32, pp, pp, C.POINTER(i64)]),
+        "sdrx_datv_points_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_datv_meas_last_dev": (C.c_int, [vp, i32, pp, C.POINTER(i64)]),
+        "sdrx_datv_state": (C.c_int, [vp, i32, vp]),
+        "sdrx_datv_get_design": (C.c_int, [vp, i32, vp]),
+        "sdrx_datv_get_tables": (C.c_int, [vp, i32, vp, i32, vp, vp, vp]),
         "sdrx_firbank_feed": (C.c_int, [vp, vp, vp, vp]),
         "sdrx_firbank_get_taps": (C.c_int, [vp, i32, vp, i32]),
         "sdrx_sdriq_parse_header": (C.c_int, [vp, C.c_uint64, vp]),
@@ -338,7 +353,7 @@ def lib() -> C.CDLL:
     five = ("sync", "set_stream", "set_timing", "get_timing", "last_launch")
     families = {"decim": five, "fdecim": five, "chan_bank": five + ("get_stream",), "spectrum": five + ("get_stream",),
                 "wfm": five + ("get_stream",), "bfm": five + ("get_stream",), "am": five + ("get_stream",), "nfm": five + ("get_stream",),
-                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "lora": five + ("get_stream",), "atv": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
+                "ssb": five + ("get_stream",), "udpsrc": five + ("get_stream",), "chana": five + ("get_stream",), "lora": five + ("get_stream",), "atv": five + ("get_stream",), "datv": five + ("get_stream",), "dccorr": five[:2], "iqimb": five[:2],
                 "backend": five[:1], "audiotail": five[:1], "decim24": five[:1], "chan24_bank": five[:1]}
     for prefix, names in families.items():
         for name in names:
@@ -1352,6 +1367,92 @@ class ATVBank(_DemodBank):
         p, r, c = C.c_void_p(), C.c_int32(), C.c_int32()
         self._call("screen_last_dev", ch, C.byref(p), C.byref(r), C.byref(c))
         return p.value or 0, r.value, c.value
+
+
+class DatvCfg(C.Structure):
+    """sdrx_datv_cfg: one DATVDemod down to p_symbols (msps, the arguments of DATVDemod::configure, finfo)"""
+    _fields_ = [("msps", C.c_int32), ("sample_rate", C.c_int32), ("centre_frequency", C.c_int32), ("rf_bandwidth", C.c_int32),
+                ("symbol_rate", C.c_int32), ("modulation", C.c_int32), ("fec", C.c_int32), ("standard", C.c_int32), ("sampler", C.c_int32),
+                ("rolloff", C.c_float), ("excursion", C.c_int32), ("hard_metric", C.c_int32), ("viterbi", C.c_int32), ("allow_drift", C.c_int32),
+                ("notch_filters", C.c_int32), ("finfo", C.c_float)]
+
+
+class DatvState(C.Structure):
+    """sdrx_datv_state_t: cstln_receiver's and fir_sampler's members, floats as their bits"""
+    _fields_ = [(k, C.c_uint32) for k in ("mu", "phase", "freqw", "agc_gain", "est_insp", "est_sp", "est_ep", "meas_count")] + [
+        ("update_freq_phase", C.c_int32), ("hist_p", C.c_uint32 * 6), ("hist_c", C.c_uint32 * 6), ("held", C.c_int32), ("chunks", C.c_int64),
+        ("n_in", C.c_int64), ("n_symbols", C.c_int64)]
+
+
+class DatvDesign(C.Structure):
+    """sdrx_datv_design_t"""
+    _fields_ = [(k, C.c_float) for k in ("omega", "min_omega", "max_omega", "min_freqw", "max_freqw", "freq_beta")] + [
+        (k, C.c_int32) for k in ("meas_decimation", "rrc_steps", "ncoeffs", "readahead", "nsymbols", "nco_inc")]
+
+
+#: sdrx_datv_meas_t as a numpy record: freq_out, ss_out, mer_out and the three estimates behind them
+DATV_MEAS = np.dtype([(k, np.float32) for k in ("freq", "ss", "mer", "est_insp", "est_sp", "est_ep")])
+
+
+class DatvBank(_DemodBank):
+    """N DATV receivers (DATVDemod::feed down to p_symbols): int16 I/Q at the channelizer's output rate in; soft symbols, constellation
+    points, measurements and the receiver's state out."""
+    _prefix, _cfg = "datv", DatvCfg
+
+    def _count(self, name: str, *args) -> int:
+        n = self._fn(name)(self._h, *args)
+        if n < 0:
+            raise SdrxError(f"sdrx_datv_{name} rc={n}: {lib().sdrx_last_error().decode()}")
+        return n
+
+    def last_dev(self, ch: int):
+        """(device pointer to the costs, device pointer to the symbols, count) of the last feed's soft symbols"""
+        pc, ps, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._call("last_dev", ch, C.byref(pc), C.byref(ps), C.byref(n))
+        return pc.value or 0, ps.value or 0, n.value
+
+    def read(self, ch: int, cap: int | None = None):
+        """the soft symbols of the last feed: (cost int16, symbol uint8)"""
+        if cap is None:
+            cap = self.last_dev(ch)[2]
+        cost, sym = np.empty(max(cap, 1), np.int16), np.empty(max(cap, 1), np.uint8)
+        n = self._count("read", ch, cost.ctypes.data, sym.ctypes.data, cap)
+        return cost[:n].copy(), sym[:n].copy()
+
+    def points(self, ch: int) -> np.ndarray:
+        """the constellation points of the last feed, one per chunk that had a symbol: float32 [n, 2]"""
+        p, n = C.c_void_p(), C.c_int64()
+        self._call("points_last_dev", ch, C.byref(p), C.byref(n))
+        out = np.empty((max(n.value, 1), 2), np.float32)
+        return out[:self._count("read_points", ch, out.ctypes.data, n.value)].copy()
+
+    def meas(self, ch: int) -> np.ndarray:
+        """the measurements of the last feed as DATV_MEAS records; ss and mer are computed on the host"""
+        p, n = C.c_void_p(), C.c_int64()
+        self._call("meas_last_dev", ch, C.byref(p), C.byref(n))
+        out = np.zeros(max(n.value, 1), DATV_MEAS)
+        return out[:self._count("read_meas", ch, out.ctypes.data, n.value)].copy()
+
+    def state(self, ch: int) -> DatvState:
+        st = DatvState()
+        self._call("state", ch, C.byref(st))
+        return st
+
+    def design(self, ch: int) -> DatvDesign:
+        d = DatvDesign()
+        self._call("get_design", ch, C.byref(d))
+        return d
+
+    def tables(self, ch: int):
+        """(RRC coefficients, trig16 as 131072 floats, the constellation table as 65536 x 8 bytes, symbols[] as 512 int8)"""
+        co, tr, lut, sy = np.zeros(4096, np.float32), np.zeros(2 * 65536, np.float32), np.zeros(65536 * 8, np.uint8), np.zeros(512, np.int8)
+        nc = self._count("get_tables", ch, co.ctypes.data, co.size, tr.ctypes.data, lut.ctypes.data, sy.ctypes.data)
+        return co[:nc].copy(), tr, lut, sy
+
+    def table_digests(self, ch: int) -> list:
+        """sha256 of the four tables, in tables()'s order"""
+        import hashlib
+        return [hashlib.sha256(np.ascontiguousarray(t).tobytes()).hexdigest() for t in self.tables(ch)]
 
 
 class LoraDemodBank(_DemodBank):
