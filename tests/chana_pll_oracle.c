@@ -14,6 +14,7 @@
  *                                (out[1..3] hold the uint32 bit patterns), out[4] = m_magsq
  *   chapo_probe(h, out[8])      saturations above / below, normalizeAngle with more than one turn, lock counter ups / downs,
  *                                cos / sin arguments past 120, arg(0), steps
+ *   chapo_seek(h, filtered_samples)   chao_seek of the front; the loops do not depend on the stream position
  */
 #include "chana_oracle.c"
 
@@ -124,3 +125,6 @@ void chapo_state(void* p, double* out)
 }
 
 void chapo_probe(void* p, long* out) { memcpy(out, ((chapo*)p)->l.probe, sizeof(long) * 8); }
+
+/* the stream position is the front's alone: the loop state does not depend on it */
+void chapo_seek(void* p, uint64_t filtered) { chao_seek(((chapo*)p)->a, filtered); }

@@ -1,15 +1,20 @@
 """Builds tests/golden/chana_pll_rec.cpp against the reference's own PhaseLockComplex, FreqLockComplex, NCOF, Interpolator, fftfilt
 and fftcorr (sdrbase/dsp/*.cpp compiled where they lie; Qt headers of the build image for qint16 & co.) and records
-tests/golden/chana_pll_golden.npz for the cases of tests/chana_pll_cases.py.
+tests/golden/chana_pll_golden.npz for the cases of tests/chana_pll_cases.py, and tests/golden/chana_random_golden.npz for its 100
+random cases.
 
     python tests/golden/make_golden_chana_pll.py [--ref /root/reference]
 
 Per case the fixture keeps the inputs, the Sample count of every feed, the Sample stream, and after every feed m_magsq,
 isPllLocked and the bits of getPllFrequency, getPllDeltaPhase and getPllPhase.  `host` notes the libm the recorder ran on: the
-loops call its cosf, sinf and atan2f, and feed back what they return."""
+loops call its cosf, sinf and atan2f, and feed back what they return.
+
+The random cases' fixture holds digests only, every feed of every case in one row of flat arrays (`feeds` has the feeds per case):
+the Sample count, a SHA-256 of the feed's Samples, m_magsq, isPllLocked and the three floats' bits."""
 from __future__ import annotations
 
 import argparse
+import hashlib
 import os
 import platform
 import subprocess
@@ -74,6 +79,19 @@ def record(exe: str, cfg: dict, iq: np.ndarray, splits, timed: bool = False) -> 
     return res
 
 
+def sha(a: np.ndarray) -> np.ndarray:
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a, np.int16).tobytes()).digest(), np.uint8)
+
+
+def digest(cases, results) -> dict:
+    """the arrays of chana_random_golden.npz from one result per case (the recorder's, or the oracle's to compare with)"""
+    flat = [(o, s) for r in results for o, s in zip(r["out"], r["states"])]
+    return {"names": np.array([c["name"] for c in cases]), "feeds": np.array([len(r["out"]) for r in results], np.int32),
+            "counts": np.array([o.shape[0] for o, _ in flat], np.int64), "sha": np.stack([sha(o) for o, _ in flat]),
+            "locked": np.array([s[0] for _, s in flat], np.int32), "state_bits": np.array([s[1:4] for _, s in flat], np.uint32).reshape(-1, 3),
+            "magsq": np.array([s[4] for _, s in flat], np.float64)}
+
+
 def cat(parts) -> np.ndarray:
     return np.concatenate(parts) if parts else np.zeros((0, 2), np.int16)
 
@@ -83,6 +101,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(HERE, "chana_pll_golden.npz"))
+    ap.add_argument("--random-out", default=os.path.join(HERE, "chana_random_golden.npz"))
     args = ap.parse_args()
     if not available(args.ref):
         sys.exit("reference tree or Qt headers not found")
@@ -100,6 +119,10 @@ def main():
         arrays[f"{name}/magsq"] = np.array([s[4] for s in r["states"]], np.float64)
     np.savez_compressed(args.out, **arrays)
     print(f"wrote {args.out}: {len(pc.CASES)} cases on {host_note()}, {os.path.getsize(args.out)} bytes")
+    cases = pc.random_cases()
+    arrays = digest(cases, [record(exe, c["cfg"], pc.inputs(c), c["splits"]) for c in cases])
+    np.savez_compressed(args.random_out, host=np.array(host_note()), **arrays)
+    print(f"wrote {args.random_out}: {len(cases)} random cases, {os.path.getsize(args.random_out)} bytes")
 
 
 if __name__ == "__main__":

@@ -3,7 +3,12 @@ sdrx_chanapll_*; its cosf, sinf and atan2f are its own) against the reference's 
 Interpolator, fftfilt and fftcorr: every case of tests/chana_pll_cases.py recorded by tests/golden/make_golden_chana_pll.py into
 tests/golden/chana_pll_golden.npz (the Samples, m_magsq, isPllLocked and the bits of the three floats after every feed), all bit
 for bit: the loops feed back, so nothing less means anything.  Probe counters show that a case reaches what it is named for.
-Where the reference tree and Qt are present, a `ref` test rebuilds the recorder and compares 100 random configurations."""
+Where the reference tree and Qt are present, a `ref` test rebuilds the recorder and compares 100 random configurations.
+
+The 100 random cases (random_cases(): a signal made for every channel, n sized in closed groups) are what the GPU runs in wide banks
+(tests/test_chana_random_gpu.py).  Here their shares are asserted on the oracle's probes, the oracle's runs are compared with the
+recorder's digests (tests/golden/chana_random_golden.npz: counts, a SHA-256 of every feed's Samples, m_magsq, isPllLocked and the
+state bits), and a second `ref` test compares every Sample with the live recorder."""
 import os
 
 import numpy as np
@@ -31,6 +36,20 @@ def golden():
 def runs(oracle, golden):
     """every case through the oracle once, on the fixture's inputs, shared by the tests below"""
     return {c["name"]: pc.run_oracle(oracle, c["cfg"], pc.cut(golden[f"{c['name']}/in"], c["splits"])) for c in pc.CASES}
+
+
+@pytest.fixture(scope="module")
+def random_runs(oracle):
+    """the 100 random cases through the oracle once"""
+    cases = pc.random_cases()
+    return cases, [pc.run_case(oracle, c) for c in cases]
+
+
+def _maker():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_golden_chana_pll as mg
+    return mg
 
 
 def _cat(parts):
@@ -123,3 +142,44 @@ def test_ref_recorder_on_random_configurations(oracle):
         assert got["states"] == want["states"], (i, cfg, got["states"], want["states"])
         kinds.add((cfg["pll"], cfg["fll"], cfg["input_type"]))
     assert len(kinds) >= 10, kinds
+
+
+def test_random_cases_cover_the_branches(random_runs):
+    cases, results = random_runs
+    assert len(cases) == 100 and len({c["name"] for c in cases}) == 100
+    assert cases == pc.random_cases()                         # drawn in order from one generator with a fixed seed
+    pc.assert_random_shares(cases, results)
+
+
+def test_random_cases_match_the_reference_digests(random_runs):
+    """ties the oracle to the reference where the reference does not exist: the recorder's digests of every feed of every case"""
+    cases, results = random_runs
+    want = np.load(os.path.join(ROOT, "tests", "golden", "chana_random_golden.npz"))
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "chana_random_golden.npz")) < os.path.getsize(GOLDEN)
+    host = str(want["host"])
+    assert "glibc" in host and "fma=1" in host, host
+    got = _maker().digest(cases, results)
+    assert set(got) | {"host"} == set(want.files)
+    assert got["names"].tolist() == want["names"].tolist() and got["feeds"].tolist() == want["feeds"].tolist()
+    ends = np.cumsum(got["feeds"])
+    for k in ("counts", "sha", "locked", "state_bits", "magsq"):
+        bad = np.flatnonzero((got[k] != want[k]).reshape(len(got[k]), -1).any(axis=1))
+        assert got[k].shape == want[k].shape and not bad.size, (k, [cases[int(np.searchsorted(ends, b, side="right"))]["name"] for b in bad[:5]])
+    assert want["counts"].sum() > 400000 and want["locked"].sum() > 60
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "sdrbase", "dsp")), reason="reference tree not present")
+def test_ref_recorder_on_random_cases(random_runs):
+    """all 100 through the live recorder: every Sample of every feed, m_magsq, locked and the three state floats as bits"""
+    mg = _maker()
+    if not mg.available(REF):
+        pytest.skip("Qt headers not present")
+    if "glibc" not in mg.host_note() or "fma=1" not in mg.host_note():
+        pytest.skip("the recorder would call a libm other than the fused glibc build the oracle restates")
+    exe = mg.build_recorder(REF)
+    cases, results = random_runs
+    for c, got in zip(cases, results):
+        want = mg.record(exe, c["cfg"], pc.inputs(c), c["splits"])
+        assert [g.shape for g in got["out"]] == [w.shape for w in want["out"]], c
+        assert all(np.array_equal(g, w) for g, w in zip(got["out"], want["out"])), c
+        assert got["states"] == want["states"], (c, got["states"], want["states"])

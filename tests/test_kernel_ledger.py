@@ -78,7 +78,11 @@ def test_every_kernel_of_the_library_is_launched_by_the_gpu_suite():
 MIN_GRID = {"decim_fast_kernel<": (3, 2), "decim_chain_kernel<": (3, 2), "hist_update_kernel": (2, 2), "fdecim_chain_kernel<": (2, 1),
             "tree_kernel<": (2, 2), "tree_mx_kernel": (2, 2), "tree_hist_kernel": (2, 2), "wide_pass_kernel<48>": (2, 2),
             "wfm_prep_kernel": (2, 1), "wfm_sched_walk_kernel": (2, 1), "be_sched_dyadic_prep_kernel": (2, 1), "be_schedule_kernel": (2, 1),
-            "am_psum_kernel": (2, 1), "nfm_psum_kernel": (2, 1), "ssb_psum_kernel": (2, 1), "udp_psum_kernel": (2, 1)}
+            "am_psum_kernel": (2, 1), "nfm_psum_kernel": (2, 1), "ssb_psum_kernel": (2, 1), "udp_psum_kernel": (2, 1),
+            # the ChannelAnalyzer bank: four channels per workgroup of the walk, 64 per workgroup of the NCOF phase walk; the channel is
+            # blockIdx.y of the group, post, corr and emit kernels and blockIdx.x of the carry
+            "chana_walk_kernel": (2, 1), "be_ncof_kernel": (2, 1), "chana_group_kernel": (1, 2), "chana_post_kernel": (1, 2),
+            "chana_corr_kernel": (1, 2), "chana_emit_kernel": (1, 2), "chana_carry_kernel": (2, 1)}
 
 
 def test_block_indexed_kernels_ran_with_more_than_one_workgroup():
